@@ -16,9 +16,13 @@ N GPUs = N processes (torch.distributed over RCCL), each with its own frames ("w
 all_gather of per-frame keypoint counts.  `python bench.py --gpus N` starts the N ranks itself (fresh child processes, spawned
 before this process touches torch or HIP); under torchrun (RANK / WORLD_SIZE set) it is one of the ranks.
 
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0: the headline (metric, value, unit, ms_per_step, ...) and the workload's config.  With --full it
+also holds what takes runs or checks of its own, outside the timed region:
+  "value_device_resident", "stage_ms_per_step", host / GPU-side step times,
   "roofline"     -- pyramid+FAST(+blur) pass: algorithmic bytes / live HIP-event span of those launches
+  "host_copy_matches_device", "match_leg_matches_oracle" (c3: "stereo_and_triangulation_match_oracle") -- the last step vs the oracle
   "cpu_baseline" -- the CPU oracle (a port, 1 thread) on a bounded sample of the same frames (+ an nproc-thread context figure).
+--dump-outputs DIR writes the results of the last timed step as they reached the host (OrbWorkload.outputs()).
 """
 import argparse
 import ctypes as C
@@ -71,8 +75,16 @@ def parse_args(argv=None):
                     help="synthetic input class (orb-slam3_amd/synth.py): dense = SURVEY 8(d)'s generator (the headline; ~6 %% of the level-0 "
                          "pixels are FAST corners), sparse = camera-like density (~2 %%), lowcontrast = corners mostly below iniThFAST "
                          "(per-cell threshold retry), mixed = the three classes side by side in every batch")
-    ap.add_argument("--cpu-sample", type=int, default=96, help="frames timed through the CPU oracle (0 = skip)")
-    return ap.parse_args(argv)
+    ap.add_argument("--cpu-sample", type=int, default=96, help="frames timed through the CPU oracle (0 = skip; --full only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the device-resident loop, per-stage times, rooflines, the host copy and the match leg "
+                         "checked against the oracle, the CPU baseline (off by default: a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) as DIR/<name>.npy, float32 / float64")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -144,6 +156,9 @@ class StubWorkload:
     def counts(self):
         import numpy as np
         return np.full(self.B, 1000 + self.rank, np.int32)
+
+    def outputs(self):
+        return {"counts": self.counts().astype("float64")}
 
 
 class OrbWorkload:
@@ -378,6 +393,62 @@ class OrbWorkload:
         """per-frame keypoint counts of the most recent batch, straight from the device"""
         out = self.np.zeros(self.B, self.np.int32)
         self.L.orbx_memcpy_d2h(out.ctypes.data_as(C.c_void_p), self.res[(self.k - 1) % self.nblk]["counts"], 4 * self.B)
+        return out
+
+    def outputs(self):
+        """What the most recent step handed to the host (its pinned result block), for --dump-outputs: every frame's keypoint
+        count and mono index; for a fixed, seeded sample of the frames (stereo configs: of the pairs, both images) the keypoints
+        (x, y, size, angle, response, octave, class_id), descriptors (byte values) and the match leg's rows.  Only the valid head
+        of a row is taken (a row's tail holds whatever an earlier batch left there)."""
+        np, B, cap = self.np, self.B, self.cap
+        hb = self.h_blk[(self.k - 1) % self.nblk].bytes
+        ok_, od_, on_, om_, _ = self.layout
+        n = hb[on_:on_ + 4 * B].view(np.int32)
+        kps = hb[ok_:ok_ + 28 * cap * B].view(self.pkg.KP_DTYPE).reshape(B, cap)
+        desc = hb[od_:od_ + 32 * cap * B].reshape(B, cap, 32)
+
+        def arr(off, key, dtype, shape):
+            return hb[off[key]:off[key] + int(np.prod(shape)) * np.dtype(dtype).itemsize].view(dtype).reshape(shape)
+
+        def rows(a, sel, lens):                                 # the valid heads of the sampled rows, one after another
+            parts = [a[i, :lens[i]] for i in sel]
+            return (np.concatenate(parts) if parts else a[:0, 0]).astype(np.float64)
+
+        stereo = self.cfg in ("c3", "c4")
+        P = B // 2 if stereo else B
+        per = (2 if stereo else 1) * cap * (7 * 8 + 32 * 4 + 4 * 8)   # dumped bytes per sampled frame / pair, at most
+        sel = np.sort(np.random.default_rng(0).choice(P, max(1, min(P, 16, (48 << 20) // per)), replace=False))
+        frames = np.concatenate([sel, sel + P]) if stereo else sel
+        kp = [kps[i, :n[i]] for i in frames]
+        out = {"counts": n.astype(np.float64), "monos": hb[om_:om_ + 4 * B].view(np.int32).astype(np.float64),
+               "sample": sel.astype(np.float64),
+               "keypoints": np.concatenate([np.stack([k[f].astype(np.float64) for f in k.dtype.names], axis=-1) for k in kp]),
+               "descriptors": np.concatenate([desc[i, :n[i]] for i in frames]).astype(np.float32)}
+        if self.cfg in ("c2", "c5") and B > 1:
+            off = self.mo_off
+            if self.args.match == "window":                     # row p: frame p+1's matches into frame p, one per keypoint of p
+                train = [p for p in sel if p < B - 1]
+                out["matches"] = rows(arr(off, "match", np.int32, (B, cap)), train, n)
+                out["matches_per_frame"] = arr(off, "nm", np.int32, (B,))[:B - 1].astype(np.float64)
+            else:                                               # row q: 2-NN of frame q's keypoints in frame q-1
+                query = [q for q in sel if q >= 1]
+                out["knn2_idx"] = rows(arr(off, "idx2", np.int32, (B, cap, 2)), query, n)
+                out["knn2_dist"] = rows(arr(off, "dist2", np.int32, (B, cap, 2)), query, n)
+        elif self.cfg == "c4":                                  # row p: 2-NN of pair p's left keypoints in its right image
+            off = self.mo_off
+            out["knn2_idx"] = rows(arr(off, "idx2", np.int32, (P, cap, 2)), sel, n)
+            out["knn2_dist"] = rows(arr(off, "dist2", np.int32, (P, cap, 2)), sel, n)
+            out["knn2_good"] = rows(arr(off, "good", np.uint8, (P, cap)), sel, n)
+        elif self.cfg == "c3":
+            off = self.c3_off
+            gs = arr(off, "gs", np.int32, (P, 3073))
+            out["stereo_ur"] = rows(arr(off, "ur", np.float32, (P, cap)), sel, n)
+            out["stereo_depth"] = rows(arr(off, "dp", np.float32, (P, cap)), sel, n)
+            out["stereo_kept"] = arr(off, "kept", np.int32, (P,)).astype(np.float64)
+            out["triangulation_matches"] = rows(arr(off, "m12", np.int32, (P, cap)), sel, n)
+            out["triangulation_count"] = arr(off, "nm", np.int32, (P,)).astype(np.float64)
+            out["grid_start"] = gs[sel].astype(np.float64)
+            out["grid_idx"] = rows(arr(off, "gi", np.int32, (P, cap)), sel, gs[:, -1])
         return out
 
     def mark(self, which):
@@ -697,9 +768,11 @@ def main():
     wl.sync()
     dt, t_enq = timed_loop(wl, args.steps, barrier, pre)     # the metric: kernels + results to the host
     dt_own = timed_loop.last_own
-    gpu_wall = wl.mark_ms() if not stub else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl.outputs(), args.dump_outputs)
+    gpu_wall = wl.mark_ms() if not stub and args.full else None
     extra = {}
-    if not stub:
+    if not stub and args.full:
         # HIP-event times of the timed steps (recorded on the streams the kernels were launched on; in graph mode the latest
         # replay of every graph slot, i.e. the last steps of the timed region)
         tm, nsamp = wl.ex.mean_timings()
@@ -746,14 +819,49 @@ def main():
             out["config"] = {"workload": "stub", "frames_per_step_per_gpu": B, "keypoints_last_batch": total_kp}
             print(json.dumps(out))
         else:
-            out.update(report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, total_kp, frames))
+            out.update(headline(wl, args, total_kp))
+            if args.full:
+                out.update(report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, frames, out["config"]))
             print(json.dumps(out))
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
 
 
-def report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, total_kp, frames):
+def dump_outputs(arrays, d):
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def headline(wl, args, total_kp):
+    """metric + config of the bench line: what the timed steps did"""
+    B, W, H, nF = wl.B, wl.W, wl.H, wl.nF
+    cw, ch, cnf, cb, _, cname = CONFIGS[wl.cfg]
+    named = (W, H, nF) == (cw, ch, cnf)
+    legs = {"c2": "dense 2-NN Hamming match (int8 MFMA) of every frame against the previous one",
+            "c5": "dense 2-NN Hamming match (int8 MFMA) of every frame against the previous one",
+            "c4": "%d fisheye stereo pairs: brute-force 2-NN of left x right descriptors per pair + Lowe ratio 0.7 in the kernel's epilogue (ComputeStereoFishEyeMatches, Frame.cc:1458-1465)" % (B // 2),
+            "c3": "%d stereo pairs (the stereo Frame constructor, Frame.cc:103-200, + what LocalMapping does with a new KeyFrame): ComputeStereoMatches and AssignFeaturesToGrid per pair, ComputeBoW buckets (seeded vocabulary of ORBvoc's shape: k=10, L=6, levelsup=4) and one SearchForTriangulation_ per pair "
+                  "(its left image against the right image of the previous step as the neighbouring KeyFrame)" % (B // 2)}
+    if args.match == "window":
+        legs["c2"] = legs["c5"] = ("AssignFeaturesToGrid + SearchByProjection(frame, previous frame, th=15, mono; ORBmatcher.cc:2469-2711) of every frame, "
+                                   "final match rows (claims, TH_HIGH, rotation-histogram cull) on the device")
+    return {
+        "metric": "ORB extract+match frames/sec @%dx%d, %d feat" % (W, H, nF),
+        "config": {"workload": (cname + ": " if named else "other size (not a named config): ") +
+                               "%dx%d grayscale (synthetic, texture class '%s', %d distinct frames per rank), %d features, 8 levels, scale 1.2, FAST 20/7; batch of %d frames/GPU/step resident in HBM; "
+                               "extract + %s; keypoints, descriptors, counts AND the match leg's outputs of every batch copied to pinned host memory inside the timed region"
+                               % (W, H, args.texture, max(1, min(args.distinct, B)), nF, B, legs[wl.cfg]),
+                   "frames_per_step_per_gpu": B, "launch": "hipGraph replay (one hipGraphLaunch per step)" if wl.graph else "eager enqueue",
+                   "keypoints_last_batch": total_kp, "result_bytes_to_host_per_step": wl.host_bytes},
+    }
+
+
+def report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, frames, config):
+    """--full: what takes runs or checks of its own beside the timed steps"""
     import numpy as np
     import torch
     ex, mt, B, W, H, nF = wl.ex, wl.mt, wl.B, wl.W, wl.H, wl.nF
@@ -831,25 +939,7 @@ def report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, total_kp, frames
         del a, b
     except Exception:
         copy_gbs = None
-    cw, ch, cnf, cb, _, cname = CONFIGS[wl.cfg]
-    named = (W, H, nF) == (cw, ch, cnf)
-    legs = {"c2": "dense 2-NN Hamming match (int8 MFMA) of every frame against the previous one",
-            "c5": "dense 2-NN Hamming match (int8 MFMA) of every frame against the previous one",
-            "c4": "%d fisheye stereo pairs: brute-force 2-NN of left x right descriptors per pair + Lowe ratio 0.7 in the kernel's epilogue (ComputeStereoFishEyeMatches, Frame.cc:1458-1465)" % (B // 2),
-            "c3": "%d stereo pairs (the stereo Frame constructor, Frame.cc:103-200, + what LocalMapping does with a new KeyFrame): ComputeStereoMatches and AssignFeaturesToGrid per pair, ComputeBoW buckets (seeded vocabulary of ORBvoc's shape: k=10, L=6, levelsup=4) and one SearchForTriangulation_ per pair "
-                  "(its left image against the right image of the previous step as the neighbouring KeyFrame)" % (B // 2)}
-    if args.match == "window":
-        legs["c2"] = legs["c5"] = ("AssignFeaturesToGrid + SearchByProjection(frame, previous frame, th=15, mono; ORBmatcher.cc:2469-2711) of every frame, "
-                                   "final match rows (claims, TH_HIGH, rotation-histogram cull) on the device")
-    d2h = wl.host_bytes
     out = {
-        "metric": "ORB extract+match frames/sec @%dx%d, %d feat" % (W, H, nF),
-        "config": {"workload": (cname + ": " if named else "other size (not a named config): ") +
-                               "%dx%d grayscale (synthetic, texture class '%s', %d distinct frames per rank), %d features, 8 levels, scale 1.2, FAST 20/7; batch of %d frames/GPU/step resident in HBM; "
-                               "extract + %s; keypoints, descriptors, counts AND the match leg's outputs of every batch copied to pinned host memory inside the timed region"
-                               % (W, H, args.texture, max(1, min(args.distinct, B)), nF, B, legs[wl.cfg]),
-                   "frames_per_step_per_gpu": B, "launch": "hipGraph replay (one hipGraphLaunch per step)" if wl.graph else "eager enqueue",
-                   "keypoints_last_batch": total_kp, "result_bytes_to_host_per_step": d2h},
         "value_device_resident": frames / dt_res, "ms_per_step_device_resident": dt_res / args.steps * 1e3,
         # host time of the calls that enqueue a step (no waiting involved: measured in the device-resident loop), and of the
         # timed loop itself, which also holds the flow control of the result ring (a block is rewritten only after its copy landed)
@@ -894,8 +984,8 @@ def report(wl, args, world, dt, dt_res, t_enq, gpu_wall, extra, total_kp, frames
     if wl.cfg == "c3":
         ok3, nst, ntri = c3_verify(wl, blk)
         out["stereo_and_triangulation_match_oracle"] = ok3
-        out["config"]["stereo_points_last_step"] = nst
-        out["config"]["triangulation_matches_last_step"] = ntri
+        config["stereo_points_last_step"] = nst
+        config["triangulation_matches_last_step"] = ntri
     if world == 1 and args.cpu_sample > 0:
         out.update(cpu_baseline(wl, args))
     return out

@@ -6,14 +6,14 @@ if [ "$1" = pmc2 ]; then
   :
 fi
 if [ "$1" = bench ]; then
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r03_bench_c2.json 2> $out/bench_c2.err; tail -c 200 $out/r03_bench_c2.json; echo
-  python bench.py --steps 20 --warmup 5 --match knn2 > $out/r03_bench_c2_knn2.json 2> $out/bench_c2k.err; tail -c 200 $out/r03_bench_c2_knn2.json; echo
-  for t in sparse lowcontrast mixed; do python bench.py --steps 20 --warmup 5 --texture $t --distinct 48 > $out/r03_bench_c2_$t.json 2> $out/bench_c2_$t.err; tail -c 200 $out/r03_bench_c2_$t.json; echo; done
-  python bench.py --steps 20 --warmup 5 --distinct 48 > $out/r03_bench_c2_dense.json 2> $out/bench_c2_dense.err; tail -c 200 $out/r03_bench_c2_dense.json; echo
-  for c in c3 c4 c5; do python bench.py --config $c --steps 20 --warmup 5 > $out/r03_bench_$c.json 2> $out/bench_$c.err; tail -c 200 $out/r03_bench_$c.json; echo; done
-  python bench.py --config c4 --batch 512 --steps 20 --warmup 5 > $out/r03_bench_c4_b512.json 2> $out/bench_c4b.err; tail -c 200 $out/r03_bench_c4_b512.json; echo
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r03_bench_c2.json 2> $out/bench_c2.err; tail -c 200 $out/r03_bench_c2.json; echo
+  python bench.py --full --steps 20 --warmup 5 --match knn2 > $out/r03_bench_c2_knn2.json 2> $out/bench_c2k.err; tail -c 200 $out/r03_bench_c2_knn2.json; echo
+  for t in sparse lowcontrast mixed; do python bench.py --full --steps 20 --warmup 5 --texture $t --distinct 48 > $out/r03_bench_c2_$t.json 2> $out/bench_c2_$t.err; tail -c 200 $out/r03_bench_c2_$t.json; echo; done
+  python bench.py --full --steps 20 --warmup 5 --distinct 48 > $out/r03_bench_c2_dense.json 2> $out/bench_c2_dense.err; tail -c 200 $out/r03_bench_c2_dense.json; echo
+  for c in c3 c4 c5; do python bench.py --full --config $c --steps 20 --warmup 5 > $out/r03_bench_$c.json 2> $out/bench_$c.err; tail -c 200 $out/r03_bench_$c.json; echo; done
+  python bench.py --full --config c4 --batch 512 --steps 20 --warmup 5 > $out/r03_bench_c4_b512.json 2> $out/bench_c4b.err; tail -c 200 $out/r03_bench_c4_b512.json; echo
   # the pass with the GPU to itself: blur behind FAST (A/B library only; the default keeps it inside the pass because the step is faster that way)
-  ORB_LIB=$GRAFT_REPO_ROOT/orb-slam3_amd/liborbslam3_amd_ab.so ORBX_BLUR_LATE=1 python bench.py --steps 20 --warmup 5 > $out/r03_bench_c2_blur_late.json 2> $out/bench_c2_bl.err; tail -c 200 $out/r03_bench_c2_blur_late.json; echo
+  ORB_LIB=$PWD/orb-slam3_amd/liborbslam3_amd_ab.so ORBX_BLUR_LATE=1 python bench.py --full --steps 20 --warmup 5 > $out/r03_bench_c2_blur_late.json 2> $out/bench_c2_bl.err; tail -c 200 $out/r03_bench_c2_blur_late.json; echo
   python tools/latency_breakdown.py > $out/r03_latency.txt 2>&1; tail -5 $out/r03_latency.txt
 else
   for c in c2 c3 c4 c5; do bash tools/prof.sh refresh3/prof_$c --config $c > $out/prof_$c.txt 2>&1; cp $GRAFT_REPO_ROOT/gpurun_out/refresh3/prof_${c}_kernel_stats.csv $out/r03_kernel_stats_$c.csv 2>/dev/null; echo prof $c done; done
