@@ -274,6 +274,33 @@ int orbm_track_window_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* 
                                   float min_x, float min_y, float inv_w, float inv_h,
                                   int q_first, int t_first, int npairs, float th, const float* scale_factors_host, int nlevels,
                                   float dx, float dy, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist);
+/* orbm_search_by_projection_points_batch_async: M3 SearchByProjection(Frame, vector<MapPoint*>, th, bFarPoints, thFarPoints) --
+ * Tracking::SearchLocalPoints -- END TO END on the device for `nframes` frames of one result block (ORBmatcher.cc:45-166, the
+ * left-camera part; the Nleft != -1 block :170-236 stays with orbm_search_by_projection_points_fisheye).  Frame f of the call is
+ * block frame t_first+f; it is searched through its grid (orbm_grid_build_batch_async over the block, indexed by block frame id).
+ * Every other per-frame array has one row per frame of the call: uright [nframes][cap] (mvuRight, e.g. orbm_stereo_batch_async with
+ * first_l == t_first; NULL = no stereo gate), t_blocked [nframes][cap] (mvpMapPoints[i] && Observations() > 0; NULL = none).
+ * The queries are the local map points: nq [nframes] of them per frame, rows of q_stride entries -- in_view, proj_x, proj_y,
+ * proj_xr (read only with uright), view_cos, level exactly as orbm_is_in_frustum(ORBM_DEVICE) writes them into row f; depth (NULL
+ * = bFarPoints off) skips a point with depth > th_far.  qdesc [..][32] and mp_obs [..] (Observations() > 0) are per frame rows
+ * too, or ONE row shared by every frame when q_shared != 0.  A point that is not in view, beyond th_far or whose level is outside
+ * [0, nlevels) reads nothing else of its row.  Window, stereo gate, best / second, TH_HIGH and the same-level ratio rule are those
+ * of orbm_search_by_projection_points; claims run in query order: an assignment may overwrite the slot of a point without
+ * observations and counts again, only a point with observations blocks its slot for later ones.  Outputs (device): match
+ * [nframes][cap] = query index or ORBM_NO_MATCH (the row orbm_search_by_projection_points returns, padded to cap), nmatches
+ * [nframes] = its return value.  All pointers are device pointers except scale_factors_host.  Enqueue-only: after one eager call
+ * the same or a smaller shape allocates nothing and can be captured (orbx_capture_begin).  ORBM_E_INVALID: a NULL array, a count
+ * < 1; ORBM_E_CAPACITY: cap > 65535, q_stride > ORBM_LP_MAX_QUERIES, nlevels > 12, nframes > 65535.  Nothing is enqueued then. */
+enum { ORBM_LP_MAX_QUERIES = 1 << 20 };
+int orbm_search_by_projection_points_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                 const int32_t* grid_start, const int32_t* grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, int nframes,
+                                                 const float* uright, const uint8_t* t_blocked, const int32_t* nq, int q_stride,
+                                                 const uint8_t* in_view, const float* proj_x, const float* proj_y, const float* proj_xr,
+                                                 const float* view_cos, const int32_t* level, const float* depth, float th_far,
+                                                 const uint8_t* qdesc, const uint8_t* mp_obs, int q_shared,
+                                                 float th, float nnratio, const float* scale_factors_host, int nlevels,
+                                                 int32_t* match, int32_t* nmatches);
 
 /* ---- batched, DEVICE-resident stereo step (config C3: EuRoC stereo).  All pointers are device pointers; enqueue only.
  * orbm_stereo_batch_async: M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276) for `npairs` stereo pairs of ONE extractor

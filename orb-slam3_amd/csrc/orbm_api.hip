@@ -1187,6 +1187,56 @@ int orbm_search_by_projection_batch_async(orbm_t* m, const orbm_kp_t* kps, const
     return ORBM_OK;
 }
 
+int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                 const int32_t* grid_start, const int32_t* grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, int nframes,
+                                                 const float* uright, const uint8_t* t_blocked, const int32_t* nq, int q_stride,
+                                                 const uint8_t* in_view, const float* proj_x, const float* proj_y, const float* proj_xr,
+                                                 const float* view_cos, const int32_t* level, const float* depth, float th_far,
+                                                 const uint8_t* qdesc, const uint8_t* mp_obs, int q_shared,
+                                                 float th, float nnratio, const float* scale_factors_host, int nlevels,
+                                                 int32_t* match, int32_t* nmatches) {
+    if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !nq || !in_view || !proj_x || !proj_y || !view_cos || !level ||
+        !qdesc || !mp_obs || !match || !nmatches || !scale_factors_host || (uright && !proj_xr)) {
+        set_merr("SearchByProjection points batch: a required array is NULL (proj_xr is required with uright)");
+        return ORBM_E_INVALID;
+    }
+    if (nframes < 1 || cap < 1 || q_stride < 1 || t_first < 0 || nlevels < 1) {
+        set_merr("SearchByProjection points batch: nframes, cap, q_stride and nlevels must be >= 1, t_first >= 0");
+        return ORBM_E_INVALID;
+    }
+    // k_lp_topk packs a keypoint index and its grid position into 16 bits each; the per-query arrays are indexed f * q_stride + q
+    if (cap > 65535) { set_merr("SearchByProjection points batch: %d keypoint slots per frame (the candidate words hold 65535)", cap); return ORBM_E_CAPACITY; }
+    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("SearchByProjection points batch: q_stride %d above %d", q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    if (nlevels > 12) { set_merr("SearchByProjection points batch: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
+    if (nframes > 65535) { set_merr("SearchByProjection points batch: %d frames in one call (at most 65535)", nframes); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    ScaleTab st;
+    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? scale_factors_host[i] : scale_factors_host[nlevels - 1];
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 64 * LP_K) * sizeof(unsigned);   // blocked bits, the current 64 queries' lists
+    // scratch of the handle: per query the window population, its LP_K best candidates and its radius
+    const size_t rows = (size_t)nframes * q_stride;
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * LP_K * sizeof(unsigned), bR = rows * sizeof(float);
+    uint8_t* scr = batch_scratch(m, bCnt + bKeys + bR);
+    if (!scr) { set_merr("SearchByProjection points batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bR); return ORBM_E_HIP; }
+    int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); float* topR = (float*)(scr + bCnt + bKeys);
+    LpRows R;
+    R.nq = nq; R.q_stride = q_stride;
+    R.in_view = in_view; R.px = proj_x; R.py = proj_y; R.pxr = proj_xr; R.view_cos = view_cos; R.level = level;
+    R.depth = depth; R.th_far = th_far;
+    R.qdesc = qdesc; R.mp_obs = mp_obs; R.q_shared = q_shared != 0;
+    R.th = th; R.nlevels = nlevels;
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_lp_topk, dim3((q_stride + 3) / 4, nframes), dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, t_first, uright, R, st, topCnt, topKeys, topR);
+    hipLaunchKernelGGL(k_lp_claim, dim3(nframes), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, t_first, uright, t_blocked, R, nnratio, topCnt, topKeys, topR, match, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 // ---- DBoW2 vocabulary ----
 struct orbm_vocab {
     int k = 0, L = 0, nnodes = 0, nwords = 0, device = 0;

@@ -1870,6 +1870,277 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
 }
 
 // ------------------------------------------------------------------------------------------------
+// Batched SearchByProjection(Frame, local MapPoints) -- M3, the left-camera part of ORBmatcher.cc:45-166 -- final matches on the device.
+// The queries are a tracker's local map points as k_frustum left them: one row of q_stride entries per searched frame of an extractor
+// result block.  Per query the window is derived on the device (RadiusByViewingCos [* th] * scale[level], levels [level-1, level],
+// the mvuRight gate, :66-117); a query that is not in view, lies beyond th_far (bFarPoints) or has a level outside the table reads
+// nothing else of its row (k_frustum leaves those fields unwritten for rejected points).
+// k_lp_topk: wave per query.  The window's grid columns are flattened into one list (column ranges loaded one per lane, prefix sum
+//   across the wave), so that a window of up to 64 grid entries costs one pass whatever its column count and larger ones (th = 10,
+//   high levels: r up to 4 * th * scale) take more passes of 64.  Out: the window population and its LP_K best candidates in
+//   (distance, visiting order) rank, each as ONE word dist << 20 | (octave + 1) << 16 | keypoint (the replay reads the level of
+//   best and second from it; no second gather).
+// k_lp_claim: one wave per frame replays the claims in query order (:119-164).  A query's list sits in LDS, one candidate per lane;
+//   one ballot over the blocked bit array gives its first two unblocked candidates -- best and second, as `dist < bestDist` /
+//   `else if dist < bestDist2` would have met them.  A truncated list with fewer than two unblocked entries is rescanned in full,
+//   blocked set applied (lp_sweep<false>).
+// ------------------------------------------------------------------------------------------------
+#define LP_K 8
+struct LpRows {                                            // the per-query arrays of one call, [nframes][q_stride] unless q_shared
+    const int* nq; int q_stride;
+    const uint8_t* in_view; const float* px; const float* py; const float* pxr; const float* view_cos; const int* level;
+    const float* depth; float th_far;
+    const uint8_t* qdesc; const uint8_t* mp_obs; int q_shared;
+    float th; int nlevels;
+};
+struct LpWin { float x, y, r, ur; int level; };
+
+// the window of query row o (wave-uniform), or false: the query is skipped
+__device__ __forceinline__ bool lp_query(const LpRows& R, const float* sf, bool stereo, size_t o, LpWin& w) {
+    if (!R.in_view[o]) return false;
+    if (R.depth && R.depth[o] > R.th_far) return false;                      // bFarPoints (:57-58)
+    const int lvl = R.level[o];
+    if (lvl < 0 || lvl >= R.nlevels) return false;
+    float r = (double)R.view_cos[o] > 0.998 ? 2.5f : 4.0f;                   // RadiusByViewingCos (:242-249): float against a double literal
+    if (R.th != 1.0f) r *= R.th;
+    w.r = r * sf[lvl];                                                     // one float multiply, as GetFeaturesInArea's argument
+    w.x = R.px[o]; w.y = R.py[o]; w.level = lvl;
+    w.ur = stereo ? R.pxr[o] : 0.f;
+    return true;
+}
+
+// One sweep of window w over a frame's grid (w wave-uniform, all 64 lanes).  Grid positions j are monotone in the reference's visiting
+// order (cell = ix * 48 + iy, cells ascending in the CSR), so (distance, j) ranks the candidates as the scan meets them.
+// key = dist << 40 | j << 20 | (octave + 1) << 16 | keypoint (j, keypoint < 65536; octave in [level - 1, level] with level < 12).
+// TOPK: cnt = window population, top[0..LP_K) = its LP_K smallest keys (wave-uniform).
+// !TOPK: only candidates not blocked in blk; top[0], top[1] = the two smallest.
+template <bool TOPK>
+__device__ __forceinline__ void lp_sweep(const LpWin& w, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt, const float* __restrict__ urt,
+                                         const int* __restrict__ gs, const int* __restrict__ gi, float min_x, float min_y, float inv_w, float inv_h,
+                                         const u64 (&a)[4], const unsigned int* blk, int lane, int& cnt, u64 (&top)[LP_K]) {
+    const u64 INV = ~0ull;
+#pragma unroll
+    for (int i = 0; i < LP_K; ++i) top[i] = INV;
+    cnt = 0;
+    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
+    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
+    if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
+    const int ncols = nMaxCellX - nMinCellX + 1;                             // 1 .. 64: one column per lane
+    int cj0 = 0, clen = 0;
+    if (lane < ncols) {
+        const int ix = nMinCellX + lane;
+        cj0 = gs[ix * 48 + nMinCellY];
+        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+    }
+    int total;
+    const int excl = wave_excl_scan(clen, &total);
+    u64 b1 = INV, b2 = INV;                                                  // !TOPK: the lane's two smallest
+    for (int base = 0; base < total; base += 64) {
+        const int t = base + lane;
+        int cs = 0, c0 = 0;
+        for (int c = 0; c < ncols; ++c) {                                    // t's column: the last one starting at or before t
+            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
+            if (t >= e) { cs = e; c0 = s; }
+        }
+        bool ok = false;
+        u64 key = INV;
+        if (t < total) {
+            const int j = c0 + (t - cs);
+            const int k = gi[j];
+            const KpIn kp = kt[k];
+            ok = !(kp.octave < w.level - 1) && !(kp.octave > w.level);       // bCheckLevels is true here (maxLevel >= 0)
+            if (!(fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r)) ok = false;
+            if (ok && urt) {
+                const float urk = urt[k];
+                if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // :107-117
+            }
+            if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
+            if (ok) {
+                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                const uint4 lo = tp[0], hi = tp[1];
+                const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
+                                     (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
+                key = ((u64)d << 40) | ((u64)j << 20) | ((u64)(kp.octave + 1) << 16) | (u64)k;
+            }
+        }
+        if (TOPK) {
+            const unsigned long long bal = __ballot(ok);
+            cnt += __popcll(bal);
+            if (bal == 0) continue;
+            for (int rnd = 0; rnd < LP_K; ++rnd) {                           // merge: pull the chunk's minima until one no longer beats the K-th
+                const u64 m = wave_min_u64(key);
+                if (m >= top[LP_K - 1]) break;
+                if (key == m) key = INV;                                     // keys are unique (grid position)
+                u64 c = m;
+#pragma unroll
+                for (int i = 0; i < LP_K; ++i) { const u64 tt = top[i]; const bool sw = c < tt; top[i] = sw ? c : tt; c = sw ? tt : c; }
+            }
+        } else {
+            if (key < b1) { b2 = b1; b1 = key; }
+            else if (key < b2) b2 = key;
+        }
+    }
+    if (!TOPK) {
+        const u64 m1 = wave_min_u64(b1);
+        top[0] = m1;
+        top[1] = wave_min_u64(b1 == m1 ? b2 : b1);                          // the winner's lane offers its runner-up
+    }
+}
+
+__device__ __forceinline__ unsigned int lp_word(u64 key) {                   // dist << 20 | (octave + 1) << 16 | keypoint, or 0xFFFFFFFF
+    return key == ~0ull ? 0xFFFFFFFFu : ((unsigned)(key >> 40) << 20) | (unsigned)(key & 0xFFFFFu);
+}
+
+__device__ __forceinline__ void lp_qdesc(const LpRows& R, size_t qrow, u64 (&a)[4]) {
+    const uint4* qp = (const uint4*)(R.qdesc + qrow * 32);
+    const uint4 qlo = qp[0], qhi = qp[1];
+    a[0] = (u64)qlo.x | ((u64)qlo.y << 32); a[1] = (u64)qlo.z | ((u64)qlo.w << 32);
+    a[2] = (u64)qhi.x | ((u64)qhi.y << 32); a[3] = (u64)qhi.z | ((u64)qhi.w << 32);
+}
+
+__global__ __launch_bounds__(256) void k_lp_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
+                                                 LpRows R, ScaleTab st, int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys,
+                                                 float* __restrict__ out_r) {
+    const int lane = threadIdx.x & 63;
+    const int f = blockIdx.y, tf = t_first + f;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nq = min(max(R.nq[f], 0), R.q_stride);
+    if (q >= nq) return;
+    const size_t o = (size_t)f * R.q_stride + q;
+    LpWin w;
+    int cnt = 0;
+    u64 top[LP_K];
+    if (lp_query(R, st.sf, uright != nullptr, o, w)) {
+        u64 a[4];
+        lp_qdesc(R, R.q_shared ? (size_t)q : o, a);
+        lp_sweep<true>(w, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)f * cap : nullptr,
+                       grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
+    } else {
+#pragma unroll
+        for (int i = 0; i < LP_K; ++i) top[i] = ~0ull;
+    }
+    if (lane == 0) {
+        out_cnt[o] = cnt;
+        out_r[o] = w.r;                                                      // read back only by a rescan (count > LP_K)
+        uint4* ok = (uint4*)(out_keys + o * LP_K);
+        ok[0] = make_uint4(lp_word(top[0]), lp_word(top[1]), lp_word(top[2]), lp_word(top[3]));
+        ok[1] = make_uint4(lp_word(top[4]), lp_word(top[5]), lp_word(top[6]), lp_word(top[7]));
+    }
+}
+
+__global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
+                                                 const uint8_t* __restrict__ t_blocked, LpRows R, float nnratio,
+                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
+                                                 int* __restrict__ match, int* __restrict__ nmatches) {
+    extern __shared__ unsigned int lp_lds[];                                 // blocked bit array [ceil(cap / 32)], the current 64 queries' lists [64][LP_K]
+    const unsigned INV = 0xFFFFFFFFu;
+    const int lane = threadIdx.x, f = blockIdx.x, tf = t_first + f;
+    const int nt = min(max(counts[tf], 0), cap);
+    const int nq = min(max(R.nq[f], 0), R.q_stride);
+    const int nwords = (cap + 31) >> 5;
+    unsigned int* blk = lp_lds;
+    unsigned int* sk = lp_lds + nwords;
+    int* mrow = match + (size_t)f * cap;
+    for (int wd = lane; wd < nwords; wd += 64) {
+        unsigned int bits = 0;
+        if (t_blocked) {
+            const uint8_t* tb = t_blocked + (size_t)f * cap;
+#pragma unroll 8
+            for (int b = 0; b < 32; ++b) if (wd * 32 + b < nt && tb[wd * 32 + b]) bits |= 1u << b;
+        }
+        blk[wd] = bits;
+    }
+    for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
+    __syncthreads();
+    const KpIn* kt = kps + (size_t)tf * cap;
+    const uint8_t* dt = desc + (size_t)tf * cap * 32;
+    const float* urt = uright ? uright + (size_t)f * cap : nullptr;
+    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
+    const int* gi = grid_idx + (size_t)tf * cap;
+    const size_t rowBase = (size_t)f * R.q_stride;
+    int nm = 0;
+    // the next 64 queries' lists, counts and observation flags are in flight while the current ones are replayed (clamped, unconditional loads)
+    unsigned int pk[LP_K];
+    int pc = 0;
+    uint8_t pob = 0;
+    auto fetch = [&](int W0) {
+        const int last = nq * LP_K - 1;
+#pragma unroll
+        for (int r = 0; r < LP_K; ++r) pk[r] = topKeys[rowBase * LP_K + min(W0 * LP_K + r * 64 + lane, last)];
+        const int qc = min(W0 + lane, nq - 1);
+        pc = topCnt[rowBase + qc];
+        pob = R.mp_obs[R.q_shared ? (size_t)qc : rowBase + qc];
+    };
+    if (nq > 0) fetch(0);
+    for (int W0 = 0; W0 < nq; W0 += 64) {
+#pragma unroll
+        for (int r = 0; r < LP_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * LP_K .. + LP_K)
+        const int cnt = W0 + lane < nq ? pc : 0;
+        const int ob = pob != 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (W0 + 64 < nq) fetch(W0 + 64);
+        unsigned long long todo = __ballot(cnt > 0);                        // skipped queries and empty windows have count 0
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            unsigned int key = INV;
+            bool fr = false;
+            if (lane < LP_K) {
+                key = sk[i * LP_K + lane];
+                const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
+                fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
+            }
+            unsigned long long fb = __ballot(fr);
+            unsigned int w1 = INV, w2 = INV;
+            if (fb) {
+                w1 = (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1);
+                fb &= fb - 1;
+                if (fb) w2 = (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1);
+            }
+            if (w2 == INV && __builtin_amdgcn_readlane(cnt, i) > LP_K) {
+                // best AND second must come from the unblocked candidates: the listed ones ran dry, the window holds more
+                const size_t o = rowBase + W0 + i;
+                LpWin w;                                                     // the window k_lp_topk swept (its radius from there: no scale table here)
+                w.x = R.px[o]; w.y = R.py[o]; w.r = topR[o]; w.level = R.level[o]; w.ur = uright ? R.pxr[o] : 0.f;
+                u64 a[4];
+                lp_qdesc(R, R.q_shared ? (size_t)(W0 + i) : o, a);
+                u64 top[LP_K];
+                int c2;
+                lp_sweep<false>(w, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                w1 = lp_word(top[0]); w2 = lp_word(top[1]);
+            }
+            if (w1 == INV) continue;
+            const int bestDist = (int)(w1 >> 20), bestLevel = (int)((w1 >> 16) & 15u) - 1;
+            const int bestDist2 = w2 == INV ? 256 : (int)(w2 >> 20), bestLevel2 = w2 == INV ? -1 : (int)((w2 >> 16) & 15u) - 1;
+            if (bestDist <= 100) {                                           // TH_HIGH (:119)
+                if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
+                if (bestLevel != bestLevel2 || (float)bestDist <= nnratio * (float)bestDist2) {
+                    const unsigned int k = w1 & 0xFFFFu;
+                    const int obi = __builtin_amdgcn_readlane(ob, i);
+                    if (lane == 0) {
+                        mrow[k] = W0 + i;                                    // may overwrite a claim of a query without observations
+                        if (obi) blk[k >> 5] |= 1u << (k & 31);
+                    }
+                    ++nm;                                                    // overwrites count, as the reference's nmatches++ does
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // the next chunk's lists overwrite sk
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0) nmatches[f] = nm;
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_bow_transform2: DBoW2 TemplatedVocabulary::transform (TemplatedVocabulary.h:1196-1262) for a batch of descriptors: at every level the
 // child with the smallest Hamming distance (first minimum, strict <) is taken; the node reached at level L - levelsup is recorded.
 // The tree is in the level-major layout the host builds (orbm_vocab_create): nodes renumbered breadth-first so
