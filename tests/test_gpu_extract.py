@@ -21,14 +21,14 @@ CASES = [
 ]
 
 
-def _check(pkg, oracle, synth, w, h, nf, seed, lap, kind, stages=True):
+def _check(pkg, oracle, synth, w, h, nf, seed, lap, kind, stages=True, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7):
     img = synth.gen_image(w, h, seed, kind)
-    ref = oracle.Extractor(nf)
+    ref = oracle.Extractor(nf, scale_factor, nlevels, ini_th, min_th)
     n_ref, kps_ref, desc_ref, mono_ref = ref(img, lap)
-    ex = pkg.ORBextractor(nf, max_size=(w, h), max_batch=1)
+    ex = pkg.ORBextractor(nf, scale_factor, nlevels, ini_th, min_th, max_size=(w, h), max_batch=1)
     mono, kps, desc = ex(img, lap)
     if stages:
-        for l in range(8):
+        for l in range(nlevels):
             assert np.array_equal(ex.level_image(l), ref.level_image(l)), "pyramid level %d" % l
             assert np.array_equal(ex.level_candidates(l), ref.level_candidates(l)), "FAST candidates level %d" % l
             assert np.array_equal(ex.level_selected(l), ref.level_keypoints(l)[0]), "quadtree level %d" % l

@@ -61,16 +61,17 @@ class _Rows:
             self.qdesc.upload(d); self.mp_obs.upload(o)
 
 
-def _call(L, m, r, cap, gs, gi, t_first, rows, sf, th, nnratio, match, nm, uright=None, blocked=None, depth=False, th_far=0.0):
+def _call(L, m, r, cap, gs, gi, t_first, rows, sf, th, nnratio, match, nm, uright=None, blocked=None, depth=False, th_far=0.0,
+          inv_w=INV_W, inv_h=INV_H, nlev=NLEV):
     return L.orbm_search_by_projection_points_batch_async(
-        m.h, r["kps"], r["desc"], r["counts"], cap, gs.ptr, gi.ptr, 0.0, 0.0, INV_W, INV_H, t_first, rows.nframes,
+        m.h, r["kps"], r["desc"], r["counts"], cap, gs.ptr, gi.ptr, 0.0, 0.0, inv_w, inv_h, t_first, rows.nframes,
         None if uright is None else uright.ptr, None if blocked is None else blocked.ptr, rows.nq.ptr, rows.qs,
         rows.in_view.ptr, rows.px.ptr, rows.py.ptr, rows.pxr.ptr, rows.view_cos.ptr, rows.level.ptr,
         rows.depth.ptr if depth else None, float(th_far), rows.qdesc.ptr, rows.mp_obs.ptr, int(rows.shared),
-        float(th), float(nnratio), _vp(sf), NLEV, match.ptr, nm.ptr)
+        float(th), float(nnratio), _vp(sf), nlev, match.ptr, nm.ptr)
 
 
-def _check_frame(pkg, m, OM, sf, kt, dt, q, row, n_dev, th, nnratio, ur=None, blocked=None, th_far=None):
+def _check_frame(pkg, m, OM, sf, kt, dt, q, row, n_dev, th, nnratio, ur=None, blocked=None, th_far=None, w=W, h=H):
     """Device row + count of one frame vs the host entry point and the oracle; returns (nmatches, matched slots)."""
     nt = len(kt)
     iv = np.asarray(q["in_view"], np.uint8).copy()
@@ -85,8 +86,8 @@ def _check_frame(pkg, m, OM, sf, kt, dt, q, row, n_dev, th, nnratio, ur=None, bl
         assert n_dev == 0 and np.all(row == -1)
         return 0, 0
     u = None if ur is None else np.ascontiguousarray(ur[:nt], np.float32)
-    n_h, m_h = m.SearchByProjectionPoints(pkg.FrameView(kt, dt, W, H, uright=u, backend=m), **args)
-    n_o, m_o = OM.SearchByProjectionPoints(pkg.FrameView(kt, dt, W, H, uright=u, backend=OM), **args)
+    n_h, m_h = m.SearchByProjectionPoints(pkg.FrameView(kt, dt, w, h, uright=u, backend=m), **args)
+    n_o, m_o = OM.SearchByProjectionPoints(pkg.FrameView(kt, dt, w, h, uright=u, backend=OM), **args)
     assert n_h == n_o and np.array_equal(m_h, m_o)
     assert n_dev == n_o, (n_dev, n_o)
     assert np.array_equal(row[:nt], m_o), np.flatnonzero(row[:nt] != m_o)[:10]
@@ -94,7 +95,7 @@ def _check_frame(pkg, m, OM, sf, kt, dt, q, row, n_dev, th, nnratio, ur=None, bl
     return n_o, int((m_o >= 0).sum())
 
 
-def _queries(rng, kps, desc, nq, jitter=1.5, flips=6, own=False):
+def _queries(rng, kps, desc, nq, jitter=1.5, flips=6, own=False, nlev=NLEV):
     n = len(kps)
     src = np.arange(nq) % n if own else rng.integers(0, n, nq)
     px = kps["x"][src].astype(np.float32); py = kps["y"][src].astype(np.float32)
@@ -109,7 +110,7 @@ def _queries(rng, kps, desc, nq, jitter=1.5, flips=6, own=False):
     vc[rng.random(nq) < 0.1] = np.float32(0.998)                        # float(0.998) > 0.998 (double): the 2.5 radius
     lev = kps["octave"][src].astype(np.int32)
     up = rng.random(nq) < 0.2
-    lev[up] = np.minimum(lev[up] + 1, NLEV - 1)                          # predicted one level up: the window's level-1 side
+    lev[up] = np.minimum(lev[up] + 1, nlev - 1)                          # predicted one level up: the window's level-1 side
     return dict(in_view=(rng.random(nq) < 0.85).astype(np.uint8), px=px, py=py, pxr=(px - rng.uniform(2, 40, nq)).astype(np.float32),
                 view_cos=vc, level=lev, qdesc=d, mp_obs=np.ones(nq, np.uint8), depth=rng.uniform(0.5, 12, nq).astype(np.float32))
 

@@ -23,8 +23,14 @@ def _fv(nodes):
 
 
 def test_stereo_bow_triangulation_batch(pkg, oracle, synth, tmp_path):
-    W, H, NF, P = 752, 480, 1200, 3
-    pairs = [synth.gen_stereo_pair(W, H, 500 + i) for i in range(P)]
+    _stereo_bow_triangulation(pkg, oracle, synth, tmp_path)
+
+
+def _stereo_bow_triangulation(pkg, oracle, synth, tmp_path, W=752, H=480, NF=1200, P=3, mb=MB, mbf=MBF, scale_factor=1.2, nlevels=8,
+                              seed0=500, min_kept=300, min_tri=100):
+    """The whole chain for P stereo pairs of a W x H camera with baseline mb and bf mbf, the extractor at (scale_factor, nlevels);
+    every output equals the oracle's.  Returns per pair (stereo points kept, triangulation matches)."""
+    pairs = [synth.gen_stereo_pair(W, H, seed0 + i) for i in range(P)]
     imgs = [p[0] for p in pairs] + [p[1] for p in pairs]                    # frames [0,P) left, [P,2P) right
     stride = (W + 63) // 64 * 64
     dev = pkg.DeviceBuffer(2 * P * stride * H)
@@ -33,14 +39,14 @@ def test_stereo_bow_triangulation_batch(pkg, oracle, synth, tmp_path):
         dev.upload(pad, offset=i * stride * H)
     arr = (C.c_void_p * (2 * P))(*[dev.ptr + i * stride * H for i in range(2 * P)])
     L = pkg.lib()
-    ex = pkg.ORBextractor(NF, max_size=(W, H), max_batch=2 * P)
+    ex = pkg.ORBextractor(NF, scale_factor, nlevels, max_size=(W, H), max_batch=2 * P)
     mt = pkg.ORBmatcher(0.6)
     assert L.orbm_set_stream(mt.h, L.orbx_stream(ex.h)) == 0
     cap = ex.cap
     ex.enqueue_device(arr, W, H, stride, np.zeros(4 * P, np.int32))
     r = ex.result_device()
     ur = pkg.DeviceBuffer(P * cap * 4); dp = pkg.DeviceBuffer(P * cap * 4); sad = pkg.DeviceBuffer(P * cap * 4); kept = pkg.DeviceBuffer(P * 4)
-    assert L.orbm_stereo_batch_async(mt.h, ex.h, 0, P, P, r["kps"], r["desc"], r["counts"], cap, MB, MBF, ur.ptr, dp.ptr, sad.ptr, kept.ptr) == 0, L.orbm_last_error()
+    assert L.orbm_stereo_batch_async(mt.h, ex.h, 0, P, P, r["kps"], r["desc"], r["counts"], cap, mb, mbf, ur.ptr, dp.ptr, sad.ptr, kept.ptr) == 0, L.orbm_last_error()
     # FeatureVector buckets of every descriptor row of the block
     path = str(tmp_path / "voc.txt")
     _write_vocab(path, 10, 3, seed=7)
@@ -50,11 +56,11 @@ def test_stereo_bow_triangulation_batch(pkg, oracle, synth, tmp_path):
     # SearchForTriangulation_: KeyFrame 1 = the left images (with their fresh mvuRight), KeyFrame 2 = the right images
     sf = ex.GetScaleFactors(); sig2 = ex.GetScaleSigmaSquares()
     F12 = np.array([0, 0, 0, 0, 0, 0.11, 0, -0.11, 0], np.float32)          # pure x-baseline between identical pinhole cameras
-    ep = (1e4, 240.0)
+    ep = (1e4, H / 2.0)
     m12 = pkg.DeviceBuffer(P * cap * 4); nm = pkg.DeviceBuffer(P * 4)
     rc = L.orbm_triangulation_batch_async(mt.h, P, cap, r["kps"], r["desc"], r["counts"], nodes.ptr, ur.ptr,
                                           r["kps"] + P * cap * 28, r["desc"] + P * cap * 32, r["counts"] + 4 * P, nodes.ptr + P * cap * 4, None,
-                                          F12.ctypes.data_as(C.c_void_p), ep[0], ep[1], sf.ctypes.data_as(C.c_void_p), sig2.ctypes.data_as(C.c_void_p), 8, 0, 0,
+                                          F12.ctypes.data_as(C.c_void_p), ep[0], ep[1], sf.ctypes.data_as(C.c_void_p), sig2.ctypes.data_as(C.c_void_p), ex.GetLevels(), 0, 0,
                                           m12.ptr, nm.ptr)
     assert rc == 0, L.orbm_last_error()
     ex.sync()
@@ -63,12 +69,13 @@ def test_stereo_bow_triangulation_batch(pkg, oracle, synth, tmp_path):
     kept_h = kept.download(np.int32, P); nodes_h = nodes.download(np.int32, 2 * P * cap).reshape(2 * P, cap)
     m12_h = m12.download(np.int32, P * cap).reshape(P, cap); nm_h = nm.download(np.int32, P)
     OM = oracle._oracle_matcher_class()()
+    out = []
     for p in range(P):
-        ol, orr = oracle.Extractor(NF), oracle.Extractor(NF)
+        ol, orr = oracle.Extractor(NF, scale_factor, nlevels), oracle.Extractor(NF, scale_factor, nlevels)
         nl, kl, dl, _ = ol(imgs[p], (0, 0)); nr, kr, dr, _ = orr(imgs[P + p], (0, 0))
         assert res[p][1].tobytes() == kl.tobytes() and res[P + p][1].tobytes() == kr.tobytes()
-        n_ref, ur_r, dp_r = OM.ComputeStereoMatches(ol, orr, kl, dl, kr, dr, MB, MBF)
-        assert kept_h[p] == n_ref and n_ref > 300, (p, kept_h[p], n_ref)
+        n_ref, ur_r, dp_r = OM.ComputeStereoMatches(ol, orr, kl, dl, kr, dr, mb, mbf)
+        assert kept_h[p] == n_ref and n_ref > min_kept, (p, kept_h[p], n_ref)
         assert ur_h[p, :nl].tobytes() == ur_r.tobytes() and dp_h[p, :nl].tobytes() == dp_r.tobytes(), p
         # buckets
         nd_l = ovoc.transform(dl, 1)[3]; nd_r = ovoc.transform(dr, 1)[3]
@@ -77,5 +84,7 @@ def test_stereo_bow_triangulation_batch(pkg, oracle, synth, tmp_path):
         n_t, m_ref = OM.SearchForTriangulation(kl, dl, np.zeros(nl, np.uint8), ur_r, _fv(nd_l), kr, dr, np.zeros(nr, np.uint8), None, _fv(nd_r),
                                                F12, ep, sf, sig2, only_stereo=False, coarse=False, check_ori=False)
         assert nm_h[p] == n_t and np.array_equal(m12_h[p, :nl], m_ref), (p, nm_h[p], n_t)
-        assert n_t > 100
+        assert n_t > min_tri
+        out.append((n_ref, n_t))
     ex.close(); mt.close()
+    return out
