@@ -301,6 +301,46 @@ int orbm_search_by_projection_points_batch_async(orbm_t*, const orbm_kp_t* kps, 
                                                  const uint8_t* qdesc, const uint8_t* mp_obs, int q_shared,
                                                  float th, float nnratio, const float* scale_factors_host, int nlevels,
                                                  int32_t* match, int32_t* nmatches);
+/* orbm_search_by_projection_frame_batch_async: M4 SearchByProjection(CurrentFrame, LastFrame, th, bMono) -- Tracking::TrackWithMotionModel
+ * -- END TO END on the device for `npairs` pairs (ORBmatcher.cc:2469-2612 and the rotation check :2686-2708, the Nleft == -1 part; the
+ * fisheye right-camera block stays with orbm_search_by_projection_frame_fisheye).  Pair p searches block frame t_first+p through its grid
+ * (orbm_grid_build_batch_async over the block, indexed by block frame id).  Per pair rows: uright [npairs][cap] (mvuRight, e.g.
+ * orbm_stereo_batch_async with first_l == t_first; NULL = no stereo gate, invzc is then not read and may be NULL), t_blocked
+ * [npairs][cap] (the slot holds a MapPoint with Observations() > 0; NULL = none), dir [npairs] (0 = levels o-1..o+1, 1 = bForward:
+ * levels >= o, 2 = bBackward: levels <= o; other values read as 0; NULL = all 0; orbm_project_last_frame_batch_async writes it).
+ * The queries are the LastFrame MapPoints: nq [npairs] of them per pair in rows of q_stride entries -- valid, u, v, invzc, octave,
+ * angle (the LastFrame keypoint's), qdesc [..][32] (the MapPoint's descriptor) and mp_obs (Observations() > 0).  A query that is not
+ * valid, or whose octave lies outside [0, nlevels), reads nothing else of its row.  Semantics per pair are exactly those of
+ * orbm_search_by_projection_frame: window th * scale[octave], stereo gate ur = u - mbf * invzc, first candidate of least distance not
+ * blocked, bestDist <= TH_HIGH; claims in query order, an assignment may overwrite the slot of a query without observations and counts
+ * again, only mp_obs blocks a slot for later queries; check_orientation applies the rotation histogram and its three-maxima cull
+ * (culled slots ORBM_MATCH_PRUNED).  retry_below > 0: every pair whose count is below it is searched again at 2 * th from an empty
+ * frame (no blocked slots, Tracking.cc:3213-3221), on the device; that row and count replace the first ones and retried[p] = 1
+ * (retried [npairs] or NULL; 0 for the other pairs).  Outputs (device): match [npairs][cap] (the row orbm_search_by_projection_frame
+ * returns, padded with ORBM_NO_MATCH to cap), nmatches [npairs] (its return value).  All pointers are device pointers except
+ * scale_factors_host.  Enqueue-only: after one eager call the same or a smaller shape allocates nothing and can be captured
+ * (orbx_capture_begin).  ORBM_E_INVALID: a NULL required array, a count < 1, t_first or retry_below < 0; ORBM_E_CAPACITY: cap >
+ * 65535, q_stride > ORBM_LP_MAX_QUERIES, nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_by_projection_frame_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                const int32_t* grid_start, const int32_t* grid_idx,
+                                                float min_x, float min_y, float inv_w, float inv_h, int t_first, int npairs,
+                                                const float* uright, float mbf, const uint8_t* t_blocked, const uint8_t* dir,
+                                                const int32_t* nq, int q_stride, const uint8_t* valid, const float* u, const float* v,
+                                                const float* invzc, const int32_t* octave, const float* angle, const uint8_t* qdesc,
+                                                const uint8_t* mp_obs, float th, int retry_below, const float* scale_factors_host, int nlevels,
+                                                int check_orientation, int32_t* match, int32_t* nmatches, uint8_t* retried);
+/* orbm_project_last_frame_batch_async: the projection half of M4 (ORBmatcher.cc:2481-2527) for a pinhole camera with Nleft == -1, the
+ * producer of the rows above.  Per pair (device): tcw_cur, tcw_last [npairs][12] (row-major 3x4 [R | t]); per query (device): x3dw
+ * [npairs][q_stride][3] (world position), has_mp [npairs][q_stride] (pMP && !mvbOutlier), nq [npairs].  Host: k_host = (fx, fy, cx, cy),
+ * bounds_host = (minX, maxX, minY, maxY), mb, mono.  Outputs (device): valid, u, v, invzc [npairs][q_stride] (rows beyond nq[p] are
+ * not written; a rejected query gets valid = 0 and u = v = invzc = 0) and dir [npairs] (1 = bForward, 2 = bBackward, else 0).
+ * Numerics are those of the facade against cvcompat.h: x3Dc = (float)(double sum of R * X) + t, invzc = (float)(1.0 / (double)z),
+ * u = fx * xc / zc + cx in float without contraction; twc = -Rcw^T * tcw and tlc = Rlw * twc + tlw by the same product rule.  A point
+ * with z == 0 exactly is outside the contract.  Enqueue-only; ORBM_E_INVALID: a NULL array, npairs or q_stride < 1; ORBM_E_CAPACITY:
+ * q_stride > ORBM_LP_MAX_QUERIES, npairs > 65535. */
+int orbm_project_last_frame_batch_async(orbm_t*, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
+                                        const float* x3dw, const uint8_t* has_mp, const float* k_host, const float* bounds_host, float mb, int mono,
+                                        uint8_t* valid, float* u, float* v, float* invzc, uint8_t* dir);
 
 /* ---- batched, DEVICE-resident stereo step (config C3: EuRoC stereo).  All pointers are device pointers; enqueue only.
  * orbm_stereo_batch_async: M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276) for `npairs` stereo pairs of ONE extractor

@@ -827,6 +827,11 @@ def _install_search():
                                                                vp, vp, vp, ci,                                  # uright, t_blocked, nq, q_stride
                                                                vp, vp, vp, vp, vp, vp, vp, cf,                  # frustum rows, depth, th_far
                                                                vp, vp, ci, cf, cf, vp, ci, vp, vp]
+    L.orbm_search_by_projection_frame_batch_async.argtypes = [vp, vp, vp, vp, ci, vp, vp, cf, cf, cf, cf, ci, ci,   # block, grid, bounds, pairs
+                                                              vp, cf, vp, vp, vp, ci,                          # uright, mbf, t_blocked, dir, nq, q_stride
+                                                              vp, vp, vp, vp, vp, vp, vp, vp,                  # valid, u, v, invzc, octave, angle, qdesc, mp_obs
+                                                              cf, ci, vp, ci, ci, vp, vp, vp]                  # th, retry_below, sf, nlevels, check_ori, outputs
+    L.orbm_project_last_frame_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp]
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -902,7 +907,8 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_kf", "orbm_search_by_bow_kf", "orbm_search_for_triangulation_legacy", "orbm_search_for_triangulation_gated",
             "orbm_search_by_projection_sim3", "orbm_fuse", "orbm_search_by_sim3",
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
-            "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_fisheye",
+            "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
+            "orbm_project_last_frame_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib

@@ -1237,6 +1237,85 @@ int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps
     return ORBM_OK;
 }
 
+int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                const int32_t* grid_start, const int32_t* grid_idx,
+                                                float min_x, float min_y, float inv_w, float inv_h, int t_first, int npairs,
+                                                const float* uright, float mbf, const uint8_t* t_blocked, const uint8_t* dir,
+                                                const int32_t* nq, int q_stride, const uint8_t* valid, const float* u, const float* v,
+                                                const float* invzc, const int32_t* octave, const float* angle, const uint8_t* qdesc,
+                                                const uint8_t* mp_obs, float th, int retry_below, const float* scale_factors_host, int nlevels,
+                                                int check_orientation, int32_t* match, int32_t* nmatches, uint8_t* retried) {
+    if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !nq || !valid || !u || !v || !octave || !angle || !qdesc || !mp_obs ||
+        !match || !nmatches || !scale_factors_host || (uright && !invzc)) {
+        set_merr("SearchByProjection frame batch: a required array is NULL (invzc is required with uright)");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || cap < 1 || q_stride < 1 || t_first < 0 || nlevels < 1 || retry_below < 0) {
+        set_merr("SearchByProjection frame batch: npairs, cap, q_stride and nlevels must be >= 1, t_first and retry_below >= 0");
+        return ORBM_E_INVALID;
+    }
+    // k_mm_topk packs a keypoint index and its grid position into 16 bits each; the per-query arrays are indexed p * q_stride + q
+    if (cap > 65535) { set_merr("SearchByProjection frame batch: %d keypoint slots per frame (the candidate words hold 65535)", cap); return ORBM_E_CAPACITY; }
+    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("SearchByProjection frame batch: q_stride %d above %d", q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    if (nlevels > 12) { set_merr("SearchByProjection frame batch: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
+    if (npairs > 65535) { set_merr("SearchByProjection frame batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    ScaleTab st;
+    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? scale_factors_host[i] : scale_factors_host[nlevels - 1];
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * MM_K) * sizeof(unsigned);   // blocked bits, histogram, the current 64 queries' lists
+    // scratch of the handle: per query the window population, its MM_K best candidates and a slot of the accepted-assignment list
+    const size_t rows = (size_t)npairs * q_stride;
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * MM_K * sizeof(unsigned), bAcc = rows * sizeof(unsigned),
+                 bR = rows * sizeof(float);
+    uint8_t* scr = batch_scratch(m, bCnt + bKeys + bAcc + bR);
+    if (!scr) { set_merr("SearchByProjection frame batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bAcc + bR); return ORBM_E_HIP; }
+    int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); unsigned* acc = (unsigned*)(scr + bCnt + bKeys);
+    float* topR = (float*)(scr + bCnt + bKeys + bAcc);
+    MmRows R;
+    R.nq = nq; R.q_stride = q_stride;
+    R.valid = valid; R.u = u; R.v = v; R.invzc = invzc; R.octave = octave; R.angle = angle;
+    R.qdesc = qdesc; R.mp_obs = mp_obs; R.dir = dir;
+    R.mbf = mbf; R.factor = ORBM_HISTO_LENGTH / 360.0f;                     // ORBmatcher.cc:2478
+    R.nlevels = nlevels; R.retry_below = retry_below; R.check_ori = check_orientation != 0;
+    const dim3 gTop((q_stride + 3) / 4, npairs);
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, t_first, uright, R, st, th, nmatches, topCnt, topKeys, topR);
+    hipLaunchKernelGGL(k_mm_claim<false>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, t_first, uright, t_blocked, R, topCnt, topKeys, topR, acc, match, nmatches, retried);
+    if (retry_below > 0) {                                                  // Tracking.cc:3213-3221, decided per pair on the device
+        const float th2 = 2 * th;
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, t_first, uright, R, st, th2, nmatches, topCnt, topKeys, topR);
+        hipLaunchKernelGGL(k_mm_claim<true>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, t_first, uright, nullptr, R, topCnt, topKeys, topR, acc, match, nmatches, retried);
+    }
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
+int orbm_project_last_frame_batch_async(orbm_t* m, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
+                                        const float* x3dw, const uint8_t* has_mp, const float* k_host, const float* bounds_host, float mb, int mono,
+                                        uint8_t* valid, float* u, float* v, float* invzc, uint8_t* dir) {
+    if (!m || !tcw_cur || !tcw_last || !nq || !x3dw || !has_mp || !k_host || !bounds_host || !valid || !u || !v || !invzc || !dir) {
+        set_merr("project last frame batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || q_stride < 1) { set_merr("project last frame batch: npairs and q_stride must be >= 1"); return ORBM_E_INVALID; }
+    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("project last frame batch: q_stride %d above %d", q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    if (npairs > 65535) { set_merr("project last frame batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    MmProj P;
+    for (int i = 0; i < 4; ++i) { P.k[i] = k_host[i]; P.bounds[i] = bounds_host[i]; }
+    P.mb = mb; P.mono = mono != 0; P.q_stride = q_stride;
+    hipLaunchKernelGGL(k_mm_project, dim3((q_stride + 255) / 256, npairs), dim3(256), 0, m->stream, tcw_cur, tcw_last, nq, x3dw, has_mp, P,
+                       valid, u, v, invzc, dir);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
 // ---- DBoW2 vocabulary ----
 struct orbm_vocab {
     int k = 0, L = 0, nnodes = 0, nwords = 0, device = 0;

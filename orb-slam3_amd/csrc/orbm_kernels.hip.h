@@ -2141,6 +2141,371 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
 }
 
 // ------------------------------------------------------------------------------------------------
+// Batched SearchByProjection(Frame, Frame) on the caller's projections -- M4, Tracking::TrackWithMotionModel -- final matches on the
+// device: ORBmatcher.cc:2469-2612 (the left-camera part, Nleft == -1) with the rotation check :2686-2708, and Tracking's wider-window
+// retry (Tracking.cc:3213-3221).  The queries are the LastFrame MapPoints as k_mm_project (or the caller) left them: one row of
+// q_stride entries per pair.  Per query the window is th * scale[octave], levels by the pair's direction (:2543-2549: o-1..o+1,
+// bForward o.., bBackward 0..o, GetFeaturesInArea's bCheckLevels rule, Frame.cc:784-871) and the mvuRight gate (:2569-2576: ur =
+// u - mbf * invzc, a multiply then a subtract: this file is compiled without contraction).  A query that is not valid or whose
+// octave lies outside the scale table reads nothing else of its row.
+// k_mm_topk: ONE WAVE PER QUERY.  Mono windows at th 15 hold about 14 grid entries, so one pass leaves most lanes idle; but a query
+//   costs four dependent round trips (cell ranges, grid indices, keypoints, descriptors) whatever its lane count, 64 pairs x 1000
+//   queries are 64 k waves -- enough to fill the machine by waves rather than by lanes --, and the windows the same call must also
+//   take (th 30 on level 7: 30 * 1.2^7 = 107 px, a few hundred entries; the retry doubles th again) then need a few passes of 64
+//   instead of many passes of 16 with the per-pass merge each time.  The window's grid columns are flattened into one list (ranges
+//   one per lane, prefix sum across the wave) as in k_lp_topk.  Out: the window population and its MM_K best candidates in
+//   (distance, visiting order) rank as ONE word each, dist << 21 | rotation bin << 16 | keypoint (bin of angle_q - angle_t as
+//   :2596-2603, TK_NOBIN outside [0, 30)), so the claim needs no second gather.
+// k_mm_claim: one wave per pair replays the claims in query order (:2553-2612).  A query's list sits in LDS, one candidate per lane;
+//   one ballot over the blocked bit array gives its first unblocked candidate, which is its `dist < bestDist` winner.  A truncated
+//   list whose candidates are all blocked is rescanned in full with the blocked set applied (mm_sweep<false>).  Each assignment with
+//   a rotation bin is appended to a per-pair list and counted in an LDS histogram; the three-maxima cull then marks every slot of a
+//   culled bin ORBM_MATCH_PRUNED once per entry, so a slot claimed twice is culled (and uncounted) as often as the reference does.
+// RETRY: the same two kernels at 2 * th for the pairs whose count is below retry_below, from an empty frame (mvpMapPoints filled
+//   with NULL: no blocked slots); every other pair returns at once, so the retry needs no host round trip.
+// ------------------------------------------------------------------------------------------------
+#define MM_K 8
+struct MmRows {                                            // the per-query arrays of one call, [npairs][q_stride]
+    const int* nq; int q_stride;
+    const uint8_t* valid; const float* u; const float* v; const float* invzc; const int* octave; const float* angle;
+    const uint8_t* qdesc; const uint8_t* mp_obs; const uint8_t* dir;
+    float mbf, factor; int nlevels, retry_below, check_ori;
+};
+struct MmWin { float x, y, r, ur, qangle; int minLevel, maxLevel; };
+
+// the window of valid query row o of pair p with octave oc, all but its radius
+__device__ __forceinline__ void mm_levels(const MmRows& R, int p, int oc, size_t o, bool stereo, MmWin& w) {
+    const int d = R.dir ? R.dir[p] : 0;
+    if (d == 1) { w.minLevel = oc; w.maxLevel = -1; }                        // bForward: GetFeaturesInArea(.., nLastOctave)
+    else if (d == 2) { w.minLevel = 0; w.maxLevel = oc; }                    // bBackward
+    else { w.minLevel = oc - 1; w.maxLevel = oc + 1; }
+    w.x = R.u[o]; w.y = R.v[o]; w.qangle = R.angle[o];
+    w.ur = stereo ? R.u[o] - R.mbf * R.invzc[o] : 0.f;                       // :2571
+}
+
+// the window of query row o of pair p (wave-uniform), or false: the query is skipped
+__device__ __forceinline__ bool mm_query(const MmRows& R, const float* sf, float th, bool stereo, int p, size_t o, MmWin& w) {
+    if (!R.valid[o]) return false;
+    const int oc = R.octave[o];
+    if (oc < 0 || oc >= R.nlevels) return false;
+    w.r = th * sf[oc];                                                       // :2536, one float multiply
+    mm_levels(R, p, oc, o, stereo, w);
+    return true;
+}
+
+// One sweep of window w over a frame's grid (w wave-uniform, all 64 lanes); grid positions j follow the reference's visiting order.
+// key = dist << 40 | j << 21 | bin << 16 | keypoint (j, keypoint < 65536).
+// TOPK: cnt = window population, top[0..MM_K) = its MM_K smallest keys.  !TOPK: top[0] = the smallest key not blocked in blk.
+template <bool TOPK>
+__device__ __forceinline__ void mm_sweep(const MmWin& w, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt, const float* __restrict__ urt,
+                                         const int* __restrict__ gs, const int* __restrict__ gi, float min_x, float min_y, float inv_w, float inv_h,
+                                         float factor, const u64 (&a)[4], const unsigned int* blk, int lane, int& cnt, u64 (&top)[MM_K]) {
+    const u64 INV = ~0ull;
+#pragma unroll
+    for (int i = 0; i < MM_K; ++i) top[i] = INV;
+    cnt = 0;
+    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
+    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
+    if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
+    const bool bCheckLevels = (w.minLevel > 0) || (w.maxLevel >= 0);
+    const int ncols = nMaxCellX - nMinCellX + 1;                             // 1 .. 64: one column per lane
+    int cj0 = 0, clen = 0;
+    if (lane < ncols) {
+        const int ix = nMinCellX + lane;
+        cj0 = gs[ix * 48 + nMinCellY];
+        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+    }
+    int total;
+    const int excl = wave_excl_scan(clen, &total);
+    u64 b1 = INV;
+    for (int base = 0; base < total; base += 64) {
+        const int t = base + lane;
+        int cs = 0, c0 = 0;
+        for (int c = 0; c < ncols; ++c) {                                    // t's column: the last one starting at or before t
+            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
+            if (t >= e) { cs = e; c0 = s; }
+        }
+        bool ok = false;
+        u64 key = INV;
+        if (t < total) {
+            const int j = c0 + (t - cs);
+            const int k = gi[j];
+            const KpIn kp = kt[k];
+            ok = true;
+            if (bCheckLevels) {
+                if (kp.octave < w.minLevel) ok = false;
+                if (w.maxLevel >= 0 && kp.octave > w.maxLevel) ok = false;
+            }
+            if (!(fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r)) ok = false;
+            if (ok && urt) {
+                const float urk = urt[k];
+                if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // :2569-2576
+            }
+            if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
+            if (ok) {
+                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                const uint4 lo = tp[0], hi = tp[1];
+                const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
+                                     (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
+                float rot = w.qangle - kp.angle;                             // :2596-2603
+                if (rot < 0.0f) rot += 360.0f;
+                int bin = (int)roundf(rot * factor);
+                if (bin == 30) bin = 0;
+                if (bin < 0 || bin >= 30) bin = TK_NOBIN;
+                key = ((u64)d << 40) | ((u64)j << 21) | ((u64)bin << 16) | (u64)k;
+            }
+        }
+        if (TOPK) {
+            const unsigned long long bal = __ballot(ok);
+            cnt += __popcll(bal);
+            if (bal == 0) continue;
+            for (int rnd = 0; rnd < MM_K; ++rnd) {                           // merge: pull the chunk's minima until one no longer beats the K-th
+                const u64 m = wave_min_u64(key);
+                if (m >= top[MM_K - 1]) break;
+                if (key == m) key = INV;                                     // keys are unique (grid position)
+                u64 c = m;
+#pragma unroll
+                for (int i = 0; i < MM_K; ++i) { const u64 tt = top[i]; const bool sw = c < tt; top[i] = sw ? c : tt; c = sw ? tt : c; }
+            }
+        } else {
+            b1 = key < b1 ? key : b1;
+        }
+    }
+    if (!TOPK) top[0] = wave_min_u64(b1);
+}
+
+__device__ __forceinline__ unsigned int mm_word(u64 key) {                   // dist << 21 | bin << 16 | keypoint, or 0xFFFFFFFF
+    return key == ~0ull ? 0xFFFFFFFFu : ((unsigned)(key >> 40) << 21) | (unsigned)(key & 0x1FFFFFu);
+}
+
+__device__ __forceinline__ void mm_qdesc(const MmRows& R, size_t o, u64 (&a)[4]) {
+    const uint4* qp = (const uint4*)(R.qdesc + o * 32);
+    const uint4 qlo = qp[0], qhi = qp[1];
+    a[0] = (u64)qlo.x | ((u64)qlo.y << 32); a[1] = (u64)qlo.z | ((u64)qlo.w << 32);
+    a[2] = (u64)qhi.x | ((u64)qhi.y << 32); a[3] = (u64)qhi.z | ((u64)qhi.w << 32);
+}
+
+template <bool RETRY>
+__global__ __launch_bounds__(256) void k_mm_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
+                                                 MmRows R, ScaleTab st, float th, const int* __restrict__ nmatches,
+                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.y, tf = t_first + p;
+    if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // the first search of this pair stands
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nq = min(max(R.nq[p], 0), R.q_stride);
+    if (q >= nq) return;
+    const size_t o = (size_t)p * R.q_stride + q;
+    MmWin w;
+    w.r = 0.f;                                                               // (a skipped query's out_r is written but never read)
+    int cnt = 0;
+    u64 top[MM_K];
+    if (mm_query(R, st.sf, th, uright != nullptr, p, o, w)) {
+        u64 a[4];
+        mm_qdesc(R, o, a);
+        mm_sweep<true>(w, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)p * cap : nullptr,
+                       grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, R.factor, a, nullptr,
+                       lane, cnt, top);
+    } else {
+#pragma unroll
+        for (int i = 0; i < MM_K; ++i) top[i] = ~0ull;
+    }
+    if (lane == 0) {
+        out_cnt[o] = cnt;
+        out_r[o] = w.r;                                                      // read back only by a rescan (count > MM_K)
+        uint4* ok = (uint4*)(out_keys + o * MM_K);
+        ok[0] = make_uint4(mm_word(top[0]), mm_word(top[1]), mm_word(top[2]), mm_word(top[3]));
+        ok[1] = make_uint4(mm_word(top[4]), mm_word(top[5]), mm_word(top[6]), mm_word(top[7]));
+    }
+}
+
+template <bool RETRY>
+__global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
+                                                 const uint8_t* __restrict__ t_blocked, MmRows R,
+                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
+                                                 unsigned int* __restrict__ accepted,
+                                                 int* __restrict__ match, int* __restrict__ nmatches, uint8_t* __restrict__ retried) {
+    extern __shared__ unsigned int mm_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][MM_K]
+    const unsigned INV = 0xFFFFFFFFu;
+    const int lane = threadIdx.x, p = blockIdx.x, tf = t_first + p;
+    if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // (wave-uniform) the first search of this pair stands
+    const int nt = min(max(counts[tf], 0), cap);
+    const int nq = min(max(R.nq[p], 0), R.q_stride);
+    const int nwords = (cap + 31) >> 5;
+    unsigned int* blk = mm_lds;
+    unsigned int* hist = mm_lds + nwords;
+    unsigned int* sk = hist + 32;
+    int* mrow = match + (size_t)p * cap;
+    for (int wd = lane; wd < nwords; wd += 64) {
+        unsigned int bits = 0;
+        if (!RETRY && t_blocked) {                                           // the retry starts from an empty frame (Tracking.cc:3217)
+            const uint8_t* tb = t_blocked + (size_t)p * cap;
+#pragma unroll 8
+            for (int b = 0; b < 32; ++b) if (wd * 32 + b < nt && tb[wd * 32 + b]) bits |= 1u << b;
+        }
+        blk[wd] = bits;
+    }
+    if (lane < 32) hist[lane] = 0;
+    for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
+    __syncthreads();
+    const KpIn* kt = kps + (size_t)tf * cap;
+    const uint8_t* dt = desc + (size_t)tf * cap * 32;
+    const float* urt = uright ? uright + (size_t)p * cap : nullptr;
+    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
+    const int* gi = grid_idx + (size_t)tf * cap;
+    const size_t rowBase = (size_t)p * R.q_stride;
+    unsigned int* acc = accepted + rowBase;                                  // (slot | bin << 16) of every assignment with a bin, in order
+    int nm = 0, nacc = 0;
+    // the next 64 queries' lists and counts are in flight while the current ones are replayed (clamped, unconditional loads);
+    // mp_obs is read only for a query with candidates (a skipped row reads nothing else)
+    const unsigned int* keyRow = topKeys + rowBase * MM_K;
+    const int* cntRow = topCnt + rowBase;
+    const uint8_t* obRow = R.mp_obs + rowBase;
+    unsigned int pk[MM_K];
+    int pc = 0;
+    uint8_t pob = 0;
+    auto fetch = [&](int W0) {
+        const int last = nq * MM_K - 1;
+#pragma unroll
+        for (int r = 0; r < MM_K; ++r) pk[r] = keyRow[min(W0 * MM_K + r * 64 + lane, last)];
+        const int qc = min(W0 + lane, nq - 1);
+        pc = cntRow[qc];
+        pob = (W0 + lane < nq && pc > 0) ? obRow[qc] : 0;
+    };
+    if (nq > 0) fetch(0);
+    for (int W0 = 0; W0 < nq; W0 += 64) {
+#pragma unroll
+        for (int r = 0; r < MM_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * MM_K .. + MM_K)
+        const int cnt = W0 + lane < nq ? pc : 0;
+        const int ob = pob != 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (W0 + 64 < nq) fetch(W0 + 64);
+        unsigned long long todo = __ballot(cnt > 0);                        // skipped queries and empty windows have count 0
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            unsigned int key = INV;
+            bool fr = false;
+            if (lane < MM_K) {
+                key = sk[i * MM_K + lane];
+                const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
+                fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
+            }
+            const unsigned long long fb = __ballot(fr);
+            unsigned int best = fb ? (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1) : INV;
+            if (best == INV && __builtin_amdgcn_readlane(cnt, i) > MM_K) {
+                // every listed candidate is blocked and the window holds more: the window again, blocked set applied
+                const size_t o = rowBase + W0 + i;
+                MmWin w;                                                     // the window k_mm_topk swept (its radius from there: no scale table here)
+                w.r = topR[o];
+                mm_levels(R, p, R.octave[o], o, urt != nullptr, w);
+                u64 a[4];
+                mm_qdesc(R, o, a);
+                u64 top[MM_K];
+                int c2;
+                mm_sweep<false>(w, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, R.factor, a, blk, lane, c2, top);
+                best = mm_word(top[0]);
+            }
+            if (best == INV || (best >> 21) > 100u) continue;                // TH_HIGH (:2589)
+            const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
+            const int obi = __builtin_amdgcn_readlane(ob, i);
+            const bool withBin = R.check_ori && bin != TK_NOBIN;
+            if (lane == 0) {
+                mrow[k] = W0 + i;                                            // may overwrite a claim of a query without observations
+                if (obi) blk[k >> 5] |= 1u << (k & 31);
+                if (withBin) { acc[nacc] = k | (bin << 16); hist[bin] += 1u; }
+            }
+            ++nm;                                                            // overwrites count, as the reference's nmatches++ does
+            if (withBin) ++nacc;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // the next chunk's lists overwrite sk
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (R.check_ori) {
+        // ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment of the other bins is cleared (:2696-2707)
+        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+        for (int i = 0; i < 30; ++i) {
+            const int sz = (int)hist[i];
+            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
+            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
+            else if (sz > max3) { max3 = sz; i3 = i; }
+        }
+        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+        else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
+        int pruned = 0;
+        for (int e = lane; e < nacc; e += 64) {
+            const unsigned int v = acc[e];
+            const int bin = (int)(v >> 16), k = (int)(v & 0xFFFFu);
+            if (bin != i1 && bin != i2 && bin != i3) { mrow[k] = -2; ++pruned; }      // ORBM_MATCH_PRUNED
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
+        nm -= pruned;
+    }
+    if (lane == 0) {
+        nmatches[p] = nm;
+        if (retried) retried[p] = RETRY ? 1 : 0;
+    }
+}
+
+// k_mm_project: the LastFrame MapPoints of every pair through the current pose (ORBmatcher.cc:2481-2527 as facade/ORBmatcher.h
+// evaluates it against cvcompat.h): a 3x3 * 3x1 product accumulates in double and rounds once to float, the translation is a float
+// add; invzc = (float)(1.0 / (double)z); pinhole u = fx * xc / zc + cx (Pinhole.cpp:33-37).  A rejected point (no MapPoint or an
+// outlier, invzc < 0, outside the bounds) gets valid = 0 and u = v = invzc = 0.  Thread 0 of each pair also writes its direction
+// (0, 1 = bForward, 2 = bBackward) from tlc = Rlw * (-Rcw^T * tcw) + tlw.
+struct MmProj { float k[4], bounds[4], mb; int mono, q_stride; };
+__device__ __forceinline__ float mm_dot3(float r0, float r1, float r2, float x0, float x1, float x2) {
+    double s = 0;
+    s += (double)r0 * (double)x0;
+    s += (double)r1 * (double)x1;
+    s += (double)r2 * (double)x2;
+    return (float)s;
+}
+__global__ __launch_bounds__(256) void k_mm_project(const float* __restrict__ tcw_cur, const float* __restrict__ tcw_last, const int* __restrict__ nq,
+                                                    const float* __restrict__ x3dw, const uint8_t* __restrict__ has_mp, MmProj P,
+                                                    uint8_t* __restrict__ valid, float* __restrict__ u, float* __restrict__ v,
+                                                    float* __restrict__ invzc, uint8_t* __restrict__ dir) {
+    const int p = blockIdx.y;
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    const float* T = tcw_cur + (size_t)p * 12;                              // row-major 3x4 [R | t]
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        float twc[3];
+        for (int r = 0; r < 3; ++r) twc[r] = mm_dot3(-T[0 * 4 + r], -T[1 * 4 + r], -T[2 * 4 + r], T[3], T[7], T[11]);   // -Rcw.t() * tcw
+        const float* Tl = tcw_last + (size_t)p * 12;
+        const float tlcz = mm_dot3(Tl[8], Tl[9], Tl[10], twc[0], twc[1], twc[2]) + Tl[11];                              // (Rlw * twc + tlw)(2)
+        dir[p] = (!P.mono && tlcz > P.mb) ? 1 : (!P.mono && -tlcz > P.mb) ? 2 : 0;
+    }
+    const int n = min(max(nq[p], 0), P.q_stride);
+    if (q >= n) return;
+    const size_t o = (size_t)p * P.q_stride + q;
+    uint8_t ok = 0;
+    float pu = 0.f, pv = 0.f, iz = 0.f;
+    if (has_mp[o]) {
+        const float* X = x3dw + o * 3;
+        const float x0 = X[0], x1 = X[1], x2 = X[2];
+        const float xc = mm_dot3(T[0], T[1], T[2], x0, x1, x2) + T[3];
+        const float yc = mm_dot3(T[4], T[5], T[6], x0, x1, x2) + T[7];
+        const float zc = mm_dot3(T[8], T[9], T[10], x0, x1, x2) + T[11];
+        const float izc = (float)(1.0 / (double)zc);
+        if (!(izc < 0)) {
+            const float uu = P.k[0] * xc / zc + P.k[2], vv = P.k[1] * yc / zc + P.k[3];
+            if (!(uu < P.bounds[0] || uu > P.bounds[1]) && !(vv < P.bounds[2] || vv > P.bounds[3])) { ok = 1; pu = uu; pv = vv; iz = izc; }
+        }
+    }
+    valid[o] = ok; u[o] = pu; v[o] = pv; invzc[o] = iz;
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_bow_transform2: DBoW2 TemplatedVocabulary::transform (TemplatedVocabulary.h:1196-1262) for a batch of descriptors: at every level the
 // child with the smallest Hamming distance (first minimum, strict <) is taken; the node reached at level L - levelsup is recorded.
 // The tree is in the level-major layout the host builds (orbm_vocab_create): nodes renumbered breadth-first so
