@@ -1118,6 +1118,23 @@ int orbm_grid_build_batch_async(orbm_t* m, const orbm_kp_t* kps, const int32_t* 
     return ORBM_OK;
 }
 
+// the first nlevels scale factors, the last one repeated to the table's 12 entries
+static ScaleTab scale_tab(const float* sf, int nlevels) {
+    ScaleTab st;
+    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? sf[i] : sf[nlevels - 1];
+    return st;
+}
+
+// the capacity refusals of the points (M3) and frame (M4) batch calls: the candidate words hold a keypoint index and its grid
+// position in 16 bits each; the per-query arrays are indexed batch * q_stride + q
+static int lp_capacity(const char* call, int cap, int q_stride, int nlevels, int nbatch, const char* batch_name) {
+    if (cap > 65535) { set_merr("%s: %d keypoint slots per frame (the candidate words hold 65535)", call, cap); return ORBM_E_CAPACITY; }
+    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("%s: q_stride %d above %d", call, q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    if (nlevels > 12) { set_merr("%s: %d scale levels (the scale table holds 12)", call, nlevels); return ORBM_E_CAPACITY; }
+    if (nbatch > 65535) { set_merr("%s: %d %s in one call (at most 65535)", call, nbatch, batch_name); return ORBM_E_CAPACITY; }
+    return ORBM_OK;
+}
+
 int orbm_track_window_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
                                   const int32_t* grid_start, const int32_t* grid_idx,
                                   float min_x, float min_y, float inv_w, float inv_h,
@@ -1126,8 +1143,7 @@ int orbm_track_window_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t
     if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !best_idx || !best_dist || !second_dist || npairs < 1 ||
         nlevels < 1 || nlevels > 12 || !sf) return ORBM_E_INVALID;
     MHIPCHK(hipSetDevice(m->device));
-    ScaleTab st;
-    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? sf[i] : sf[nlevels - 1];
+    const ScaleTab st = scale_tab(sf, nlevels);
     MHIPCHK(rec_time(m, m->e0));
     hipLaunchKernelGGL(k_track_window, dim3((cap + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
                        grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, best_idx, best_dist, second_dist);
@@ -1146,8 +1162,7 @@ int orbm_search_by_projection_batch_async(orbm_t* m, const orbm_kp_t* kps, const
     if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !match || !nmatches || npairs < 1 || cap < 1 || cap > 65535 ||
         nlevels < 1 || nlevels > 12 || !sf || q_first < 0 || t_first < 0) return ORBM_E_INVALID;
     MHIPCHK(hipSetDevice(m->device));
-    ScaleTab st;
-    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? sf[i] : sf[nlevels - 1];
+    const ScaleTab st = scale_tab(sf, nlevels);
     const size_t lds = (size_t)(2 * ((cap + 31) >> 5) + 32 + cap) * sizeof(unsigned);   // blocked bits, rotation histogram, observed bits, proposal tags
     if (lds > 64 * 1024) { set_merr("SearchByProjection batch: %d keypoint slots per frame need %zu B of LDS (limit 64 KB, ~16 000 slots)", cap, lds); return ORBM_E_INVALID; }
     // scratch of the handle: per query the window population and its TK_K best candidates, per pair the (slot, bin) list of the assignments
@@ -1205,18 +1220,13 @@ int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps
         set_merr("SearchByProjection points batch: nframes, cap, q_stride and nlevels must be >= 1, t_first >= 0");
         return ORBM_E_INVALID;
     }
-    // k_lp_topk packs a keypoint index and its grid position into 16 bits each; the per-query arrays are indexed f * q_stride + q
-    if (cap > 65535) { set_merr("SearchByProjection points batch: %d keypoint slots per frame (the candidate words hold 65535)", cap); return ORBM_E_CAPACITY; }
-    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("SearchByProjection points batch: q_stride %d above %d", q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
-    if (nlevels > 12) { set_merr("SearchByProjection points batch: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
-    if (nframes > 65535) { set_merr("SearchByProjection points batch: %d frames in one call (at most 65535)", nframes); return ORBM_E_CAPACITY; }
+    if (const int rc = lp_capacity("SearchByProjection points batch", cap, q_stride, nlevels, nframes, "frames")) return rc;
     MHIPCHK(hipSetDevice(m->device));
-    ScaleTab st;
-    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? scale_factors_host[i] : scale_factors_host[nlevels - 1];
-    const size_t lds = (size_t)(((cap + 31) >> 5) + 64 * LP_K) * sizeof(unsigned);   // blocked bits, the current 64 queries' lists
-    // scratch of the handle: per query the window population, its LP_K best candidates and its radius
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 64 * TK_K) * sizeof(unsigned);   // blocked bits, the current 64 queries' lists
+    // scratch of the handle: per query the window population, its TK_K best candidates and its radius
     const size_t rows = (size_t)nframes * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * LP_K * sizeof(unsigned), bR = rows * sizeof(float);
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = rows * sizeof(float);
     uint8_t* scr = batch_scratch(m, bCnt + bKeys + bR);
     if (!scr) { set_merr("SearchByProjection points batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bR); return ORBM_E_HIP; }
     int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); float* topR = (float*)(scr + bCnt + bKeys);
@@ -1254,18 +1264,13 @@ int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps,
         set_merr("SearchByProjection frame batch: npairs, cap, q_stride and nlevels must be >= 1, t_first and retry_below >= 0");
         return ORBM_E_INVALID;
     }
-    // k_mm_topk packs a keypoint index and its grid position into 16 bits each; the per-query arrays are indexed p * q_stride + q
-    if (cap > 65535) { set_merr("SearchByProjection frame batch: %d keypoint slots per frame (the candidate words hold 65535)", cap); return ORBM_E_CAPACITY; }
-    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("SearchByProjection frame batch: q_stride %d above %d", q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
-    if (nlevels > 12) { set_merr("SearchByProjection frame batch: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
-    if (npairs > 65535) { set_merr("SearchByProjection frame batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    if (const int rc = lp_capacity("SearchByProjection frame batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
     MHIPCHK(hipSetDevice(m->device));
-    ScaleTab st;
-    for (int i = 0; i < 12; ++i) st.sf[i] = i < nlevels ? scale_factors_host[i] : scale_factors_host[nlevels - 1];
-    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * MM_K) * sizeof(unsigned);   // blocked bits, histogram, the current 64 queries' lists
-    // scratch of the handle: per query the window population, its MM_K best candidates and a slot of the accepted-assignment list
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // blocked bits, histogram, the current 64 queries' lists
+    // scratch of the handle: per query the window population, its TK_K best candidates and a slot of the accepted-assignment list
     const size_t rows = (size_t)npairs * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * MM_K * sizeof(unsigned), bAcc = rows * sizeof(unsigned),
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bAcc = rows * sizeof(unsigned),
                  bR = rows * sizeof(float);
     uint8_t* scr = batch_scratch(m, bCnt + bKeys + bAcc + bR);
     if (!scr) { set_merr("SearchByProjection frame batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bAcc + bR); return ORBM_E_HIP; }

@@ -1101,7 +1101,7 @@ __global__ __launch_bounds__(256) void k_track_window(const KpIn* __restrict__ k
 //   travel by register compare.  A query whose TK_K listed candidates are all blocked although its window holds more is rescanned
 //   in place, blocked set applied (rare; the single-frame host replay falls back to full lists in the same case).
 // ------------------------------------------------------------------------------------------------
-#define TK_K 8
+#define TK_K 8                                                              // candidates listed per query, every batched search (track, M3, M4)
 #define TK_NOBIN 31
 // wave-wide minimum of a 32-bit key by DPP (six v_min_u32 with data movement folded in; the result of a full reduction sits in lane 63)
 __device__ __forceinline__ unsigned wave_min_u32(unsigned v) {
@@ -1132,6 +1132,167 @@ __device__ __forceinline__ int wave_excl_scan(int v, int* total) {           // 
     *total = __builtin_amdgcn_readlane(s, 63);
     return s - v;
 }
+
+// ---- shared by the batched SearchByProjection kernels (track M4, M3 k_lp_*, motion-model M4 k_mm_*) ----
+__device__ __forceinline__ void load_desc(const uint8_t* p, u64 (&a)[4]) {    // one 32-byte descriptor as four 64-bit words
+    const uint4* qp = (const uint4*)p;
+    const uint4 qlo = qp[0], qhi = qp[1];
+    a[0] = (u64)qlo.x | ((u64)qlo.y << 32); a[1] = (u64)qlo.z | ((u64)qlo.w << 32);
+    a[2] = (u64)qhi.x | ((u64)qhi.y << 32); a[3] = (u64)qhi.z | ((u64)qhi.w << 32);
+}
+
+// A GetFeaturesInArea window (Frame.cc:784-871): levels by the generic rule (bCheckLevels = minLevel > 0 || maxLevel >= 0, maxLevel < 0
+// leaves the top open) and, with an mvuRight array, the stereo gate |ur - uR[k]| <= r of the right-projecting searches.
+struct Win { float x, y, r, ur; int minLevel, maxLevel; };
+
+// The 5-bit payload a candidate word carries: the candidate's octave + 1 (M3: the ratio test compares levels) or its rotation bin
+// (M4: angle_q - angle_t as ORBmatcher.cc:2596-2603, TK_NOBIN outside [0, 30)).
+struct OctavePay { __device__ unsigned operator()(const KpIn& kp) const { return (unsigned)(kp.octave + 1); } };
+struct RotBinPay {
+    float qangle, factor;
+    __device__ unsigned operator()(const KpIn& kp) const {
+        float rot = qangle - kp.angle;
+        if (rot < 0.0f) rot += 360.0f;
+        int bin = (int)roundf(rot * factor);
+        if (bin == 30) bin = 0;
+        if (bin < 0 || bin >= 30) bin = TK_NOBIN;
+        return (unsigned)bin;
+    }
+};
+
+// One sweep of window w over a frame's grid (w wave-uniform, all 64 lanes).  The window's grid columns are flattened into one list
+// (column ranges one per lane, prefix sum across the wave) and taken in passes of 64.  Grid positions j are monotone in the reference's
+// visiting order (cell = ix * 48 + iy, cells ascending in the CSR), so (distance, j) ranks the candidates as the scan meets them.
+// key = dist << 40 | j << 21 | payload << 16 | keypoint (j, keypoint < 65536).
+// TOPK: cnt = window population, top[0..TK_K) = its TK_K smallest keys (wave-uniform).
+// !TOPK: only candidates not blocked in blk; top[0], top[1] = the two smallest.
+template <bool TOPK, class Pay>
+__device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt,
+                                          const float* __restrict__ urt, const int* __restrict__ gs, const int* __restrict__ gi,
+                                          float min_x, float min_y, float inv_w, float inv_h, const u64 (&a)[4], const unsigned int* blk,
+                                          int lane, int& cnt, u64 (&top)[TK_K]) {
+    const u64 INV = ~0ull;
+#pragma unroll
+    for (int i = 0; i < TK_K; ++i) top[i] = INV;
+    cnt = 0;
+    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
+    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
+    if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
+    const bool bCheckLevels = (w.minLevel > 0) || (w.maxLevel >= 0);
+    const int loLevel = bCheckLevels ? w.minLevel : INT_MIN, hiLevel = bCheckLevels && w.maxLevel >= 0 ? w.maxLevel : INT_MAX;
+    const int ncols = nMaxCellX - nMinCellX + 1;                             // 1 .. 64: one column per lane
+    int cj0 = 0, clen = 0;
+    if (lane < ncols) {
+        const int ix = nMinCellX + lane;
+        cj0 = gs[ix * 48 + nMinCellY];
+        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+    }
+    int total;
+    const int excl = wave_excl_scan(clen, &total);
+    u64 b1 = INV, b2 = INV;                                                  // !TOPK: the lane's two smallest
+    for (int base = 0; base < total; base += 64) {
+        const int t = base + lane;
+        int cs = 0, c0 = 0;
+        for (int c = 0; c < ncols; ++c) {                                    // t's column: the last one starting at or before t
+            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
+            if (t >= e) { cs = e; c0 = s; }
+        }
+        bool ok = false;
+        u64 key = INV;
+        if (t < total) {
+            const int j = c0 + (t - cs);
+            const int k = gi[j];
+            const KpIn kp = kt[k];
+            ok = (kp.octave >= loLevel) & (kp.octave <= hiLevel) & (fabsf(kp.x - w.x) < w.r) & (fabsf(kp.y - w.y) < w.r);   // (no short cut: one x, y load)
+            if (ok && urt) {
+                const float urk = urt[k];
+                if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // ORBmatcher.cc:107-117, :2569-2576
+            }
+            if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
+            if (ok) {
+                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                const uint4 lo = tp[0], hi = tp[1];
+                const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
+                                     (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
+                key = ((u64)d << 40) | ((u64)j << 21) | ((u64)pay(kp) << 16) | (u64)k;
+            }
+        }
+        if (TOPK) {
+            const unsigned long long bal = __ballot(ok);
+            cnt += __popcll(bal);
+            if (bal == 0) continue;
+            for (int rnd = 0; rnd < TK_K; ++rnd) {                           // merge: pull the chunk's minima until one no longer beats the K-th
+                const u64 m = wave_min_u64(key);
+                if (m >= top[TK_K - 1]) break;
+                if (key == m) key = INV;                                     // keys are unique (grid position)
+                u64 c = m;
+#pragma unroll
+                for (int i = 0; i < TK_K; ++i) { const u64 tt = top[i]; const bool sw = c < tt; top[i] = sw ? c : tt; c = sw ? tt : c; }
+            }
+        } else {
+            if (key < b1) { b2 = b1; b1 = key; }
+            else if (key < b2) b2 = key;
+        }
+    }
+    if (!TOPK) {
+        const u64 m1 = wave_min_u64(b1);
+        top[0] = m1;
+        top[1] = wave_min_u64(b1 == m1 ? b2 : b1);                          // the winner's lane offers its runner-up
+    }
+}
+
+__device__ __forceinline__ unsigned int cand_word(u64 key) {                 // dist << 21 | payload << 16 | keypoint, or 0xFFFFFFFF
+    return key == ~0ull ? 0xFFFFFFFFu : ((unsigned)(key >> 40) << 21) | (unsigned)(key & 0x1FFFFFu);
+}
+
+// word w of an LDS bit array over a byte array: bit b = src[32 w + b] != 0 for 32 w + b < n.  src NULL: dflt (0 for a blocked set:
+// nothing blocked; ~0 for "observed": every query counts).  32 byte loads in flight (clamped, not predicated), then the bits.
+__device__ __forceinline__ unsigned int bits_word(const uint8_t* __restrict__ src, int n, int w, unsigned int dflt) {
+    if (!src) return dflt;
+    const int last = max(n - 1, 0);
+    unsigned v[32];
+#pragma unroll
+    for (int b = 0; b < 32; ++b) v[b] = src[min(w * 32 + b, last)];
+    unsigned int bits = 0;
+#pragma unroll
+    for (int b = 0; b < 32; ++b) if (w * 32 + b < n && v[b]) bits |= 1u << b;
+    return bits;
+}
+
+// ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment acc[0..nacc) (slot | bin << 16) of another bin
+// is cleared (:2696-2707) as ORBM_MATCH_PRUNED.  Returns the number of pruned entries (wave-uniform).
+__device__ __forceinline__ int rot_cull(const unsigned int* hist, const unsigned int* acc, int nacc, int* mrow, int lane) {
+    int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
+    for (int i = 0; i < 30; ++i) {
+        const int sz = (int)hist[i];
+        if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
+        else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
+        else if (sz > max3) { max3 = sz; i3 = i; }
+    }
+    if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
+    else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
+    int pruned = 0;
+    for (int e = lane; e < nacc; e += 64) {
+        const unsigned int v = acc[e];
+        const int bin = (int)(v >> 16), k = (int)(v & 0xFFFFu);
+        if (bin != i1 && bin != i2 && bin != i3) { mrow[k] = -2; ++pruned; }      // ORBM_MATCH_PRUNED
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
+    return pruned;
+}
+
+// per query row o: the window population, the radius a rescan reads back and the TK_K best candidates as words
+__device__ __forceinline__ void put_topk(int* out_cnt, float* out_r, unsigned int* out_keys, size_t o, int cnt, float r, const u64 (&top)[TK_K]) {
+    out_cnt[o] = cnt;
+    out_r[o] = r;
+    uint4* ok = (uint4*)(out_keys + o * TK_K);
+    ok[0] = make_uint4(cand_word(top[0]), cand_word(top[1]), cand_word(top[2]), cand_word(top[3]));
+    ok[1] = make_uint4(cand_word(top[4]), cand_word(top[5]), cand_word(top[6]), cand_word(top[7]));
+}
+
 #ifdef ORBX_AB   /* A/B reference (a wave per query), not in the product library */
 // The window's grid columns are flattened into ONE candidate list (column starts / lengths loaded by one lane each, prefix sum across
 // lanes), so that a window of up to 64 candidates costs four dependent round trips (cell ranges, indices, keypoints, descriptors)
@@ -1416,10 +1577,8 @@ __global__ __launch_bounds__(256) void k_track_topk16(const KpIn* __restrict__ k
     const int nMaxCellY = min(47, (int)ceilf((y - min_y + r) * inv_h));
     const bool hit = live && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0;
     const int ncols = hit ? nMaxCellX - nMinCellX + 1 : 0;                  // <= 64
-    const uint4* qp = (const uint4*)(desc + ((size_t)qf * cap + (live ? q : 0)) * 32);
-    const uint4 qlo = qp[0], qhi = qp[1];
-    const u64 a[4] = {(u64)qlo.x | ((u64)qlo.y << 32), (u64)qlo.z | ((u64)qlo.w << 32),
-                      (u64)qhi.x | ((u64)qhi.y << 32), (u64)qhi.z | ((u64)qhi.w << 32)};
+    u64 a[4];
+    load_desc(desc + ((size_t)qf * cap + (live ? q : 0)) * 32, a);
     if (l16 < TK_K) sTop[qr][l16] = make_uint2(INV, INV);
     int total = 0;
     for (int cb = 0; __any(cb < ncols); cb += 16) {
@@ -1471,60 +1630,6 @@ __global__ __launch_bounds__(256) void k_track_topk16(const KpIn* __restrict__ k
     }
 }
 
-// every listed candidate of query qi is blocked but its window holds more: the window again, blocked set applied (all 64 lanes; qi wave-uniform).
-// Returns the best candidate as distance << 21 | rotation bin << 16 | keypoint, or 0xFFFFFFFF.
-__device__ __forceinline__ unsigned int tk_rescan(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap, const int* __restrict__ grid_start,
-                                                  const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h, int qf, int tf, int qi,
-                                                  float th, const ScaleTab& st, float dx, float dy, float factor, const unsigned int* blk, int lane) {
-// every listed candidate is blocked but the window holds more: scan it again with the blocked set applied
-    const KpIn kq = kps[(size_t)qf * cap + qi];
-    const KpIn* kt = kps + (size_t)tf * cap;
-    const uint8_t* dt = desc + (size_t)tf * cap * 32;
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const int* gi = grid_idx + (size_t)tf * cap;
-    const float x = kq.x + dx, y = kq.y + dy, r = th * st.sf[kq.octave];
-    const int minLevel = kq.octave - 1, maxLevel = kq.octave + 1;
-    const int nMinCellX = max(0, (int)floorf((x - min_x - r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((x - min_x + r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - min_y - r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((y - min_y + r) * inv_h));
-    const uint4* qp = (const uint4*)(desc + ((size_t)qf * cap + qi) * 32);
-    const uint4 qlo = qp[0], qhi = qp[1];
-    const u64 a[4] = {(u64)qlo.x | ((u64)qlo.y << 32), (u64)qlo.z | ((u64)qlo.w << 32),
-                      (u64)qhi.x | ((u64)qhi.y << 32), (u64)qhi.z | ((u64)qhi.w << 32)};
-    u64 bk = ~0ull;
-    int ord0 = 0;
-    for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-        const int j0 = gs[ix * 48 + nMinCellY], j1 = gs[ix * 48 + nMaxCellY + 1];
-        for (int jb = j0; jb < j1; jb += 64) {
-            const int j = jb + lane;
-            if (j < j1) {
-                const int k = gi[j];
-                const KpIn kp = kt[k];
-                bool ok = !(kp.octave < minLevel) && !(kp.octave > maxLevel);
-                if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) ok = false;
-                if (ok && !((blk[k >> 5] >> (k & 31)) & 1u)) {
-                    const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
-                    const uint4 lo = tp[0], hi = tp[1];
-                    const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
-                                         (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
-                    float rot = kq.angle - kp.angle;
-                    if (rot < 0.0f) rot += 360.0f;
-                    int bin = (int)roundf(rot * factor);
-                    if (bin == 30) bin = 0;
-                    if (bin < 0 || bin >= 30) bin = TK_NOBIN;
-                    // (order among grid entries, not among window members: monotone in it, which is all the first-minimum rule needs)
-                    const u64 kk = ((u64)d << 44) | ((u64)(ord0 + (j - j0)) << 24) | ((u64)bin << 16) | (u64)k;
-                    bk = kk < bk ? kk : bk;
-                }
-            }
-        }
-        ord0 += j1 - j0;
-    }
-    bk = wave_min_u64(bk);
-    return bk != ~0ull ? ((unsigned)(bk >> 44) << 21) | (unsigned)(bk & 0x1FFFFFu) : 0xFFFFFFFFu;
-}
-
 #ifdef ORBX_AB   /* A/B reference (eight queries per step), not in the product library */
 __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
                                                     const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
@@ -1543,31 +1648,9 @@ __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps
     unsigned int* obsb = hist + 32;
     int* mrow = match + (size_t)pair * cap;
     unsigned int* acc = accepted + (size_t)pair * cap;
-    for (int w = lane; w < nwords; w += 64) {
-        unsigned int bits = 0;
-        if (t_blocked) {
-            const uint8_t* tb = t_blocked + (size_t)tf * cap;
-            const int last = max(nt - 1, 0);
-            unsigned v[32];                                                 // 32 byte loads in flight (clamped, not predicated), then the bits
-#pragma unroll
-            for (int b = 0; b < 32; ++b) v[b] = tb[min(w * 32 + b, last)];
-#pragma unroll
-            for (int b = 0; b < 32; ++b) if (w * 32 + b < nt && v[b]) bits |= 1u << b;
-        }
-        blk[w] = bits;
-        unsigned int ob = 0xFFFFFFFFu;                                      // q_obs absent: every query counts as observed
-        if (q_obs) {
-            const uint8_t* qo = q_obs + (size_t)qf * cap;
-            const int last = max(nq - 1, 0);
-            unsigned v[32];
-#pragma unroll
-            for (int b = 0; b < 32; ++b) v[b] = qo[min(w * 32 + b, last)];
-            ob = 0;
-#pragma unroll
-            for (int b = 0; b < 32; ++b) if (v[b]) ob |= 1u << b;
-        }
-        obsb[w] = ob;
-    }
+    const uint8_t* tb = t_blocked ? t_blocked + (size_t)tf * cap : nullptr;
+    const uint8_t* qo = q_obs ? q_obs + (size_t)qf * cap : nullptr;
+    for (int w = lane; w < nwords; w += 64) { blk[w] = bits_word(tb, nt, w, 0u); obsb[w] = bits_word(qo, nq, w, 0xFFFFFFFFu); }
     if (lane < 32) hist[lane] = 0;
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                        // ORBM_NO_MATCH
     __syncthreads();
@@ -1649,8 +1732,15 @@ __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps
             if (bal) best = (unsigned int)__builtin_amdgcn_readlane((int)key, __ffsll((long long)bal) - 1);   // (wave-uniform lane: no LDS crossbar round trip)
             else {
                 const int c = __builtin_amdgcn_readlane(cnt, 8 * s);
-                if (c > TK_K) {
-                    best = tk_rescan(kps, desc, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, qf, tf, qi, th, st, dx, dy, factor, blk, lane);
+                if (c > TK_K) {                                             // the list ran dry, the window holds more: rescan it, blocked set applied
+                    const KpIn kq = kps[(size_t)qf * cap + qi];                     // the window k_track_topk16 swept
+                    const Win w = {kq.x + dx, kq.y + dy, th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
+                    u64 a[4], top[TK_K];
+                    load_desc(desc + ((size_t)qf * cap + qi) * 32, a);
+                    int c2;
+                    win_sweep<false>(w, RotBinPay{kq.angle, factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, nullptr,
+                                     grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                    best = cand_word(top[0]);
                 }
             }
             if (best == 0xFFFFFFFFu) continue;
@@ -1672,27 +1762,7 @@ __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps
       ak0 = bk0; ak1 = bk1; ak2 = bk2; ak3 = bk3; ac0 = bc0; ac1 = bc1; ac2 = bc2; ac3 = bc3;
     }
     __syncthreads();
-    if (check_ori) {
-        // ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment of the other bins is cleared (:2696-2707)
-        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = (int)hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
-        int pruned = 0;
-        for (int e = lane; e < nacc; e += 64) {
-            const unsigned int v = acc[e];
-            const int bin = (int)(v >> 16), k = (int)(v & 0xFFFFu);
-            if (bin != i1 && bin != i2 && bin != i3) { mrow[k] = -2; ++pruned; }      // ORBM_MATCH_PRUNED
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
-        nm -= pruned;
-    }
+    if (check_ori) nm -= rot_cull(hist, acc, nacc, mrow, lane);
     if (lane == 0) nmatches[pair] = nm;
 }
 
@@ -1716,31 +1786,9 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
     unsigned int* tag = obsb + nwords;                                      // [cap]: per slot the latest proposal (round << 6 | 63 - lane), see below
     int* mrow = match + (size_t)pair * cap;
     unsigned int* acc = accepted + (size_t)pair * cap;
-    for (int w = lane; w < nwords; w += 64) {
-        unsigned int bits = 0;
-        if (t_blocked) {
-            const uint8_t* tb = t_blocked + (size_t)tf * cap;
-            const int last = max(nt - 1, 0);
-            unsigned v[32];                                                 // 32 byte loads in flight (clamped, not predicated), then the bits
-#pragma unroll
-            for (int b = 0; b < 32; ++b) v[b] = tb[min(w * 32 + b, last)];
-#pragma unroll
-            for (int b = 0; b < 32; ++b) if (w * 32 + b < nt && v[b]) bits |= 1u << b;
-        }
-        blk[w] = bits;
-        unsigned int ob = 0xFFFFFFFFu;                                      // q_obs absent: every query counts as observed
-        if (q_obs) {
-            const uint8_t* qo = q_obs + (size_t)qf * cap;
-            const int last = max(nq - 1, 0);
-            unsigned v[32];
-#pragma unroll
-            for (int b = 0; b < 32; ++b) v[b] = qo[min(w * 32 + b, last)];
-            ob = 0;
-#pragma unroll
-            for (int b = 0; b < 32; ++b) if (v[b]) ob |= 1u << b;
-        }
-        obsb[w] = ob;
-    }
+    const uint8_t* tb = t_blocked ? t_blocked + (size_t)tf * cap : nullptr;
+    const uint8_t* qo = q_obs ? q_obs + (size_t)qf * cap : nullptr;
+    for (int w = lane; w < nwords; w += 64) { blk[w] = bits_word(tb, nt, w, 0u); obsb[w] = bits_word(qo, nq, w, 0xFFFFFFFFu); }
     if (lane < 32) hist[lane] = 0;
     for (int k = lane; k < cap; k += 64) { mrow[k] = -1; tag[k] = 0; }       // ORBM_NO_MATCH
     __syncthreads();
@@ -1750,7 +1798,7 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
     // that is free right now; per slot the lowest lane wins (LDS atomicMax of round << 6 | 63 - lane, then a read-back).  The queries
     // below the first loser f take their proposals at once -- none of them wanted a slot a lower query took, and everything listed before
     // a proposal was blocked already, so this IS what the one-by-one replay (:2555-2593) does for them -- query f is resolved alone with
-    // those claims applied (its proposal is gone, or its list ran dry with more in the window: tk_rescan), and the rest of the 64 propose
+    // those claims applied (its proposal is gone, or its list ran dry with more in the window: win_sweep), and the rest of the 64 propose
     // again.  Lists come from another XCD's writes, i.e. from memory: the next 64 queries' loads are in flight while these are resolved;
     // the loaded values are touched only when their window becomes current, and the loads are unconditional (clamped index).
     const int qLast = max(nq - 1, 0);
@@ -1823,8 +1871,16 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
                     const bool fr = ki != 0xFFFFFFFFu && !((blk[k >> 5] >> (k & 31)) & 1u);
                     best = fr ? ki : best;
                 }
-                if (best == 0xFFFFFFFFu && __builtin_amdgcn_readlane(cnt, f) > TK_K)
-                    best = tk_rescan(kps, desc, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, qf, tf, qi, th, st, dx, dy, factor, blk, lane);
+                if (best == 0xFFFFFFFFu && __builtin_amdgcn_readlane(cnt, f) > TK_K) {   // the list ran dry, the window holds more: rescan it, blocked set applied
+                    const KpIn kq = kps[(size_t)qf * cap + qi];                     // the window k_track_topk16 swept
+                    const Win w = {kq.x + dx, kq.y + dy, th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
+                    u64 a[4], top[TK_K];
+                    load_desc(desc + ((size_t)qf * cap + qi) * 32, a);
+                    int c2;
+                    win_sweep<false>(w, RotBinPay{kq.angle, factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, nullptr,
+                                     grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                    best = cand_word(top[0]);
+                }
                 if (best != 0xFFFFFFFFu && (best >> 21) <= 100u) {
                     const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
                     const bool obs = (obsb[qi >> 5] >> (qi & 31)) & 1u;
@@ -1845,27 +1901,7 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
         alo = blo; ahi = bhi; ac = bc;
     }
     __syncthreads();
-    if (check_ori) {
-        // ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment of the other bins is cleared (:2696-2707)
-        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = (int)hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
-        int pruned = 0;
-        for (int e = lane; e < nacc; e += 64) {
-            const unsigned int v = acc[e];
-            const int bin = (int)(v >> 16), k = (int)(v & 0xFFFFu);
-            if (bin != i1 && bin != i2 && bin != i3) { mrow[k] = -2; ++pruned; }      // ORBM_MATCH_PRUNED
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
-        nm -= pruned;
-    }
+    if (check_ori) nm -= rot_cull(hist, acc, nacc, mrow, lane);
     if (lane == 0) nmatches[pair] = nm;
 }
 
@@ -1875,17 +1911,15 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
 // result block.  Per query the window is derived on the device (RadiusByViewingCos [* th] * scale[level], levels [level-1, level],
 // the mvuRight gate, :66-117); a query that is not in view, lies beyond th_far (bFarPoints) or has a level outside the table reads
 // nothing else of its row (k_frustum leaves those fields unwritten for rejected points).
-// k_lp_topk: wave per query.  The window's grid columns are flattened into one list (column ranges loaded one per lane, prefix sum
-//   across the wave), so that a window of up to 64 grid entries costs one pass whatever its column count and larger ones (th = 10,
-//   high levels: r up to 4 * th * scale) take more passes of 64.  Out: the window population and its LP_K best candidates in
-//   (distance, visiting order) rank, each as ONE word dist << 20 | (octave + 1) << 16 | keypoint (the replay reads the level of
-//   best and second from it; no second gather).
+// k_lp_topk: wave per query, one win_sweep: a window of up to 64 grid entries costs one pass whatever its column count and larger
+//   ones (th = 10, high levels: r up to 4 * th * scale) take more passes of 64.  Out: the window population and its TK_K best
+//   candidates in (distance, visiting order) rank, each as ONE word dist << 21 | (octave + 1) << 16 | keypoint (the replay reads the
+//   level of best and second from it; no second gather).
 // k_lp_claim: one wave per frame replays the claims in query order (:119-164).  A query's list sits in LDS, one candidate per lane;
 //   one ballot over the blocked bit array gives its first two unblocked candidates -- best and second, as `dist < bestDist` /
 //   `else if dist < bestDist2` would have met them.  A truncated list with fewer than two unblocked entries is rescanned in full,
-//   blocked set applied (lp_sweep<false>).
+//   blocked set applied (win_sweep<false>).
 // ------------------------------------------------------------------------------------------------
-#define LP_K 8
 struct LpRows {                                            // the per-query arrays of one call, [nframes][q_stride] unless q_shared
     const int* nq; int q_stride;
     const uint8_t* in_view; const float* px; const float* py; const float* pxr; const float* view_cos; const int* level;
@@ -1893,10 +1927,9 @@ struct LpRows {                                            // the per-query arra
     const uint8_t* qdesc; const uint8_t* mp_obs; int q_shared;
     float th; int nlevels;
 };
-struct LpWin { float x, y, r, ur; int level; };
 
 // the window of query row o (wave-uniform), or false: the query is skipped
-__device__ __forceinline__ bool lp_query(const LpRows& R, const float* sf, bool stereo, size_t o, LpWin& w) {
+__device__ __forceinline__ bool lp_query(const LpRows& R, const float* sf, bool stereo, size_t o, Win& w) {
     if (!R.in_view[o]) return false;
     if (R.depth && R.depth[o] > R.th_far) return false;                      // bFarPoints (:57-58)
     const int lvl = R.level[o];
@@ -1904,100 +1937,9 @@ __device__ __forceinline__ bool lp_query(const LpRows& R, const float* sf, bool 
     float r = (double)R.view_cos[o] > 0.998 ? 2.5f : 4.0f;                   // RadiusByViewingCos (:242-249): float against a double literal
     if (R.th != 1.0f) r *= R.th;
     w.r = r * sf[lvl];                                                     // one float multiply, as GetFeaturesInArea's argument
-    w.x = R.px[o]; w.y = R.py[o]; w.level = lvl;
+    w.x = R.px[o]; w.y = R.py[o]; w.minLevel = lvl - 1; w.maxLevel = lvl;
     w.ur = stereo ? R.pxr[o] : 0.f;
     return true;
-}
-
-// One sweep of window w over a frame's grid (w wave-uniform, all 64 lanes).  Grid positions j are monotone in the reference's visiting
-// order (cell = ix * 48 + iy, cells ascending in the CSR), so (distance, j) ranks the candidates as the scan meets them.
-// key = dist << 40 | j << 20 | (octave + 1) << 16 | keypoint (j, keypoint < 65536; octave in [level - 1, level] with level < 12).
-// TOPK: cnt = window population, top[0..LP_K) = its LP_K smallest keys (wave-uniform).
-// !TOPK: only candidates not blocked in blk; top[0], top[1] = the two smallest.
-template <bool TOPK>
-__device__ __forceinline__ void lp_sweep(const LpWin& w, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt, const float* __restrict__ urt,
-                                         const int* __restrict__ gs, const int* __restrict__ gi, float min_x, float min_y, float inv_w, float inv_h,
-                                         const u64 (&a)[4], const unsigned int* blk, int lane, int& cnt, u64 (&top)[LP_K]) {
-    const u64 INV = ~0ull;
-#pragma unroll
-    for (int i = 0; i < LP_K; ++i) top[i] = INV;
-    cnt = 0;
-    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
-    if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
-    const int ncols = nMaxCellX - nMinCellX + 1;                             // 1 .. 64: one column per lane
-    int cj0 = 0, clen = 0;
-    if (lane < ncols) {
-        const int ix = nMinCellX + lane;
-        cj0 = gs[ix * 48 + nMinCellY];
-        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
-    }
-    int total;
-    const int excl = wave_excl_scan(clen, &total);
-    u64 b1 = INV, b2 = INV;                                                  // !TOPK: the lane's two smallest
-    for (int base = 0; base < total; base += 64) {
-        const int t = base + lane;
-        int cs = 0, c0 = 0;
-        for (int c = 0; c < ncols; ++c) {                                    // t's column: the last one starting at or before t
-            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
-            if (t >= e) { cs = e; c0 = s; }
-        }
-        bool ok = false;
-        u64 key = INV;
-        if (t < total) {
-            const int j = c0 + (t - cs);
-            const int k = gi[j];
-            const KpIn kp = kt[k];
-            ok = !(kp.octave < w.level - 1) && !(kp.octave > w.level);       // bCheckLevels is true here (maxLevel >= 0)
-            if (!(fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r)) ok = false;
-            if (ok && urt) {
-                const float urk = urt[k];
-                if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // :107-117
-            }
-            if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
-            if (ok) {
-                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
-                const uint4 lo = tp[0], hi = tp[1];
-                const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
-                                     (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
-                key = ((u64)d << 40) | ((u64)j << 20) | ((u64)(kp.octave + 1) << 16) | (u64)k;
-            }
-        }
-        if (TOPK) {
-            const unsigned long long bal = __ballot(ok);
-            cnt += __popcll(bal);
-            if (bal == 0) continue;
-            for (int rnd = 0; rnd < LP_K; ++rnd) {                           // merge: pull the chunk's minima until one no longer beats the K-th
-                const u64 m = wave_min_u64(key);
-                if (m >= top[LP_K - 1]) break;
-                if (key == m) key = INV;                                     // keys are unique (grid position)
-                u64 c = m;
-#pragma unroll
-                for (int i = 0; i < LP_K; ++i) { const u64 tt = top[i]; const bool sw = c < tt; top[i] = sw ? c : tt; c = sw ? tt : c; }
-            }
-        } else {
-            if (key < b1) { b2 = b1; b1 = key; }
-            else if (key < b2) b2 = key;
-        }
-    }
-    if (!TOPK) {
-        const u64 m1 = wave_min_u64(b1);
-        top[0] = m1;
-        top[1] = wave_min_u64(b1 == m1 ? b2 : b1);                          // the winner's lane offers its runner-up
-    }
-}
-
-__device__ __forceinline__ unsigned int lp_word(u64 key) {                   // dist << 20 | (octave + 1) << 16 | keypoint, or 0xFFFFFFFF
-    return key == ~0ull ? 0xFFFFFFFFu : ((unsigned)(key >> 40) << 20) | (unsigned)(key & 0xFFFFFu);
-}
-
-__device__ __forceinline__ void lp_qdesc(const LpRows& R, size_t qrow, u64 (&a)[4]) {
-    const uint4* qp = (const uint4*)(R.qdesc + qrow * 32);
-    const uint4 qlo = qp[0], qhi = qp[1];
-    a[0] = (u64)qlo.x | ((u64)qlo.y << 32); a[1] = (u64)qlo.z | ((u64)qlo.w << 32);
-    a[2] = (u64)qhi.x | ((u64)qhi.y << 32); a[3] = (u64)qhi.z | ((u64)qhi.w << 32);
 }
 
 __global__ __launch_bounds__(256) void k_lp_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
@@ -2011,25 +1953,19 @@ __global__ __launch_bounds__(256) void k_lp_topk(const KpIn* __restrict__ kps, c
     const int nq = min(max(R.nq[f], 0), R.q_stride);
     if (q >= nq) return;
     const size_t o = (size_t)f * R.q_stride + q;
-    LpWin w;
+    Win w;
     int cnt = 0;
-    u64 top[LP_K];
+    u64 top[TK_K];
     if (lp_query(R, st.sf, uright != nullptr, o, w)) {
         u64 a[4];
-        lp_qdesc(R, R.q_shared ? (size_t)q : o, a);
-        lp_sweep<true>(w, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)f * cap : nullptr,
-                       grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
+        load_desc(R.qdesc + (R.q_shared ? (size_t)q : o) * 32, a);
+        win_sweep<true>(w, OctavePay{}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)f * cap : nullptr,
+                        grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
-        for (int i = 0; i < LP_K; ++i) top[i] = ~0ull;
+        for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
-    if (lane == 0) {
-        out_cnt[o] = cnt;
-        out_r[o] = w.r;                                                      // read back only by a rescan (count > LP_K)
-        uint4* ok = (uint4*)(out_keys + o * LP_K);
-        ok[0] = make_uint4(lp_word(top[0]), lp_word(top[1]), lp_word(top[2]), lp_word(top[3]));
-        ok[1] = make_uint4(lp_word(top[4]), lp_word(top[5]), lp_word(top[6]), lp_word(top[7]));
-    }
+    if (lane == 0) put_topk(out_cnt, out_r, out_keys, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
 }
 
 __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
@@ -2038,7 +1974,7 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
                                                  const uint8_t* __restrict__ t_blocked, LpRows R, float nnratio,
                                                  const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
                                                  int* __restrict__ match, int* __restrict__ nmatches) {
-    extern __shared__ unsigned int lp_lds[];                                 // blocked bit array [ceil(cap / 32)], the current 64 queries' lists [64][LP_K]
+    extern __shared__ unsigned int lp_lds[];                                 // blocked bit array [ceil(cap / 32)], the current 64 queries' lists [64][TK_K]
     const unsigned INV = 0xFFFFFFFFu;
     const int lane = threadIdx.x, f = blockIdx.x, tf = t_first + f;
     const int nt = min(max(counts[tf], 0), cap);
@@ -2047,15 +1983,7 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
     unsigned int* blk = lp_lds;
     unsigned int* sk = lp_lds + nwords;
     int* mrow = match + (size_t)f * cap;
-    for (int wd = lane; wd < nwords; wd += 64) {
-        unsigned int bits = 0;
-        if (t_blocked) {
-            const uint8_t* tb = t_blocked + (size_t)f * cap;
-#pragma unroll 8
-            for (int b = 0; b < 32; ++b) if (wd * 32 + b < nt && tb[wd * 32 + b]) bits |= 1u << b;
-        }
-        blk[wd] = bits;
-    }
+    for (int wd = lane; wd < nwords; wd += 64) blk[wd] = bits_word(t_blocked ? t_blocked + (size_t)f * cap : nullptr, nt, wd, 0u);
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
     __syncthreads();
     const KpIn* kt = kps + (size_t)tf * cap;
@@ -2066,13 +1994,13 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
     const size_t rowBase = (size_t)f * R.q_stride;
     int nm = 0;
     // the next 64 queries' lists, counts and observation flags are in flight while the current ones are replayed (clamped, unconditional loads)
-    unsigned int pk[LP_K];
+    unsigned int pk[TK_K];
     int pc = 0;
     uint8_t pob = 0;
     auto fetch = [&](int W0) {
-        const int last = nq * LP_K - 1;
+        const int last = nq * TK_K - 1;
 #pragma unroll
-        for (int r = 0; r < LP_K; ++r) pk[r] = topKeys[rowBase * LP_K + min(W0 * LP_K + r * 64 + lane, last)];
+        for (int r = 0; r < TK_K; ++r) pk[r] = topKeys[rowBase * TK_K + min(W0 * TK_K + r * 64 + lane, last)];
         const int qc = min(W0 + lane, nq - 1);
         pc = topCnt[rowBase + qc];
         pob = R.mp_obs[R.q_shared ? (size_t)qc : rowBase + qc];
@@ -2080,7 +2008,7 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
     if (nq > 0) fetch(0);
     for (int W0 = 0; W0 < nq; W0 += 64) {
 #pragma unroll
-        for (int r = 0; r < LP_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * LP_K .. + LP_K)
+        for (int r = 0; r < TK_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * TK_K .. + TK_K)
         const int cnt = W0 + lane < nq ? pc : 0;
         const int ob = pob != 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2092,8 +2020,8 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
             todo &= todo - 1;
             unsigned int key = INV;
             bool fr = false;
-            if (lane < LP_K) {
-                key = sk[i * LP_K + lane];
+            if (lane < TK_K) {
+                key = sk[i * TK_K + lane];
                 const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
                 fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
             }
@@ -2104,21 +2032,19 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
                 fb &= fb - 1;
                 if (fb) w2 = (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1);
             }
-            if (w2 == INV && __builtin_amdgcn_readlane(cnt, i) > LP_K) {
+            if (w2 == INV && __builtin_amdgcn_readlane(cnt, i) > TK_K) {
                 // best AND second must come from the unblocked candidates: the listed ones ran dry, the window holds more
                 const size_t o = rowBase + W0 + i;
-                LpWin w;                                                     // the window k_lp_topk swept (its radius from there: no scale table here)
-                w.x = R.px[o]; w.y = R.py[o]; w.r = topR[o]; w.level = R.level[o]; w.ur = uright ? R.pxr[o] : 0.f;
-                u64 a[4];
-                lp_qdesc(R, R.q_shared ? (size_t)(W0 + i) : o, a);
-                u64 top[LP_K];
+                const Win w = {R.px[o], R.py[o], topR[o], uright ? R.pxr[o] : 0.f, R.level[o] - 1, R.level[o]};   // the window k_lp_topk swept
+                u64 a[4], top[TK_K];                                         // (its radius from there: no scale table here)
+                load_desc(R.qdesc + (R.q_shared ? (size_t)(W0 + i) : o) * 32, a);
                 int c2;
-                lp_sweep<false>(w, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
-                w1 = lp_word(top[0]); w2 = lp_word(top[1]);
+                win_sweep<false>(w, OctavePay{}, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                w1 = cand_word(top[0]); w2 = cand_word(top[1]);
             }
             if (w1 == INV) continue;
-            const int bestDist = (int)(w1 >> 20), bestLevel = (int)((w1 >> 16) & 15u) - 1;
-            const int bestDist2 = w2 == INV ? 256 : (int)(w2 >> 20), bestLevel2 = w2 == INV ? -1 : (int)((w2 >> 16) & 15u) - 1;
+            const int bestDist = (int)(w1 >> 21), bestLevel = (int)((w1 >> 16) & 31u) - 1;
+            const int bestDist2 = w2 == INV ? 256 : (int)(w2 >> 21), bestLevel2 = w2 == INV ? -1 : (int)((w2 >> 16) & 31u) - 1;
             if (bestDist <= 100) {                                           // TH_HIGH (:119)
                 if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
                 if (bestLevel != bestLevel2 || (float)bestDist <= nnratio * (float)bestDist2) {
@@ -2152,139 +2078,42 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
 //   costs four dependent round trips (cell ranges, grid indices, keypoints, descriptors) whatever its lane count, 64 pairs x 1000
 //   queries are 64 k waves -- enough to fill the machine by waves rather than by lanes --, and the windows the same call must also
 //   take (th 30 on level 7: 30 * 1.2^7 = 107 px, a few hundred entries; the retry doubles th again) then need a few passes of 64
-//   instead of many passes of 16 with the per-pass merge each time.  The window's grid columns are flattened into one list (ranges
-//   one per lane, prefix sum across the wave) as in k_lp_topk.  Out: the window population and its MM_K best candidates in
-//   (distance, visiting order) rank as ONE word each, dist << 21 | rotation bin << 16 | keypoint (bin of angle_q - angle_t as
-//   :2596-2603, TK_NOBIN outside [0, 30)), so the claim needs no second gather.
+//   instead of many passes of 16 with the per-pass merge each time: one win_sweep, as in k_lp_topk.  Out: the window population and
+//   its TK_K best candidates in (distance, visiting order) rank as ONE word each, dist << 21 | rotation bin << 16 | keypoint (bin of
+//   angle_q - angle_t as :2596-2603, TK_NOBIN outside [0, 30)), so the claim needs no second gather.
 // k_mm_claim: one wave per pair replays the claims in query order (:2553-2612).  A query's list sits in LDS, one candidate per lane;
 //   one ballot over the blocked bit array gives its first unblocked candidate, which is its `dist < bestDist` winner.  A truncated
-//   list whose candidates are all blocked is rescanned in full with the blocked set applied (mm_sweep<false>).  Each assignment with
+//   list whose candidates are all blocked is rescanned in full with the blocked set applied (win_sweep<false>).  Each assignment with
 //   a rotation bin is appended to a per-pair list and counted in an LDS histogram; the three-maxima cull then marks every slot of a
 //   culled bin ORBM_MATCH_PRUNED once per entry, so a slot claimed twice is culled (and uncounted) as often as the reference does.
 // RETRY: the same two kernels at 2 * th for the pairs whose count is below retry_below, from an empty frame (mvpMapPoints filled
 //   with NULL: no blocked slots); every other pair returns at once, so the retry needs no host round trip.
 // ------------------------------------------------------------------------------------------------
-#define MM_K 8
 struct MmRows {                                            // the per-query arrays of one call, [npairs][q_stride]
     const int* nq; int q_stride;
     const uint8_t* valid; const float* u; const float* v; const float* invzc; const int* octave; const float* angle;
     const uint8_t* qdesc; const uint8_t* mp_obs; const uint8_t* dir;
     float mbf, factor; int nlevels, retry_below, check_ori;
 };
-struct MmWin { float x, y, r, ur, qangle; int minLevel, maxLevel; };
 
 // the window of valid query row o of pair p with octave oc, all but its radius
-__device__ __forceinline__ void mm_levels(const MmRows& R, int p, int oc, size_t o, bool stereo, MmWin& w) {
+__device__ __forceinline__ void mm_levels(const MmRows& R, int p, int oc, size_t o, bool stereo, Win& w) {
     const int d = R.dir ? R.dir[p] : 0;
     if (d == 1) { w.minLevel = oc; w.maxLevel = -1; }                        // bForward: GetFeaturesInArea(.., nLastOctave)
     else if (d == 2) { w.minLevel = 0; w.maxLevel = oc; }                    // bBackward
     else { w.minLevel = oc - 1; w.maxLevel = oc + 1; }
-    w.x = R.u[o]; w.y = R.v[o]; w.qangle = R.angle[o];
+    w.x = R.u[o]; w.y = R.v[o];
     w.ur = stereo ? R.u[o] - R.mbf * R.invzc[o] : 0.f;                       // :2571
 }
 
 // the window of query row o of pair p (wave-uniform), or false: the query is skipped
-__device__ __forceinline__ bool mm_query(const MmRows& R, const float* sf, float th, bool stereo, int p, size_t o, MmWin& w) {
+__device__ __forceinline__ bool mm_query(const MmRows& R, const float* sf, float th, bool stereo, int p, size_t o, Win& w) {
     if (!R.valid[o]) return false;
     const int oc = R.octave[o];
     if (oc < 0 || oc >= R.nlevels) return false;
     w.r = th * sf[oc];                                                       // :2536, one float multiply
     mm_levels(R, p, oc, o, stereo, w);
     return true;
-}
-
-// One sweep of window w over a frame's grid (w wave-uniform, all 64 lanes); grid positions j follow the reference's visiting order.
-// key = dist << 40 | j << 21 | bin << 16 | keypoint (j, keypoint < 65536).
-// TOPK: cnt = window population, top[0..MM_K) = its MM_K smallest keys.  !TOPK: top[0] = the smallest key not blocked in blk.
-template <bool TOPK>
-__device__ __forceinline__ void mm_sweep(const MmWin& w, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt, const float* __restrict__ urt,
-                                         const int* __restrict__ gs, const int* __restrict__ gi, float min_x, float min_y, float inv_w, float inv_h,
-                                         float factor, const u64 (&a)[4], const unsigned int* blk, int lane, int& cnt, u64 (&top)[MM_K]) {
-    const u64 INV = ~0ull;
-#pragma unroll
-    for (int i = 0; i < MM_K; ++i) top[i] = INV;
-    cnt = 0;
-    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
-    if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
-    const bool bCheckLevels = (w.minLevel > 0) || (w.maxLevel >= 0);
-    const int ncols = nMaxCellX - nMinCellX + 1;                             // 1 .. 64: one column per lane
-    int cj0 = 0, clen = 0;
-    if (lane < ncols) {
-        const int ix = nMinCellX + lane;
-        cj0 = gs[ix * 48 + nMinCellY];
-        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
-    }
-    int total;
-    const int excl = wave_excl_scan(clen, &total);
-    u64 b1 = INV;
-    for (int base = 0; base < total; base += 64) {
-        const int t = base + lane;
-        int cs = 0, c0 = 0;
-        for (int c = 0; c < ncols; ++c) {                                    // t's column: the last one starting at or before t
-            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
-            if (t >= e) { cs = e; c0 = s; }
-        }
-        bool ok = false;
-        u64 key = INV;
-        if (t < total) {
-            const int j = c0 + (t - cs);
-            const int k = gi[j];
-            const KpIn kp = kt[k];
-            ok = true;
-            if (bCheckLevels) {
-                if (kp.octave < w.minLevel) ok = false;
-                if (w.maxLevel >= 0 && kp.octave > w.maxLevel) ok = false;
-            }
-            if (!(fabsf(kp.x - w.x) < w.r && fabsf(kp.y - w.y) < w.r)) ok = false;
-            if (ok && urt) {
-                const float urk = urt[k];
-                if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // :2569-2576
-            }
-            if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
-            if (ok) {
-                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
-                const uint4 lo = tp[0], hi = tp[1];
-                const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
-                                     (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
-                float rot = w.qangle - kp.angle;                             // :2596-2603
-                if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == 30) bin = 0;
-                if (bin < 0 || bin >= 30) bin = TK_NOBIN;
-                key = ((u64)d << 40) | ((u64)j << 21) | ((u64)bin << 16) | (u64)k;
-            }
-        }
-        if (TOPK) {
-            const unsigned long long bal = __ballot(ok);
-            cnt += __popcll(bal);
-            if (bal == 0) continue;
-            for (int rnd = 0; rnd < MM_K; ++rnd) {                           // merge: pull the chunk's minima until one no longer beats the K-th
-                const u64 m = wave_min_u64(key);
-                if (m >= top[MM_K - 1]) break;
-                if (key == m) key = INV;                                     // keys are unique (grid position)
-                u64 c = m;
-#pragma unroll
-                for (int i = 0; i < MM_K; ++i) { const u64 tt = top[i]; const bool sw = c < tt; top[i] = sw ? c : tt; c = sw ? tt : c; }
-            }
-        } else {
-            b1 = key < b1 ? key : b1;
-        }
-    }
-    if (!TOPK) top[0] = wave_min_u64(b1);
-}
-
-__device__ __forceinline__ unsigned int mm_word(u64 key) {                   // dist << 21 | bin << 16 | keypoint, or 0xFFFFFFFF
-    return key == ~0ull ? 0xFFFFFFFFu : ((unsigned)(key >> 40) << 21) | (unsigned)(key & 0x1FFFFFu);
-}
-
-__device__ __forceinline__ void mm_qdesc(const MmRows& R, size_t o, u64 (&a)[4]) {
-    const uint4* qp = (const uint4*)(R.qdesc + o * 32);
-    const uint4 qlo = qp[0], qhi = qp[1];
-    a[0] = (u64)qlo.x | ((u64)qlo.y << 32); a[1] = (u64)qlo.z | ((u64)qlo.w << 32);
-    a[2] = (u64)qhi.x | ((u64)qhi.y << 32); a[3] = (u64)qhi.z | ((u64)qhi.w << 32);
 }
 
 template <bool RETRY>
@@ -2300,27 +2129,20 @@ __global__ __launch_bounds__(256) void k_mm_topk(const KpIn* __restrict__ kps, c
     const int nq = min(max(R.nq[p], 0), R.q_stride);
     if (q >= nq) return;
     const size_t o = (size_t)p * R.q_stride + q;
-    MmWin w;
+    Win w;
     w.r = 0.f;                                                               // (a skipped query's out_r is written but never read)
     int cnt = 0;
-    u64 top[MM_K];
+    u64 top[TK_K];
     if (mm_query(R, st.sf, th, uright != nullptr, p, o, w)) {
         u64 a[4];
-        mm_qdesc(R, o, a);
-        mm_sweep<true>(w, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)p * cap : nullptr,
-                       grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, R.factor, a, nullptr,
-                       lane, cnt, top);
+        load_desc(R.qdesc + o * 32, a);
+        win_sweep<true>(w, RotBinPay{R.angle[o], R.factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)p * cap : nullptr,
+                        grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
-        for (int i = 0; i < MM_K; ++i) top[i] = ~0ull;
+        for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
-    if (lane == 0) {
-        out_cnt[o] = cnt;
-        out_r[o] = w.r;                                                      // read back only by a rescan (count > MM_K)
-        uint4* ok = (uint4*)(out_keys + o * MM_K);
-        ok[0] = make_uint4(mm_word(top[0]), mm_word(top[1]), mm_word(top[2]), mm_word(top[3]));
-        ok[1] = make_uint4(mm_word(top[4]), mm_word(top[5]), mm_word(top[6]), mm_word(top[7]));
-    }
+    if (lane == 0) put_topk(out_cnt, out_r, out_keys, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
 }
 
 template <bool RETRY>
@@ -2331,7 +2153,7 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
                                                  const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
                                                  unsigned int* __restrict__ accepted,
                                                  int* __restrict__ match, int* __restrict__ nmatches, uint8_t* __restrict__ retried) {
-    extern __shared__ unsigned int mm_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][MM_K]
+    extern __shared__ unsigned int mm_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][TK_K]
     const unsigned INV = 0xFFFFFFFFu;
     const int lane = threadIdx.x, p = blockIdx.x, tf = t_first + p;
     if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // (wave-uniform) the first search of this pair stands
@@ -2342,15 +2164,8 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
     unsigned int* hist = mm_lds + nwords;
     unsigned int* sk = hist + 32;
     int* mrow = match + (size_t)p * cap;
-    for (int wd = lane; wd < nwords; wd += 64) {
-        unsigned int bits = 0;
-        if (!RETRY && t_blocked) {                                           // the retry starts from an empty frame (Tracking.cc:3217)
-            const uint8_t* tb = t_blocked + (size_t)p * cap;
-#pragma unroll 8
-            for (int b = 0; b < 32; ++b) if (wd * 32 + b < nt && tb[wd * 32 + b]) bits |= 1u << b;
-        }
-        blk[wd] = bits;
-    }
+    const uint8_t* tb = !RETRY && t_blocked ? t_blocked + (size_t)p * cap : nullptr;   // the retry starts from an empty frame (Tracking.cc:3217)
+    for (int wd = lane; wd < nwords; wd += 64) blk[wd] = bits_word(tb, nt, wd, 0u);
     if (lane < 32) hist[lane] = 0;
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
     __syncthreads();
@@ -2364,16 +2179,16 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
     int nm = 0, nacc = 0;
     // the next 64 queries' lists and counts are in flight while the current ones are replayed (clamped, unconditional loads);
     // mp_obs is read only for a query with candidates (a skipped row reads nothing else)
-    const unsigned int* keyRow = topKeys + rowBase * MM_K;
+    const unsigned int* keyRow = topKeys + rowBase * TK_K;
     const int* cntRow = topCnt + rowBase;
     const uint8_t* obRow = R.mp_obs + rowBase;
-    unsigned int pk[MM_K];
+    unsigned int pk[TK_K];
     int pc = 0;
     uint8_t pob = 0;
     auto fetch = [&](int W0) {
-        const int last = nq * MM_K - 1;
+        const int last = nq * TK_K - 1;
 #pragma unroll
-        for (int r = 0; r < MM_K; ++r) pk[r] = keyRow[min(W0 * MM_K + r * 64 + lane, last)];
+        for (int r = 0; r < TK_K; ++r) pk[r] = keyRow[min(W0 * TK_K + r * 64 + lane, last)];
         const int qc = min(W0 + lane, nq - 1);
         pc = cntRow[qc];
         pob = (W0 + lane < nq && pc > 0) ? obRow[qc] : 0;
@@ -2381,7 +2196,7 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
     if (nq > 0) fetch(0);
     for (int W0 = 0; W0 < nq; W0 += 64) {
 #pragma unroll
-        for (int r = 0; r < MM_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * MM_K .. + MM_K)
+        for (int r = 0; r < TK_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * TK_K .. + TK_K)
         const int cnt = W0 + lane < nq ? pc : 0;
         const int ob = pob != 0;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -2393,25 +2208,24 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
             todo &= todo - 1;
             unsigned int key = INV;
             bool fr = false;
-            if (lane < MM_K) {
-                key = sk[i * MM_K + lane];
+            if (lane < TK_K) {
+                key = sk[i * TK_K + lane];
                 const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
                 fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
             }
             const unsigned long long fb = __ballot(fr);
             unsigned int best = fb ? (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1) : INV;
-            if (best == INV && __builtin_amdgcn_readlane(cnt, i) > MM_K) {
+            if (best == INV && __builtin_amdgcn_readlane(cnt, i) > TK_K) {
                 // every listed candidate is blocked and the window holds more: the window again, blocked set applied
                 const size_t o = rowBase + W0 + i;
-                MmWin w;                                                     // the window k_mm_topk swept (its radius from there: no scale table here)
+                Win w;                                                       // the window k_mm_topk swept (its radius from there: no scale table here)
                 w.r = topR[o];
                 mm_levels(R, p, R.octave[o], o, urt != nullptr, w);
-                u64 a[4];
-                mm_qdesc(R, o, a);
-                u64 top[MM_K];
+                u64 a[4], top[TK_K];
+                load_desc(R.qdesc + o * 32, a);
                 int c2;
-                mm_sweep<false>(w, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, R.factor, a, blk, lane, c2, top);
-                best = mm_word(top[0]);
+                win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                best = cand_word(top[0]);
             }
             if (best == INV || (best >> 21) > 100u) continue;                // TH_HIGH (:2589)
             const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
@@ -2431,27 +2245,7 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
-    if (R.check_ori) {
-        // ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment of the other bins is cleared (:2696-2707)
-        int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
-        for (int i = 0; i < 30; ++i) {
-            const int sz = (int)hist[i];
-            if (sz > max1) { max3 = max2; max2 = max1; max1 = sz; i3 = i2; i2 = i1; i1 = i; }
-            else if (sz > max2) { max3 = max2; max2 = sz; i3 = i2; i2 = i; }
-            else if (sz > max3) { max3 = sz; i3 = i; }
-        }
-        if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
-        else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
-        int pruned = 0;
-        for (int e = lane; e < nacc; e += 64) {
-            const unsigned int v = acc[e];
-            const int bin = (int)(v >> 16), k = (int)(v & 0xFFFFu);
-            if (bin != i1 && bin != i2 && bin != i3) { mrow[k] = -2; ++pruned; }      // ORBM_MATCH_PRUNED
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
-        nm -= pruned;
-    }
+    if (R.check_ori) nm -= rot_cull(hist, acc, nacc, mrow, lane);
     if (lane == 0) {
         nmatches[p] = nm;
         if (retried) retried[p] = RETRY ? 1 : 0;
