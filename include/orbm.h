@@ -382,6 +382,41 @@ int orbm_bow_vectors(int n, const int32_t* word_id, const int32_t* node_id, cons
                      int32_t* bow_ids, double* bow_vals, int* nbow,
                      int32_t* fv_nodes, int32_t* fv_start, int32_t* fv_idx, int* nfv);
 
+/* orbm_bow_transform_batch_async: the device form of orbm_bow_transform for nrows descriptor rows (e.g. a whole result block,
+ * [frames][cap] rows; slots beyond a frame's count give values nobody reads).  word_id, node_id, weight [nrows]; word_id and weight
+ * may be NULL, node_id may not.  weight 0 marks a stopped word, which DBoW2 leaves out of the FeatureVector (TemplatedVocabulary.h:1157,
+ * `w > 0`): orbm_search_by_bow_batch_async reads it for that rule.  All pointers are device pointers; enqueue-only (capturable).
+ * ORBM_E_INVALID: a NULL handle, vocabulary, desc or node_id, nrows < 1, a vocabulary of another device. */
+int orbm_bow_transform_batch_async(orbm_t*, const orbm_vocab_t* vocab, const uint8_t* desc, int nrows, int levelsup,
+                                   int32_t* word_id, int32_t* node_id, double* weight);
+/* orbm_search_by_bow_batch_async: M7 SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) -- Tracking::TrackReferenceKeyFrame
+ * (Tracking.cc:3002-3015, nnratio 0.7) and Tracking::Relocalization (Tracking.cc:4175-4215, nnratio 0.75, one call per candidate
+ * KeyFrame) -- END TO END on the device for `npairs` pairs (ORBmatcher.cc:314-547, the Nleft == -1 part; the fisheye / right-camera
+ * branch :406-433, :471-498 stays with orbm_search_by_bow_fisheye).  Two pools of rows: the KeyFrame pool has nkf_rows rows of cap_kf
+ * slots -- kps_kf (mvKeysUn), desc_kf [..][32], counts_kf [nkf_rows], node_kf / weight_kf (orbm_bow_transform_batch_async over the
+ * rows), good_kf (pMP && !pMP->isBad()) --, the frame pool nf_rows rows of cap_f slots with the same arrays but good.  An extractor
+ * result block is one valid pool, a caller-gathered array of KeyFrame rows in the same layout another.  Pair p matches KF row kf_row[p]
+ * against frame row f_row[p] (NULL = row p): P frames against their reference KeyFrames, or one frame against N relocalization
+ * candidates (f_row all equal).  Per pair the FeatureVector buckets are the features of one node id in ascending index, without the
+ * stopped words (weight <= 0; NULL weight = none), without KF features whose good_kf is 0 and without slots >= count.  Per KF feature
+ * in bucket order: the first minimum over the bucket's unmatched frame features, bestDist1 <= TH_LOW and bestDist1 < nnratio *
+ * bestDist2 (the if / else-if runner-up) claim the frame feature; check_orientation applies the 30-bin rotation histogram (rot =
+ * angle_kf - angle_f) and its three-maxima cull.  Outputs (device): f_match [npairs][cap_f] = KF feature index or -1 (culled matches
+ * -1 too: the row orbm_search_by_bow returns, padded with -1 to cap_f), nmatches [npairs] = its return value.  A pair whose kf_row or
+ * f_row lies outside [0, nkf_rows) / [0, nf_rows) gets an all -1 row and 0.  The TrackReferenceKeyFrame / Relocalization tests on
+ * nmatches (< 15) stay with the caller.  All pointers are device pointers; enqueue-only, no scratch: every call can be captured
+ * (orbx_capture_begin) once one eager call with the same or a larger cap_kf / cap_f has run.  ORBM_E_INVALID: a NULL required array,
+ * npairs, nkf_rows, nf_rows, cap_kf or cap_f < 1, nnratio not finite; ORBM_E_CAPACITY: cap_kf or cap_f > ORBM_BOW_MAX_CAP (the bucket
+ * lists and the pair's row live in LDS), npairs > 65535.  Nothing is enqueued then. */
+enum { ORBM_BOW_MAX_CAP = 24576 };
+int orbm_search_by_bow_batch_async(orbm_t*, int npairs,
+                                   int nkf_rows, int cap_kf, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                   const int32_t* node_kf, const double* weight_kf, const uint8_t* good_kf,
+                                   int nf_rows, int cap_f, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                   const int32_t* node_f, const double* weight_f,
+                                   const int32_t* kf_row, const int32_t* f_row, float nnratio, int check_orientation,
+                                   int32_t* f_match, int32_t* nmatches);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -1873,6 +1873,54 @@ int orbm_bow_nodes_batch_async(orbm_t* m, const orbm_vocab_t* v, const uint8_t* 
     return ORBM_OK;
 }
 
+int orbm_bow_transform_batch_async(orbm_t* m, const orbm_vocab_t* v, const uint8_t* desc, int nrows, int levelsup,
+                                   int32_t* word_id, int32_t* node_id, double* weight) {
+    if (!m || !v || !desc || !node_id || nrows < 1) { set_merr("bow transform batch: a required array is NULL or nrows < 1"); return ORBM_E_INVALID; }
+    if (v->device != m->device) { set_merr("vocabulary lives on another device"); return ORBM_E_INVALID; }
+    MHIPCHK(hipSetDevice(m->device));
+    hipLaunchKernelGGL(k_bow_transform2, dim3((unsigned)(((size_t)nrows * 16 + 255) / 256)), dim3(256), 0, m->stream, desc, nrows, v->dInfo, v->dDesc, v->dOrig,
+                       v->dWord, v->dWeight, v->L, levelsup, word_id, node_id, weight);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_search_by_bow_batch_async(orbm_t* m, int npairs,
+                                   int nkf_rows, int cap_kf, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                   const int32_t* node_kf, const double* weight_kf, const uint8_t* good_kf,
+                                   int nf_rows, int cap_f, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                   const int32_t* node_f, const double* weight_f,
+                                   const int32_t* kf_row, const int32_t* f_row, float nnratio, int check_orientation,
+                                   int32_t* f_match, int32_t* nmatches) {
+    if (!m || !kps_kf || !desc_kf || !counts_kf || !node_kf || !good_kf || !kps_f || !desc_f || !counts_f || !node_f || !f_match || !nmatches) {
+        set_merr("SearchByBoW batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nkf_rows < 1 || nf_rows < 1 || cap_kf < 1 || cap_f < 1 || !std::isfinite(nnratio)) {
+        set_merr("SearchByBoW batch: npairs, nkf_rows, nf_rows, cap_kf and cap_f must be >= 1 and nnratio finite");
+        return ORBM_E_INVALID;
+    }
+    if (cap_kf > ORBM_BOW_MAX_CAP || cap_f > ORBM_BOW_MAX_CAP) {
+        set_merr("SearchByBoW batch: cap_kf %d / cap_f %d above %d (the bucket lists and the row live in LDS)", cap_kf, cap_f, (int)ORBM_BOW_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (npairs > 65535) { set_merr("SearchByBoW batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t lds = bow_search_lds(cap_kf, cap_f);
+    // above 48 KB the launch needs the attribute on the current device; always the largest legal size, so that a graph captured
+    // earlier with bigger rows still launches after a call with smaller ones
+    if (lds > 48 * 1024)
+        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bow_search_lds(ORBM_BOW_MAX_CAP, ORBM_BOW_MAX_CAP)));
+    BowSide K{(const KpIn*)kps_kf, desc_kf, counts_kf, node_kf, weight_kf, good_kf, nkf_rows, cap_kf};
+    BowSide F{(const KpIn*)kps_f, desc_f, counts_f, node_f, weight_f, nullptr, nf_rows, cap_f};
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_bow_search, dim3(npairs), dim3(BOW_WAVES * 64), lds, m->stream, npairs, K, F, kf_row, f_row, nnratio,
+                       check_orientation, f_match, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 int orbm_triangulation_batch_async(orbm_t* m, int npairs, int cap,
                                    const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1, const int32_t* node1, const float* uright1,
                                    const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2, const int32_t* node2, const float* uright2,

@@ -1261,9 +1261,9 @@ __device__ __forceinline__ unsigned int bits_word(const uint8_t* __restrict__ sr
     return bits;
 }
 
-// ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the bin counts, then every assignment acc[0..nacc) (slot | bin << 16) of another bin
-// is cleared (:2696-2707) as ORBM_MATCH_PRUNED.  Returns the number of pruned entries (wave-uniform).
-__device__ __forceinline__ int rot_cull(const unsigned int* hist, const unsigned int* acc, int nacc, int* mrow, int lane) {
+// ComputeThreeMaxima (ORBmatcher.cc:2870-2909) on the 30 bin counts: the kept bins, -1 where the 0.1 rule drops one
+struct Max3 { int i1, i2, i3; };
+__device__ __forceinline__ Max3 three_maxima(const unsigned int* hist) {
     int max1 = 0, max2 = 0, max3 = 0, i1 = -1, i2 = -1, i3 = -1;
     for (int i = 0; i < 30; ++i) {
         const int sz = (int)hist[i];
@@ -1273,6 +1273,14 @@ __device__ __forceinline__ int rot_cull(const unsigned int* hist, const unsigned
     }
     if ((float)max2 < 0.1f * (float)max1) { i2 = -1; i3 = -1; }
     else if ((float)max3 < 0.1f * (float)max1) i3 = -1;
+    return Max3{i1, i2, i3};
+}
+
+// three_maxima on the bin counts, then every assignment acc[0..nacc) (slot | bin << 16) of another bin is cleared (:2696-2707) as
+// ORBM_MATCH_PRUNED.  Returns the number of pruned entries (wave-uniform).
+__device__ __forceinline__ int rot_cull(const unsigned int* hist, const unsigned int* acc, int nacc, int* mrow, int lane) {
+    const Max3 m3 = three_maxima(hist);
+    const int i1 = m3.i1, i2 = m3.i2, i3 = m3.i3;
     int pruned = 0;
     for (int e = lane; e < nacc; e += 64) {
         const unsigned int v = acc[e];
@@ -2349,6 +2357,201 @@ __global__ __launch_bounds__(256) void k_bow_transform2(const uint8_t* __restric
         if (weight) weight[i] = nweight[cur];
         node_id[i] = nid ? orig[nid] : 0;
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_bow_search: M7 ORBmatcher::SearchByBoW(KeyFrame*, Frame&) (ORBmatcher.cc:314-547, Nleft == -1) for a batch of (KF row, frame row)
+// pairs, one workgroup of BOW_WAVES waves per pair, everything in LDS.
+// 1. Both rows are bucketed by (node & 255) with a STABLE counting sort (bow_buckets): each wave owns a contiguous run of indices,
+//    per-wave histograms give every (bucket, wave) its first slot, and inside a 64-chunk a lane's rank among the lanes of its bucket
+//    comes from eight ballots (v_mbcnt).  Each list is in ascending feature index, as a FeatureVector bucket is walked.  Stopped words
+//    (weight <= 0), KF features without a good MapPoint and slots >= count are left out here.
+// 2. Claims: wave w takes the hash buckets w, w + BOW_WAVES, ...  Features of different nodes never meet, so a hash list that holds
+//    several nodes is still walked correctly in index order, and hash buckets are independent.  Per KF feature (in order) the lanes
+//    take the frame list in passes of 64 (the first 64 stay in registers for the whole bucket), key = dist << 16 | list position for
+//    an unmatched frame feature of the same node; the wave minimum is bestDist1 (first minimum in frame index order) and the minimum
+//    of the other keys is the if / else-if chain's bestDist2.  An accepted claim writes KF index + 1 into the pair's LDS row.
+// 3. check_orientation: the 30-bin histogram is rebuilt from the finished row (rot = angle_kf - angle_f, :451-459; a bin outside
+//    [0, 30) is neither counted nor culled, as the host RotHist), three_maxima, and the matches of the other bins are cleared (-1).
+// LDS: cur [BOW_WAVES][256] + kstart [257] + fstart [257] + hist [32] + red [8] ints, klist [cap_kf] + flist [cap_f] + row [cap_f]
+// ushorts (bow_search_lds).
+// ------------------------------------------------------------------------------------------------
+#define BOW_WAVES 8
+struct BowSide {                                           // one pool: rows of cap slots
+    const KpIn* kps; const uint8_t* desc; const int* counts; const int* node; const double* weight; const uint8_t* good;
+    int nrows, cap;
+};
+__host__ __device__ inline size_t bow_search_lds(int cap_kf, int cap_f) {
+    return (size_t)(BOW_WAVES * 256 + 2 * 257 + 32 + 8) * sizeof(int) + (size_t)(cap_kf + 2 * cap_f) * sizeof(unsigned short);
+}
+
+__device__ __forceinline__ unsigned bow_rank(u64 m) {                       // set bits of m below this lane
+    return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+}
+__device__ __forceinline__ u64 readlane64(u64 v, int l) {
+    return (u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l) | ((u64)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l) << 32);
+}
+__device__ __forceinline__ bool bow_live(const BowSide& s, size_t o, int i, int n) {
+    return i < n && (!s.weight || s.weight[o + i] > 0) && (!s.good || s.good[o + i]);
+}
+
+// the stable (node & 255) buckets of row `o` of side s: start [257], list [n live entries] (whole workgroup)
+__device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* start, int* red, unsigned short* list) {
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    for (int e = tid; e < BOW_WAVES * 256; e += BOW_WAVES * 64) cur[e] = 0;
+    __syncthreads();
+    const int per = ((n + BOW_WAVES * 64 - 1) / (BOW_WAVES * 64)) * 64;     // whole 64-chunks per wave, in index order
+    const int lo = min(w * per, n), hi = min(lo + per, n);
+    for (int i0 = lo; i0 < hi; i0 += 64) {
+        const int i = i0 + lane;
+        if (i < hi && bow_live(s, o, i, n)) atomicAdd(&cur[w * 256 + (s.node[o + i] & 255)], 1);
+    }
+    __syncthreads();
+    int c[BOW_WAVES], tot = 0, ex = 0;
+    if (tid < 256) {                                                         // bucket h = tid: (h, wave) order
+#pragma unroll
+        for (int v = 0; v < BOW_WAVES; ++v) { c[v] = cur[v * 256 + tid]; tot += c[v]; }
+        int wt;
+        ex = wave_excl_scan(tot, &wt);
+        if (lane == 0) red[w] = wt;
+    }
+    __syncthreads();
+    if (tid < 256) {
+        int base = ex;
+        for (int v = 0; v < w; ++v) base += red[v];
+        start[tid] = base;
+        if (tid == 255) start[256] = base + tot;
+#pragma unroll
+        for (int v = 0; v < BOW_WAVES; ++v) { cur[v * 256 + tid] = base; base += c[v]; }
+    }
+    __syncthreads();
+    for (int i0 = lo; i0 < hi; i0 += 64) {
+        const int i = i0 + lane;
+        const bool ok = i < hi && bow_live(s, o, i, n);
+        const int h = ok ? (s.node[o + i] & 255) : 0;
+        u64 eq = __ballot(ok);
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const u64 bb = __ballot((h >> b) & 1);
+            eq &= ((h >> b) & 1) ? bb : ~bb;
+        }
+        if (ok) {
+            const unsigned r = bow_rank(eq), nb = (unsigned)__popcll(eq);
+            list[cur[w * 256 + h] + r] = (unsigned short)i;
+            if (r == nb - 1) cur[w * 256 + h] += nb;                        // the bucket's last lane moves the cursor
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSide K, BowSide F, const int* __restrict__ kf_row,
+                                                               const int* __restrict__ f_row, float nnratio, int check_ori,
+                                                               int* __restrict__ f_match, int* __restrict__ nmatches) {
+    extern __shared__ int bow_lds[];
+    int* cur = bow_lds;
+    int* kstart = cur + BOW_WAVES * 256;
+    int* fstart = kstart + 257;
+    unsigned int* hist = (unsigned int*)(fstart + 257);
+    int* red = (int*)(hist + 32);
+    unsigned short* klist = (unsigned short*)(red + 8);
+    unsigned short* flist = klist + K.cap;
+    unsigned short* row = flist + F.cap;
+    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    int* out = f_match + (size_t)p * F.cap;
+    const int kr = kf_row ? kf_row[p] : p, fr = f_row ? f_row[p] : p;
+    if (kr < 0 || kr >= K.nrows || fr < 0 || fr >= F.nrows) {              // (block-uniform) an empty row
+        for (int j = tid; j < F.cap; j += BOW_WAVES * 64) out[j] = -1;
+        if (tid == 0) nmatches[p] = 0;
+        return;
+    }
+    const size_t ko = (size_t)kr * K.cap, fo = (size_t)fr * F.cap;
+    const int nk = min(max(K.counts[kr], 0), K.cap), nf = min(max(F.counts[fr], 0), F.cap);
+    for (int j = tid; j < F.cap; j += BOW_WAVES * 64) row[j] = 0;
+    bow_buckets(K, ko, nk, cur, kstart, red, klist);
+    bow_buckets(F, fo, nf, cur, fstart, red, flist);
+    const unsigned INV = 0xFFFFFFFFu;
+    for (int h = w; h < 256; h += BOW_WAVES) {
+        const int ks = kstart[h], ke = kstart[h + 1], fs = fstart[h], fe = fstart[h + 1];
+        if (ks == ke || fs == fe) continue;
+        int fj0 = -1, fn0 = 0;                                               // the first 64 frame candidates, for the whole bucket
+        u64 fd0[4] = {0, 0, 0, 0};
+        if (fs + lane < fe) { fj0 = flist[fs + lane]; fn0 = F.node[fo + fj0]; load_desc(F.desc + (fo + fj0) * 32, fd0); }
+        for (int kb = ks; kb < ke; kb += 64) {
+            int ki = -1, kn = 0;
+            u64 kd[4] = {0, 0, 0, 0};
+            if (kb + lane < ke) { ki = klist[kb + lane]; kn = K.node[ko + ki]; load_desc(K.desc + (ko + ki) * 32, kd); }
+            const int kcnt = min(64, ke - kb);
+            for (int t = 0; t < kcnt; ++t) {
+                const int i = __builtin_amdgcn_readlane(ki, t), nd = __builtin_amdgcn_readlane(kn, t);
+                u64 a[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a[q] = readlane64(kd[q], t);
+                unsigned b1 = INV, b2 = INV;                                 // the lane's two smallest keys
+                if (fj0 >= 0 && fn0 == nd && row[fj0] == 0) b1 = ((unsigned)ham256(a, fd0[0], fd0[1], fd0[2], fd0[3]) << 16) | (unsigned)lane;
+                for (int fb = fs + 64; fb < fe; fb += 64) {                  // buckets longer than 64
+                    const int pos = fb + lane;
+                    if (pos < fe) {
+                        const int j = flist[pos];
+                        if (F.node[fo + j] == nd && row[j] == 0) {
+                            u64 d4[4];
+                            load_desc(F.desc + (fo + j) * 32, d4);
+                            const unsigned key = ((unsigned)ham256(a, d4[0], d4[1], d4[2], d4[3]) << 16) | (unsigned)(pos - fs);
+                            if (key < b1) { b2 = b1; b1 = key; }
+                            else if (key < b2) b2 = key;
+                        }
+                    }
+                }
+                const unsigned m1 = wave_min_u32(b1);
+                if (m1 == INV) continue;
+                const unsigned m2 = wave_min_u32(b1 == m1 ? b2 : b1);       // the winner's lane offers its runner-up
+                const int d1 = (int)(m1 >> 16), d2 = m2 == INV ? 256 : (int)(m2 >> 16);
+                if (d1 <= 50 && (float)d1 < nnratio * (float)d2) {           // TH_LOW, :436-442
+                    if (lane == 0) row[flist[fs + (m1 & 0xFFFFu)]] = (unsigned short)(i + 1);
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const float factor = 30 / 360.0f;                                        // HISTO_LENGTH / 360.0f, :334
+    auto bin_of = [&](int j, int v) {
+        float rot = K.kps[ko + v - 1].angle - F.kps[fo + j].angle;
+        if (rot < 0.0f) rot += 360.0f;
+        int bin = (int)roundf(rot * factor);
+        if (bin == 30) bin = 0;
+        return bin;
+    };
+    if (check_ori) {
+        if (tid < 32) hist[tid] = 0;
+        __syncthreads();
+        for (int j = tid; j < nf; j += BOW_WAVES * 64) {
+            const int v = row[j];
+            if (v) { const int bin = bin_of(j, v); if (bin >= 0 && bin < 30) atomicAdd(&hist[bin], 1u); }
+        }
+        __syncthreads();
+        const Max3 m3 = three_maxima(hist);
+        const int i1 = m3.i1, i2 = m3.i2, i3 = m3.i3;
+        for (int j = tid; j < nf; j += BOW_WAVES * 64) {
+            const int v = row[j];
+            if (v) { const int bin = bin_of(j, v); if (bin >= 0 && bin < 30 && bin != i1 && bin != i2 && bin != i3) row[j] = 0; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) red[0] = 0;
+    __syncthreads();
+    int nm = 0;
+    for (int j0 = w * 64; j0 < F.cap; j0 += BOW_WAVES * 64) {
+        const int j = j0 + lane;
+        const int v = j < F.cap ? (int)row[j] : 0;
+        if (j < F.cap) out[j] = v - 1;
+        nm += __popcll(__ballot(v != 0));
+    }
+    if (lane == 0 && nm) atomicAdd(&red[0], nm);
+    __syncthreads();
+    if (tid == 0) nmatches[p] = red[0];
 }
 
 // ------------------------------------------------------------------------------------------------
