@@ -341,6 +341,41 @@ int orbm_search_by_projection_frame_batch_async(orbm_t*, const orbm_kp_t* kps, c
 int orbm_project_last_frame_batch_async(orbm_t*, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
                                         const float* x3dw, const uint8_t* has_mp, const float* k_host, const float* bounds_host, float mb, int mono,
                                         uint8_t* valid, float* u, float* v, float* invzc, uint8_t* dir);
+/* orbm_fuse_batch_async: M13 Fuse(pKF, vpMapPoints, th) -- LocalMapping::SearchInNeighbors (LocalMapping.cc:925-1070) -- and its Sim3 twin
+ * Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) -- LoopClosing::SearchAndFuse -- search core END TO END on the device for `npairs` (KeyFrame
+ * row, query row) pairs (ORBmatcher.cc:1823-2049 with chi2_gate = 1, :2051-2199 with chi2_gate = 0), pinhole camera, Nleft == -1; the
+ * bRight / fisheye call stays with orbm_fuse.  The KeyFrame pool has nkf_rows rows of cap slots: kps_kf (mvKeysUn), desc_kf [..][32],
+ * uright_kf (mvuRight; NULL = every slot < 0) and the grid of orbm_grid_build_batch_async over the pool, indexed by row -- the grid is how
+ * the search reaches a slot.  An extractor result block is one valid pool, a caller-gathered array of KeyFrame rows another.  Pair p reads
+ * KF row kf_row[p] (NULL = row p); tcw [npairs][12] is its row-major 3x4 [Rcw | tcw] and ow [npairs][3] its camera centre: GetRotation /
+ * GetTranslation / GetCameraCenter for chi2_gate = 1, or Rcw = sRcw / scw, tcw / scw and Ow = -Rcw^T tcw as the caller computes them for
+ * the Sim3 variant.  The queries are MapPoints: nq [npairs] of them per pair; valid [npairs][q_stride] holds the caller-side tests (pMP &&
+ * !isBad(), plus !IsInKeyFrame(pKF) or !spAlreadyFound.count(pMP)); pw [..][3] (GetWorldPos), normal [..][3] (GetNormal), min_dist /
+ * max_dist (mfMinDistance / mfMaxDistance) and qdesc [..][32] are rows of q_stride entries per pair, or ONE row shared by every pair when
+ * q_shared != 0.  A query that is not valid reads nothing else.  Numerics are those of the facade's Fuse lines against cvcompat.h: x3Dc =
+ * (float)(double sum of R * X) + t, z < 0 rejects, invz = 1 / z, u = fx * x / z + cx in float without contraction, IsInImage (u >= minX
+ * && u < maxX && v >= minY && v < maxY; k_host = (fx, fy, cx, cy), bounds_host = (minX, maxX, minY, maxY)), ur = u - bf * invz, dist3D =
+ * (float)sqrt(double sum of PO^2) within [0.8f * min_dist, 1.2f * max_dist], PO . normal (double) >= 0.5 * dist3D, PredictScale as
+ * orbm_is_in_frustum computes it (log_scale_factor, nlevels); a point with z == 0 exactly is outside the contract.  The window is
+ * KeyFrame::GetFeaturesInArea(u, v, th * scale[level]) without a stereo gate; candidates of levels [level-1, level]; chi2_gate adds the
+ * test e2 * inv_sigma2[octave] > 7.8 (with er = ur - uright[k] where uright[k] >= 0) or > 5.99 (two terms); the first minimum in visiting
+ * order is accepted at bestDist <= TH_LOW.  Outputs (device): best_idx [npairs][q_stride] = KF slot or -1 (the row orbm_fuse returns,
+ * padded with -1 to q_stride), nfused [npairs] = its return value, level_out [npairs][q_stride] (NULL = not written) = the predicted
+ * level of a query that passed every geometric gate, else -1.  A pair whose kf_row lies outside [0, nkf_rows) gets an all -1 row and 0.
+ * AddObservation / Replace stay with the caller (the cross-KeyFrame rule).  All pointers are device pointers except
+ * the *_host tables; enqueue-only, no scratch: every call can be captured (orbx_capture_begin) after one eager call.  ORBM_E_INVALID: a
+ * NULL required array (inv_sigma2_host only with chi2_gate), npairs, nkf_rows, cap, q_stride or nlevels < 1, th not finite;
+ * ORBM_E_CAPACITY: cap > 65535, q_stride > ORBM_LP_MAX_QUERIES, nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_fuse_batch_async(orbm_t*, int npairs,
+                          int nkf_rows, int cap, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const float* uright_kf,
+                          const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                          const int32_t* kf_row, const float* tcw, const float* ow,
+                          const int32_t* nq, int q_stride, const uint8_t* valid,
+                          const float* pw, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* qdesc, int q_shared,
+                          const float* k_host, const float* bounds_host, float bf,
+                          float th, int chi2_gate, const float* scale_factors_host, const float* inv_sigma2_host,
+                          float log_scale_factor, int nlevels,
+                          int32_t* best_idx, int32_t* nfused, int32_t* level_out);
 
 /* ---- batched, DEVICE-resident stereo step (config C3: EuRoC stereo).  All pointers are device pointers; enqueue only.
  * orbm_stereo_batch_async: M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276) for `npairs` stereo pairs of ONE extractor

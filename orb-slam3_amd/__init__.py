@@ -832,6 +832,11 @@ def _install_search():
                                                               vp, vp, vp, vp, vp, vp, vp, vp,                  # valid, u, v, invzc, octave, angle, qdesc, mp_obs
                                                               cf, ci, vp, ci, ci, vp, vp, vp]                  # th, retry_below, sf, nlevels, check_ori, outputs
     L.orbm_project_last_frame_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp]
+    L.orbm_fuse_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,                 # pairs, KF pool (kps, desc, uright)
+                                        vp, vp, cf, cf, cf, cf, vp, vp, vp,         # grid, bounds, kf_row, tcw, ow
+                                        vp, ci, vp, vp, vp, vp, vp, vp, ci,         # nq, q_stride, valid, pw, normal, min/max dist, qdesc, q_shared
+                                        vp, vp, cf, cf, ci, vp, vp, cf, ci,         # k, bounds, bf, th, chi2_gate, sf, inv_sigma2, log sf, nlevels
+                                        vp, vp, vp]                                 # best_idx, nfused, level_out
     L.orbm_bow_transform_batch_async.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
     L.orbm_search_by_bow_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, KF pool
                                                  ci, ci, vp, vp, vp, vp, vp,               # frame pool
@@ -912,7 +917,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_sim3", "orbm_fuse", "orbm_search_by_sim3",
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
-            "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async",
+            "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
             "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]

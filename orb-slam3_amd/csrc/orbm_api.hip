@@ -1321,6 +1321,48 @@ int orbm_project_last_frame_batch_async(orbm_t* m, int npairs, const float* tcw_
     return ORBM_OK;
 }
 
+int orbm_fuse_batch_async(orbm_t* m, int npairs,
+                          int nkf_rows, int cap, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const float* uright_kf,
+                          const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                          const int32_t* kf_row, const float* tcw, const float* ow,
+                          const int32_t* nq, int q_stride, const uint8_t* valid,
+                          const float* pw, const float* normal, const float* min_dist, const float* max_dist, const uint8_t* qdesc, int q_shared,
+                          const float* k_host, const float* bounds_host, float bf,
+                          float th, int chi2_gate, const float* scale_factors_host, const float* inv_sigma2_host,
+                          float log_scale_factor, int nlevels,
+                          int32_t* best_idx, int32_t* nfused, int32_t* level_out) {
+    if (!m || !kps_kf || !desc_kf || !grid_start || !grid_idx || !tcw || !ow || !nq || !valid || !pw || !normal || !min_dist || !max_dist ||
+        !qdesc || !k_host || !bounds_host || !scale_factors_host || (chi2_gate && !inv_sigma2_host) || !best_idx || !nfused) {
+        set_merr("Fuse batch: a required array is NULL (inv_sigma2 is required with chi2_gate)");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nkf_rows < 1 || cap < 1 || q_stride < 1 || nlevels < 1 || !std::isfinite(th)) {
+        set_merr("Fuse batch: npairs, nkf_rows, cap, q_stride and nlevels must be >= 1, th finite");
+        return ORBM_E_INVALID;
+    }
+    if (const int rc = lp_capacity("Fuse batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    FuseRows R;
+    R.nq = nq; R.valid = valid; R.pw = pw; R.normal = normal; R.min_dist = min_dist; R.max_dist = max_dist; R.qdesc = qdesc;
+    FuseParams P;
+    for (int i = 0; i < 4; ++i) { P.k[i] = k_host[i]; P.bounds[i] = bounds_host[i]; }
+    P.bf = bf; P.th = th; P.logSF = log_scale_factor;
+    P.nlevels = nlevels; P.q_stride = q_stride; P.q_shared = q_shared != 0; P.chi2 = chi2_gate != 0; P.nkf_rows = nkf_rows;
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    for (int i = 0; i < 12; ++i) {
+        P.sf[i] = st.sf[i];
+        P.isg[i] = chi2_gate ? inv_sigma2_host[std::min(i, nlevels - 1)] : 0.f;
+    }
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_fuse_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, uright_kf,
+                       grid_start, grid_idx, min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, best_idx, level_out);
+    hipLaunchKernelGGL(k_fuse_count, dim3(npairs), dim3(256), 0, m->stream, best_idx, q_stride, nfused);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 // ---- DBoW2 vocabulary ----
 struct orbm_vocab {
     int k = 0, L = 0, nnodes = 0, nwords = 0, device = 0;

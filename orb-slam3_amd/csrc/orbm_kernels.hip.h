@@ -1166,11 +1166,16 @@ struct RotBinPay {
 // key = dist << 40 | j << 21 | payload << 16 | keypoint (j, keypoint < 65536).
 // TOPK: cnt = window population, top[0..TK_K) = its TK_K smallest keys (wave-uniform).
 // !TOPK: only candidates not blocked in blk; top[0], top[1] = the two smallest.
-template <bool TOPK, class Pay>
+// Gate: a further candidate test after the window, level and stereo tests (Fuse's chi2 test, FuseGate); NoGate compiles to nothing.
+struct NoGate {
+    static constexpr bool on = false;
+    __device__ bool operator()(const KpIn&, int) const { return true; }
+};
+template <bool TOPK, class Pay, class Gate = NoGate>
 __device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt,
                                           const float* __restrict__ urt, const int* __restrict__ gs, const int* __restrict__ gi,
                                           float min_x, float min_y, float inv_w, float inv_h, const u64 (&a)[4], const unsigned int* blk,
-                                          int lane, int& cnt, u64 (&top)[TK_K]) {
+                                          int lane, int& cnt, u64 (&top)[TK_K], const Gate& gate = Gate{}) {
     const u64 INV = ~0ull;
 #pragma unroll
     for (int i = 0; i < TK_K; ++i) top[i] = INV;
@@ -1210,6 +1215,7 @@ __device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const Kp
                 const float urk = urt[k];
                 if (urk > 0 && fabsf(w.ur - urk) > w.r) ok = false;            // ORBmatcher.cc:107-117, :2569-2576
             }
+            if (Gate::on && ok && !gate(kp, k)) ok = false;
             if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
             if (ok) {
                 const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
@@ -2305,6 +2311,120 @@ __global__ __launch_bounds__(256) void k_mm_project(const float* __restrict__ tc
         }
     }
     valid[o] = ok; u[o] = pu; v[o] = pv; invzc[o] = iz;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Batched Fuse -- M13, the search core of ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:1823-2049, chi2 = 1) and of its Sim3
+// twin (:2051-2199, chi2 = 0) -- for (KeyFrame row, query row) pairs, pinhole, Nleft == -1.  No claims: a MapPoint's best slot depends on
+// no other MapPoint, so every (pair, query) is independent.
+// k_fuse_topk: a wave per (pair, query), as k_lp_topk.  The projection and the gates run wave-uniformly in the facade's numerics against
+//   cvcompat.h (fuse_project); the window KeyFrame::GetFeaturesInArea (KeyFrame.cc:916-962: no level or stereo gate) is one win_sweep
+//   with the level band [level-1, level] (:1959) and FuseGate.  The smallest key is the `dist < bestDist` first minimum in visiting order.
+// k_fuse_count: one block per pair counts the row's fused entries (deterministic, nothing to zero before a replay).
+// ------------------------------------------------------------------------------------------------
+struct FuseRows {                                          // the per-query arrays of one call, [npairs][q_stride] unless q_shared
+    const int* nq; const uint8_t* valid;
+    const float* pw; const float* normal; const float* min_dist; const float* max_dist; const uint8_t* qdesc;
+};
+struct FuseParams { float k[4], bounds[4], bf, th, logSF; int nlevels, q_stride, q_shared, chi2, nkf_rows; float sf[12], isg[12]; };
+
+// Fuse's candidate test (ORBmatcher.cc:1963-1992): the reprojection error against the keypoint's level sigma, with the right-image term
+// where the slot has an mvuRight >= 0 (urt NULL: none has).  Float expressions in the reference's order, compared with the double literal.
+struct FuseGate {
+    static constexpr bool on = true;
+    float u, v, ur;
+    const float* __restrict__ urt;
+    const float* isg;
+    bool chi2;                                                               // 0: the Sim3 variant, no test
+    __device__ bool operator()(const KpIn& kp, int k) const {
+        if (!chi2) return true;
+        const float ex = u - kp.x, ey = v - kp.y;
+        if (urt && urt[k] >= 0) {
+            const float er = ur - urt[k];
+            const float e2 = ex * ex + ey * ey + er * er;
+            return !(e2 * isg[kp.octave] > 7.8);
+        }
+        const float e2 = ex * ex + ey * ey;
+        return !(e2 * isg[kp.octave] > 5.99);
+    }
+};
+
+// The projection and geometric gates of Fuse (ORBmatcher.cc:1878-1930 as facade/ORBmatcher.h evaluates them against cvcompat.h): x3Dc
+// through mm_dot3 + t, z < 0 rejects, invz = 1 / z, pinhole u = fx * x / z + cx, KeyFrame::IsInImage (half-open, KeyFrame.cc:965-968),
+// ur = u - bf * invz, dist3D the float of a double norm against [0.8 min, 1.2 max], PO . Pn (double) >= 0.5 dist3D, then PredictScale as
+// k_frustum computes it.  Returns the predicted level, or -1.
+__device__ __forceinline__ int fuse_project(const float* T, const float* O, const float* X, const float* N, float minDist, float maxDist,
+                                            const FuseParams& P, float& u, float& v, float& ur) {
+    const float x0 = X[0], x1 = X[1], x2 = X[2];
+    const float xc = mm_dot3(T[0], T[1], T[2], x0, x1, x2) + T[3];
+    const float yc = mm_dot3(T[4], T[5], T[6], x0, x1, x2) + T[7];
+    const float zc = mm_dot3(T[8], T[9], T[10], x0, x1, x2) + T[11];
+    if (zc < 0.0f) return -1;
+    const float invz = 1.0f / zc;
+    u = P.k[0] * xc / zc + P.k[2];
+    v = P.k[1] * yc / zc + P.k[3];
+    if (!(u >= P.bounds[0] && u < P.bounds[1] && v >= P.bounds[2] && v < P.bounds[3])) return -1;
+    ur = u - P.bf * invz;
+    const float maxD = 1.2f * maxDist, minD = 0.8f * minDist;
+    const float o0 = x0 - O[0], o1 = x1 - O[1], o2 = x2 - O[2];
+    double d2 = 0.0;
+    d2 += (double)o0 * (double)o0; d2 += (double)o1 * (double)o1; d2 += (double)o2 * (double)o2;
+    const float dist = (float)sqrt(d2);
+    if (dist < minD || dist > maxD) return -1;
+    double dot = 0.0;
+    dot += (double)o0 * (double)N[0]; dot += (double)o1 * (double)N[1]; dot += (double)o2 * (double)N[2];
+    if (dot < 0.5 * (double)dist) return -1;
+    const float ratio = maxDist / dist;
+    const float lg = (float)log((double)ratio);
+    int ns = (int)ceilf(lg / P.logSF);
+    if (ns < 0) ns = 0; else if (ns >= P.nlevels) ns = P.nlevels - 1;
+    return ns;
+}
+
+__global__ __launch_bounds__(256) void k_fuse_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
+                                                   const float* __restrict__ uright, const int* __restrict__ grid_start,
+                                                   const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                                   const int* __restrict__ kf_row, const float* __restrict__ tcw, const float* __restrict__ ow,
+                                                   FuseRows R, FuseParams P, int* __restrict__ best_idx, int* __restrict__ level_out) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.y;
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (q >= P.q_stride) return;
+    const size_t o = (size_t)p * P.q_stride + q;
+    const int row = kf_row ? kf_row[p] : p;
+    const int nq = min(max(R.nq[p], 0), P.q_stride);
+    int lvl = -1, best = -1;
+    float u = 0.f, v = 0.f, ur = 0.f;
+    const size_t qo = P.q_shared ? (size_t)q : o;
+    if (row >= 0 && row < P.nkf_rows && q < nq && R.valid[o])
+        lvl = fuse_project(tcw + (size_t)p * 12, ow + (size_t)p * 3, R.pw + qo * 3, R.normal + qo * 3, R.min_dist[qo], R.max_dist[qo], P, u, v, ur);
+    if (lvl >= 0) {
+        u64 a[4];
+        load_desc(R.qdesc + qo * 32, a);
+        const Win w = {u, v, P.th * P.sf[lvl], 0.f, lvl - 1, lvl};               // radius = th * mvScaleFactors[nPredictedLevel]
+        const FuseGate g = {u, v, ur, uright ? uright + (size_t)row * cap : nullptr, P.isg, P.chi2 != 0};
+        int cnt;
+        u64 top[TK_K];
+        win_sweep<true>(w, OctavePay{}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr, grid_start + (size_t)row * (64 * 48 + 1),
+                        grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top, g);
+        if (top[0] != ~0ull && (int)(top[0] >> 40) <= 50) best = (int)(top[0] & 0xFFFFu);   // bestDist <= TH_LOW
+    }
+    if (lane == 0) {
+        best_idx[o] = best;
+        if (level_out) level_out[o] = lvl;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fuse_count(const int* __restrict__ best_idx, int q_stride, int* __restrict__ nfused) {
+    __shared__ int part[4];
+    const int p = blockIdx.x;
+    int c = 0;
+    for (int i = threadIdx.x; i < q_stride; i += 256) c += best_idx[(size_t)p * q_stride + i] >= 0;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_xor(c, off);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) nfused[p] = part[0] + part[1] + part[2] + part[3];
 }
 
 // ------------------------------------------------------------------------------------------------
