@@ -376,6 +376,40 @@ int orbm_fuse_batch_async(orbm_t*, int npairs,
                           float th, int chi2_gate, const float* scale_factors_host, const float* inv_sigma2_host,
                           float log_scale_factor, int nlevels,
                           int32_t* best_idx, int32_t* nfused, int32_t* level_out);
+/* orbm_search_by_projection_kf_batch_async: M5 SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) -- the two guided
+ * searches of Tracking::Relocalization (Tracking.cc:4309 with th 10 / ORBdist 100, :4334 with th 3 / ORBdist 64) -- END TO END on the
+ * device for `npairs` (frame row, candidate KeyFrame, pose) triples (ORBmatcher.cc:2723-2852), pinhole camera, Nleft == -1; the fisheye
+ * call stays with orbm_search_by_projection_kf.  The frame pool has nf_rows rows of cap slots: kps_f (mvKeysUn), desc_f [..][32],
+ * counts_f and the grid of orbm_grid_build_batch_async over the pool, indexed by row.  Pair p searches row f_row[p] (NULL = row p): one
+ * frame against N relocalisation candidates repeats the row.  f_blocked [npairs][cap] = CurrentFrame.mvpMapPoints[i2] != NULL in this
+ * candidate's state (NULL = none blocked); tcw [npairs][12] is the candidate's pose (mCurrentFrame.mTcw after PnP / PoseOptimization)
+ * as a row-major 3x4 [Rcw | tcw], ow [npairs][3] = -Rcw^T tcw as the caller computes it.  Query i of pair p is KeyFrame slot i
+ * (pKF->GetMapPointMatches()[i]); nq [npairs] of them in rows of q_stride: valid (pMP && !isBad() && !sAlreadyFound.count(pMP)),
+ * pw [..][3] (GetWorldPos), min_dist / max_dist (mfMinDistance / mfMaxDistance), angle (pKF->mvKeysUn[i].angle) and qdesc [..][32]
+ * (GetDescriptor).  A query that is not valid reads nothing else.  Numerics are those of the facade's M5 lines against cvcompat.h:
+ * x3Dc = (float)(double sum of R * X) + t, u = fx * x / z + cx in float without contraction and NO depth test, closed bounds (reject
+ * only u < minX || u > maxX || v < minY || v > maxY; k_host = (fx, fy, cx, cy), bounds_host = (minX, maxX, minY, maxY)), dist3D =
+ * (float)sqrt(double sum of PO^2) within [0.8f * min_dist, 1.2f * max_dist], PredictScale as orbm_is_in_frustum computes it
+ * (log_scale_factor, nlevels of the frame); a point with z == 0 exactly is outside the contract.  The window is
+ * Frame::GetFeaturesInArea(u, v, th * scale[level], level - 1, level + 1) without a stereo gate.  Claims run in query order: the first
+ * candidate of least distance whose slot is not blocked is accepted at bestDist <= orb_dist and EVERY claim blocks its slot
+ * (:2791-2793); with check_orientation the 30-bin histogram of angle_kf - angle_f and the three-maxima cull follow.  Outputs (device):
+ * match [npairs][cap] = the row orbm_search_by_projection_kf returns (query index / ORBM_NO_MATCH / ORBM_MATCH_PRUNED, padded with
+ * ORBM_NO_MATCH to cap), nmatches [npairs] = its return value.  A pair whose f_row lies outside [0, nf_rows) gets an all
+ * ORBM_NO_MATCH row and 0.  All pointers are device pointers except the *_host tables; enqueue-only: the handle's work buffers are
+ * allocated by the first eager call and reused, so after one eager call of the same or a smaller shape the call can be captured
+ * (orbx_capture_begin) and allocates nothing.  ORBM_E_INVALID: a NULL required array, npairs, nf_rows, cap, q_stride or nlevels < 1,
+ * th not finite, orb_dist > 255 (a negative orb_dist matches nothing); ORBM_E_CAPACITY: cap > 65535, q_stride > ORBM_LP_MAX_QUERIES,
+ * nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_by_projection_kf_batch_async(orbm_t*, int npairs,
+                                             int nf_rows, int cap, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                             const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                             const int32_t* f_row, const uint8_t* f_blocked, const float* tcw, const float* ow,
+                                             const int32_t* nq, int q_stride, const uint8_t* valid, const float* pw,
+                                             const float* min_dist, const float* max_dist, const float* angle, const uint8_t* qdesc,
+                                             const float* k_host, const float* bounds_host, float th, int orb_dist,
+                                             const float* scale_factors_host, float log_scale_factor, int nlevels, int check_orientation,
+                                             int32_t* match, int32_t* nmatches);
 
 /* ---- batched, DEVICE-resident stereo step (config C3: EuRoC stereo).  All pointers are device pointers; enqueue only.
  * orbm_stereo_batch_async: M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276) for `npairs` stereo pairs of ONE extractor

@@ -837,6 +837,11 @@ def _install_search():
                                         vp, ci, vp, vp, vp, vp, vp, vp, ci,         # nq, q_stride, valid, pw, normal, min/max dist, qdesc, q_shared
                                         vp, vp, cf, cf, ci, vp, vp, cf, ci,         # k, bounds, bf, th, chi2_gate, sf, inv_sigma2, log sf, nlevels
                                         vp, vp, vp]                                 # best_idx, nfused, level_out
+    L.orbm_search_by_projection_kf_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,          # pairs, frame pool (kps, desc, counts)
+                                                           vp, vp, cf, cf, cf, cf, vp, vp, vp, vp,  # grid, bounds, f_row, f_blocked, tcw, ow
+                                                           vp, ci, vp, vp, vp, vp, vp, vp,      # nq, q_stride, valid, pw, min/max dist, angle, qdesc
+                                                           vp, vp, cf, ci, vp, cf, ci, ci,      # k, bounds, th, orb_dist, sf, log sf, nlevels, check_ori
+                                                           vp, vp]                              # match, nmatches
     L.orbm_bow_transform_batch_async.argtypes = [vp, vp, vp, ci, ci, vp, vp, vp]
     L.orbm_search_by_bow_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, KF pool
                                                  ci, ci, vp, vp, vp, vp, vp,               # frame pool
@@ -918,6 +923,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
             "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
+            "orbm_search_by_projection_kf_batch_async",
             "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]

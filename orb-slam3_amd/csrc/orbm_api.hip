@@ -1363,6 +1363,58 @@ int orbm_fuse_batch_async(orbm_t* m, int npairs,
     return ORBM_OK;
 }
 
+int orbm_search_by_projection_kf_batch_async(orbm_t* m, int npairs,
+                                             int nf_rows, int cap, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                             const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                             const int32_t* f_row, const uint8_t* f_blocked, const float* tcw, const float* ow,
+                                             const int32_t* nq, int q_stride, const uint8_t* valid, const float* pw,
+                                             const float* min_dist, const float* max_dist, const float* angle, const uint8_t* qdesc,
+                                             const float* k_host, const float* bounds_host, float th, int orb_dist,
+                                             const float* scale_factors_host, float log_scale_factor, int nlevels, int check_orientation,
+                                             int32_t* match, int32_t* nmatches) {
+    if (!m || !kps_f || !desc_f || !counts_f || !grid_start || !grid_idx || !tcw || !ow || !nq || !valid || !pw || !min_dist || !max_dist ||
+        !angle || !qdesc || !k_host || !bounds_host || !scale_factors_host || !match || !nmatches) {
+        set_merr("SearchByProjection KF batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nf_rows < 1 || cap < 1 || q_stride < 1 || nlevels < 1 || !std::isfinite(th) || orb_dist > 255) {
+        set_merr("SearchByProjection KF batch: npairs, nf_rows, cap, q_stride and nlevels must be >= 1, th finite, orb_dist <= 255");
+        return ORBM_E_INVALID;
+    }
+    if (const int rc = lp_capacity("SearchByProjection KF batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // blocked bits, histogram, the current 64 queries' lists
+    // scratch of the handle: per query the window population, its TK_K best candidates, a slot of the accepted-assignment list, the
+    // radius and the window centre / level (the last two read back only by a rescan)
+    const size_t rows = (size_t)npairs * q_stride;
+    const size_t bWin = rows * sizeof(float4), bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned),
+                 bAcc = rows * sizeof(unsigned), bR = rows * sizeof(float);
+    uint8_t* scr = batch_scratch(m, bWin + bCnt + bKeys + bAcc + bR);
+    if (!scr) {
+        set_merr("SearchByProjection KF batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bWin + bCnt + bKeys + bAcc + bR);
+        return ORBM_E_HIP;
+    }
+    float4* topWin = (float4*)scr; int* topCnt = (int*)(scr + bWin); unsigned* topKeys = (unsigned*)(scr + bWin + bCnt);
+    unsigned* acc = (unsigned*)(scr + bWin + bCnt + bKeys); float* topR = (float*)(scr + bWin + bCnt + bKeys + bAcc);
+    RlRows R;
+    R.nq = nq; R.valid = valid; R.pw = pw; R.min_dist = min_dist; R.max_dist = max_dist; R.angle = angle; R.qdesc = qdesc;
+    RlParams P;
+    for (int i = 0; i < 4; ++i) { P.k[i] = k_host[i]; P.bounds[i] = bounds_host[i]; }
+    P.th = th; P.logSF = log_scale_factor; P.factor = ORBM_HISTO_LENGTH / 360.0f;   // ORBmatcher.cc:2736
+    P.nlevels = nlevels; P.q_stride = q_stride; P.nf_rows = nf_rows; P.orb_dist = orb_dist; P.check_ori = check_orientation != 0;
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    for (int i = 0; i < 12; ++i) P.sf[i] = st.sf[i];
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_rl_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps_f, desc_f, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, f_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
+    hipLaunchKernelGGL(k_rl_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_f, desc_f, counts_f, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, f_row, f_blocked, R, P, topCnt, topKeys, topR, topWin, acc, match, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 // ---- DBoW2 vocabulary ----
 struct orbm_vocab {
     int k = 0, L = 0, nnodes = 0, nwords = 0, device = 0;

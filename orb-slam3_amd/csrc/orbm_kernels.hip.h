@@ -2428,6 +2428,184 @@ __global__ __launch_bounds__(256) void k_fuse_count(const int* __restrict__ best
 }
 
 // ------------------------------------------------------------------------------------------------
+// Batched relocalisation SearchByProjection -- M5, SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) (ORBmatcher.cc:
+// 2723-2852) of Tracking::Relocalization -- for (frame row, candidate KeyFrame, pose) pairs, pinhole, Nleft == -1.  Query i of a pair
+// is KeyFrame slot i; the frame is a row of a Frame pool with its grid.
+// k_rl_topk: a wave per (pair, query), as k_fuse_topk.  The projection and gates run wave-uniformly (rl_project); the window
+//   Frame::GetFeaturesInArea(u, v, th * scale[level], level - 1, level + 1) (:2778) is one win_sweep with the rotation-bin payload of
+//   angle_kf - angle_f (:2829-2833).  Out, as k_mm_topk: the window population, its TK_K best candidate words, the radius, and the
+//   window centre and level a rescan needs.
+// k_rl_claim: one wave per pair replays the claims in query order, as k_mm_claim: the first unblocked listed candidate is the query's
+//   `dist < bestDist` winner among the free slots; a truncated list whose candidates are all blocked is rescanned with the blocked set
+//   applied.  Unlike M4, EVERY claim blocks its slot (:2793, mvpMapPoints[i2] is set for every match), so a slot is assigned at most once
+//   and the rotation cull prunes each assignment once.  bestDist <= ORBdist accepts.
+// ------------------------------------------------------------------------------------------------
+struct RlRows {                                            // the per-query arrays of one call, [npairs][q_stride]
+    const int* nq; const uint8_t* valid;
+    const float* pw; const float* min_dist; const float* max_dist; const float* angle; const uint8_t* qdesc;
+};
+struct RlParams { float k[4], bounds[4], th, logSF, factor; int nlevels, q_stride, nf_rows, orb_dist, check_ori; float sf[12]; };
+
+// The projection and gates of M5 (ORBmatcher.cc:2756-2776 as facade/ORBmatcher.h evaluates them against cvcompat.h): x3Dc through
+// mm_dot3 + t, pinhole u = fx * x / z + cx with NO depth test, the closed bounds test (u < minX || u > maxX, v < minY || v > maxY
+// reject), dist3D the float of a double norm against [0.8 min, 1.2 max], then PredictScale with the frame's log scale factor as
+// k_frustum computes it.  Returns the predicted level, or -1.
+__device__ __forceinline__ int rl_project(const float* T, const float* O, const float* X, float minDist, float maxDist, const RlParams& P,
+                                          float& u, float& v) {
+    const float x0 = X[0], x1 = X[1], x2 = X[2];
+    const float xc = mm_dot3(T[0], T[1], T[2], x0, x1, x2) + T[3];
+    const float yc = mm_dot3(T[4], T[5], T[6], x0, x1, x2) + T[7];
+    const float zc = mm_dot3(T[8], T[9], T[10], x0, x1, x2) + T[11];
+    u = P.k[0] * xc / zc + P.k[2];
+    v = P.k[1] * yc / zc + P.k[3];
+    if (u < P.bounds[0] || u > P.bounds[1]) return -1;
+    if (v < P.bounds[2] || v > P.bounds[3]) return -1;
+    const float maxD = 1.2f * maxDist, minD = 0.8f * minDist;
+    const float o0 = x0 - O[0], o1 = x1 - O[1], o2 = x2 - O[2];
+    double d2 = 0.0;
+    d2 += (double)o0 * (double)o0; d2 += (double)o1 * (double)o1; d2 += (double)o2 * (double)o2;
+    const float dist = (float)sqrt(d2);
+    if (dist < minD || dist > maxD) return -1;
+    const float ratio = maxDist / dist;
+    const float lg = (float)log((double)ratio);
+    int ns = (int)ceilf(lg / P.logSF);
+    if (ns < 0) ns = 0; else if (ns >= P.nlevels) ns = P.nlevels - 1;
+    return ns;
+}
+
+__global__ __launch_bounds__(256) void k_rl_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row,
+                                                 const float* __restrict__ tcw, const float* __restrict__ ow, RlRows R, RlParams P,
+                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r,
+                                                 float4* __restrict__ out_win) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.y;
+    const int row = f_row ? f_row[p] : p;
+    if (row < 0 || row >= P.nf_rows) return;                                 // k_rl_claim reads nothing of this pair
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nq = min(max(R.nq[p], 0), P.q_stride);
+    if (q >= nq) return;
+    const size_t o = (size_t)p * P.q_stride + q;
+    int lvl = -1, cnt = 0;
+    float u = 0.f, v = 0.f, r = 0.f;
+    u64 top[TK_K];
+    if (R.valid[o]) lvl = rl_project(tcw + (size_t)p * 12, ow + (size_t)p * 3, R.pw + o * 3, R.min_dist[o], R.max_dist[o], P, u, v);
+    if (lvl >= 0) {
+        u64 a[4];
+        load_desc(R.qdesc + o * 32, a);
+        r = P.th * P.sf[lvl];                                                // radius = th * mvScaleFactors[nPredictedLevel], :2775
+        const Win w = {u, v, r, 0.f, lvl - 1, lvl + 1};
+        win_sweep<true>(w, RotBinPay{R.angle[o], P.factor}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr,
+                        grid_start + (size_t)row * (64 * 48 + 1), grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr,
+                        lane, cnt, top);
+    } else {
+#pragma unroll
+        for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
+    }
+    if (lane == 0) {
+        put_topk(out_cnt, out_r, out_keys, o, cnt, r, top);
+        out_win[o] = make_float4(u, v, 0.f, __int_as_float(lvl));            // read back only by a rescan (count > TK_K)
+    }
+}
+
+__global__ __launch_bounds__(64) void k_rl_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row,
+                                                 const uint8_t* __restrict__ f_blocked, RlRows R, RlParams P,
+                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
+                                                 const float4* __restrict__ topWin, unsigned int* __restrict__ accepted,
+                                                 int* __restrict__ match, int* __restrict__ nmatches) {
+    extern __shared__ unsigned int rl_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][TK_K]
+    const unsigned INV = 0xFFFFFFFFu;
+    const int lane = threadIdx.x, p = blockIdx.x;
+    const int row = f_row ? f_row[p] : p;
+    const bool live = row >= 0 && row < P.nf_rows;                           // (wave-uniform) an out-of-range row: all NO_MATCH and 0
+    const int nt = live ? min(max(counts[row], 0), cap) : 0;
+    const int nq = live ? min(max(R.nq[p], 0), P.q_stride) : 0;
+    const int nwords = (cap + 31) >> 5;
+    unsigned int* blk = rl_lds;
+    unsigned int* hist = rl_lds + nwords;
+    unsigned int* sk = hist + 32;
+    int* mrow = match + (size_t)p * cap;
+    for (int wd = lane; wd < nwords; wd += 64) blk[wd] = bits_word(f_blocked ? f_blocked + (size_t)p * cap : nullptr, nt, wd, 0u);
+    if (lane < 32) hist[lane] = 0;
+    for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
+    __syncthreads();
+    const size_t rowOff = live ? (size_t)row : 0;
+    const KpIn* kt = kps + rowOff * cap;
+    const uint8_t* dt = desc + rowOff * cap * 32;
+    const int* gs = grid_start + rowOff * (64 * 48 + 1);
+    const int* gi = grid_idx + rowOff * cap;
+    const size_t rowBase = (size_t)p * P.q_stride;
+    unsigned int* acc = accepted + rowBase;                                  // (slot | bin << 16) of every assignment with a bin, in order
+    int nm = 0, nacc = 0;
+    // the next 64 queries' lists and counts are in flight while the current ones are replayed (clamped, unconditional loads)
+    const unsigned int* keyRow = topKeys + rowBase * TK_K;
+    const int* cntRow = topCnt + rowBase;
+    unsigned int pk[TK_K];
+    int pc = 0;
+    auto fetch = [&](int W0) {
+        const int last = nq * TK_K - 1;
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) pk[r] = keyRow[min(W0 * TK_K + r * 64 + lane, last)];
+        pc = cntRow[min(W0 + lane, nq - 1)];
+    };
+    if (nq > 0) fetch(0);
+    for (int W0 = 0; W0 < nq; W0 += 64) {
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) sk[r * 64 + lane] = pk[r];             // query i's list: sk[i * TK_K .. + TK_K)
+        const int cnt = W0 + lane < nq ? pc : 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (W0 + 64 < nq) fetch(W0 + 64);
+        unsigned long long todo = __ballot(cnt > 0);                        // skipped queries and empty windows have count 0
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            unsigned int key = INV;
+            bool fr = false;
+            if (lane < TK_K) {
+                key = sk[i * TK_K + lane];
+                const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
+                fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
+            }
+            const unsigned long long fb = __ballot(fr);
+            unsigned int best = fb ? (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1) : INV;
+            if (best == INV && __builtin_amdgcn_readlane(cnt, i) > TK_K) {
+                // every listed candidate is blocked and the window holds more: the window k_rl_topk swept again, blocked set applied
+                const size_t o = rowBase + W0 + i;
+                const float4 cw = topWin[o];
+                const int lvl = __float_as_int(cw.w);
+                const Win w = {cw.x, cw.y, topR[o], 0.f, lvl - 1, lvl + 1};
+                u64 a[4], top[TK_K];
+                load_desc(R.qdesc + o * 32, a);
+                int c2;
+                win_sweep<false>(w, RotBinPay{R.angle[o], P.factor}, kt, dt, nullptr, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                best = cand_word(top[0]);
+            }
+            if (best == INV || (int)(best >> 21) > P.orb_dist) continue;    // bestDist <= ORBdist (:2789)
+            const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
+            const bool withBin = P.check_ori && bin != TK_NOBIN;
+            if (lane == 0) {
+                mrow[k] = W0 + i;
+                blk[k >> 5] |= 1u << (k & 31);                               // every claim blocks its slot (:2791-2793)
+                if (withBin) { acc[nacc] = k | (bin << 16); hist[bin] += 1u; }
+            }
+            ++nm;
+            if (withBin) ++nacc;
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // the next chunk's lists overwrite sk
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (P.check_ori) nm -= rot_cull(hist, acc, nacc, mrow, lane);
+    if (lane == 0) nmatches[p] = nm;
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_bow_transform2: DBoW2 TemplatedVocabulary::transform (TemplatedVocabulary.h:1196-1262) for a batch of descriptors: at every level the
 // child with the smallest Hamming distance (first minimum, strict <) is taken; the node reached at level L - levelsup is recorded.
 // The tree is in the level-major layout the host builds (orbm_vocab_create): nodes renumbered breadth-first so
