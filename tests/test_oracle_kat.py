@@ -4,6 +4,8 @@ import hashlib
 
 import numpy as np
 
+from structured_images import fast_bruteforce
+
 
 def test_tables_match_reference_constructor(oracle):
     # ORBextractor.cc:509-526 (feature split) and :542-570 (umax), SURVEY 8(a) E0
@@ -95,25 +97,8 @@ def test_fast_matches_bruteforce_definition(oracle):
     base = rng.integers(0, 256, (8, 9)).astype(np.float64)
     img = np.kron(base, np.ones((5, 5)))[:38, :42] + rng.normal(0, 6, (38, 42))
     img = np.clip(np.rint(img), 0, 255).astype(np.uint8)
-    dx = [0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1]
-    dy = [3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3]
-    h, w = img.shape
     for thr in (7, 20):
-        S = np.zeros((h, w), np.int64)
-        for y in range(3, h - 3):
-            for x in range(3, w - 3):
-                v = int(img[y, x]); d = [v - int(img[y + dy[k], x + dx[k]]) for k in range(16)]
-                A = max(min(d[(s + t) % 16] for t in range(9)) for s in range(16))
-                B = max(min(-d[(s + t) % 16] for t in range(9)) for s in range(16))
-                if max(A, B) > thr:
-                    S[y, x] = max(A, B) - 1
-        exp = []
-        for y in range(3, h - 3):
-            for x in range(3, w - 3):
-                if S[y, x] > 0:
-                    nb = S[y - 1:y + 2, x - 1:x + 2].copy(); nb[1, 1] = -1
-                    if S[y, x] > nb.max():
-                        exp.append([x, y, int(S[y, x])])
+        exp = fast_bruteforce(img, thr)
         assert oracle.fast(img, thr).tolist() == exp
 
 
