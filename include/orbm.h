@@ -485,6 +485,65 @@ int orbm_search_by_bow_batch_async(orbm_t*, int npairs,
                                    const int32_t* node_f, const double* weight_f,
                                    const int32_t* kf_row, const int32_t* f_row, float nnratio, int check_orientation,
                                    int32_t* f_match, int32_t* nmatches);
+/* orbm_search_by_bow_kf_batch_async: M8 SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) -- LoopClosing::DetectCommonRegionsFromBoW
+ * (LoopClosing.cc:822, matcher(0.9, true): the current KeyFrame against every candidate and its covisibles) -- END TO END on the device for
+ * `npairs` pairs (ORBmatcher.cc:955-1105, Nleft == -1; fisheye KeyFrames stay with orbm_search_by_bow_kf).  Two pools of rows as in
+ * orbm_search_by_bow_batch_async: pool 1 has nrows1 rows of cap1 slots -- kps1 (mvKeysUn), desc1 [..][32], counts1 [nrows1], node1 / weight1
+ * (orbm_bow_transform_batch_async over the rows), good1 (pMP && !pMP->isBad()) --, pool 2 the same arrays with nrows2 / cap2; a caller with
+ * one pool passes it twice.  Pair p matches row row1[p] of pool 1 (pKF1) against row row2[p] of pool 2 (pKF2); NULL = row p; place
+ * recognition repeats row1.  Where M8 differs from M7: BOTH sides drop features without a good MapPoint (:1000-1004, :1021-1028) besides
+ * the stopped words (weight <= 0; NULL weight = none) and slots >= count; the outer loop is pKF1's bucket in ascending feature index and
+ * the claimed side is pKF2 (vbMatched2); bestDist1 < TH_LOW is STRICT (:1054; M7 has <=) with (float)bestDist1 < nnratio *
+ * (float)bestDist2 and the if / else-if runner-up; check_orientation: rot = angle1 - angle2, factor 30/360.0f, round, bin 30 -> 0, the
+ * three-maxima cull; a culled idx1 becomes -1 and is not counted.  Outputs (device): matches12 [npairs][cap1] = the pKF2 feature index of
+ * pKF1 feature idx1, or -1 (the row orbm_search_by_bow_kf returns, padded with -1 to cap1), nmatches [npairs] = its return value.  A pair
+ * whose row1 or row2 lies outside [0, nrows1) / [0, nrows2) gets an all -1 row and 0.  The kernel is M7's (one workgroup per pair, bucket
+ * lists and the claimed-side row over cap2 in LDS); M7 at ORBM_BOW_MAX_CAP already uses 157 of the 160 KB, so there is no second LDS row
+ * over cap1: the claimed-side row is transposed into matches12 at the end (fill -1, barrier, scatter), and ORBM_BOW_MAX_CAP holds for both
+ * caps here too.  All pointers are device pointers; enqueue-only, no scratch: every call can be captured (orbx_capture_begin) once one
+ * eager call with the same or larger caps has run.  ORBM_E_INVALID: a NULL required array (the weights may be NULL), npairs, nrows1,
+ * nrows2, cap1 or cap2 < 1, nnratio not finite; ORBM_E_CAPACITY: cap1 or cap2 > ORBM_BOW_MAX_CAP, npairs > 65535.  Nothing is enqueued
+ * then. */
+int orbm_search_by_bow_kf_batch_async(orbm_t*, int npairs,
+                                      int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                      const int32_t* node1, const double* weight1, const uint8_t* good1,
+                                      int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                      const int32_t* node2, const double* weight2, const uint8_t* good2,
+                                      const int32_t* row1, const int32_t* row2, float nnratio, int check_orientation,
+                                      int32_t* matches12, int32_t* nmatches);
+/* orbm_search_by_projection_sim3_batch_async: M6 SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:549-679)
+ * and its vpPointsKFs overload (:681-797) -- LoopClosing::DetectCommonRegionsFromBoW (LoopClosing.cc:963 with th 8 / ratio 1.5, :993 with
+ * 5 / 1.0) and FindMatchesByProjection (:1248, 3 / 1.5) -- END TO END on the device for `npairs` (KeyFrame row, Sim3 pose, MapPoint row)
+ * triples, pinhole camera, Nleft == -1; fisheye KeyFrames and other cameras stay with orbm_search_by_projection_sim3.  The KeyFrame pool
+ * has nkf_rows rows of cap slots: kps_kf (mvKeysUn), desc_kf [..][32], counts_kf and the grid of orbm_grid_build_batch_async over the pool,
+ * indexed by row.  Pair p searches row kf_row[p] (NULL = row p); tcw [npairs][12] is the row-major 3x4 [Rcw | tcw] with Rcw = sRcw / scw
+ * and tcw / scw, ow [npairs][3] = -Rcw^T tcw, as the caller computes them from Scw; matched_in [npairs][cap] = vpMatched[idx] != NULL
+ * (NULL = none).  The queries are MapPoints: nq [npairs] of them per pair in rows of q_stride: valid (!pMP->isBad() &&
+ * !spAlreadyFound.count(pMP)), pw [..][3] (GetWorldPos), normal [..][3] (GetNormal), min_dist / max_dist (mfMinDistance / mfMaxDistance),
+ * qdesc [..][32] (GetDescriptor).  A query that is not valid reads nothing else.  Projection and gates are those of orbm_fuse_batch_async
+ * (x3Dc = (float)(double sum of R * X) + t, z < 0 rejects, half-open IsInImage, [0.8f * min_dist, 1.2f * max_dist], PO . normal < 0.5 *
+ * dist rejects, PredictScale with log_scale_factor / nlevels) with ONE difference that proj_form selects: 0 = mpCamera->project, u = fx *
+ * x / z + cx (:602); 1 = the vpPointsKFs overload's invz = 1 / z, u = fx * (x * invz) + cx (:724-729).  They round differently.  The window
+ * is KeyFrame::GetFeaturesInArea(u, v, th * scale[level]); candidates of levels [level-1, level]; slots with matched set are skipped; the
+ * first minimum in visiting order is accepted when (float)bestDist <= TH_LOW * ratio_hamming (the float product, as the reference writes
+ * it).  Claims run in query order and EVERY claim blocks its slot for later queries; no rotation check.  A window whose candidates are all
+ * blocked leaves bestDist = 256, where the reference would write vpMatched[-1] if the bound reached it: a ratio_hamming with
+ * 50 * ratio_hamming >= 256 is refused.  Outputs (device): match [npairs][cap] = the query index iMP assigned to KeyFrame slot idx, or -1
+ * (the row orbm_search_by_projection_sim3 returns, padded with -1 to cap), nmatches [npairs] = its return value.  A pair whose kf_row lies
+ * outside [0, nkf_rows) gets an all -1 row and 0.  All pointers are device pointers except the *_host tables; enqueue-only: the handle's
+ * work buffers are allocated by the first eager call and reused, so after one eager call of the same or a smaller shape the call can be
+ * captured (orbx_capture_begin) and allocates nothing.  ORBM_E_INVALID: a NULL required array, npairs, nkf_rows, cap, q_stride or nlevels
+ * < 1, ratio_hamming not finite or 50 * ratio_hamming >= 256, proj_form not 0 / 1; ORBM_E_CAPACITY: cap > 65535, q_stride >
+ * ORBM_LP_MAX_QUERIES, nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_by_projection_sim3_batch_async(orbm_t*, int npairs,
+                                               int nkf_rows, int cap, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                               const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                               const int32_t* kf_row, const uint8_t* matched_in, const float* tcw, const float* ow,
+                                               const int32_t* nq, int q_stride, const uint8_t* valid, const float* pw, const float* normal,
+                                               const float* min_dist, const float* max_dist, const uint8_t* qdesc,
+                                               const float* k_host, const float* bounds_host, int th, float ratio_hamming, int proj_form,
+                                               const float* scale_factors_host, float log_scale_factor, int nlevels,
+                                               int32_t* match, int32_t* nmatches);
 
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the

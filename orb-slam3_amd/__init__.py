@@ -846,6 +846,14 @@ def _install_search():
     L.orbm_search_by_bow_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, KF pool
                                                  ci, ci, vp, vp, vp, vp, vp,               # frame pool
                                                  vp, vp, cf, ci, vp, vp]                   # kf_row, f_row, nnratio, check_ori, outputs
+    L.orbm_search_by_bow_kf_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, pool 1 (pKF1)
+                                                    ci, ci, vp, vp, vp, vp, vp, vp,            # pool 2 (pKF2)
+                                                    vp, vp, cf, ci, vp, vp]                    # row1, row2, nnratio, check_ori, outputs
+    L.orbm_search_by_projection_sim3_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,       # pairs, KF pool (kps, desc, counts)
+                                                             vp, vp, cf, cf, cf, cf, vp, vp, vp, vp,   # grid, bounds, kf_row, matched_in, tcw, ow
+                                                             vp, ci, vp, vp, vp, vp, vp, vp,   # nq, q_stride, valid, pw, normal, min/max dist, qdesc
+                                                             vp, vp, ci, cf, ci, vp, cf, ci,   # k, bounds, th, ratio, proj_form, sf, log sf, nlevels
+                                                             vp, vp]                           # match, nmatches
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -923,7 +931,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
             "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
-            "orbm_search_by_projection_kf_batch_async",
+            "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",
             "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]

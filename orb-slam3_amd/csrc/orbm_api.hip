@@ -1223,7 +1223,7 @@ int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps
     if (const int rc = lp_capacity("SearchByProjection points batch", cap, q_stride, nlevels, nframes, "frames")) return rc;
     MHIPCHK(hipSetDevice(m->device));
     const ScaleTab st = scale_tab(scale_factors_host, nlevels);
-    const size_t lds = (size_t)(((cap + 31) >> 5) + 64 * TK_K) * sizeof(unsigned);   // blocked bits, the current 64 queries' lists
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // k_claim's layout: blocked bits, histogram (unused here), the current 64 queries' lists
     // scratch of the handle: per query the window population, its TK_K best candidates and its radius
     const size_t rows = (size_t)nframes * q_stride;
     const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = rows * sizeof(float);
@@ -1407,8 +1407,68 @@ int orbm_search_by_projection_kf_batch_async(orbm_t* m, int npairs,
     MHIPCHK(rec_time(m, m->e0));
     hipLaunchKernelGGL(k_rl_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps_f, desc_f, cap, grid_start, grid_idx,
                        min_x, min_y, inv_w, inv_h, f_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
-    hipLaunchKernelGGL(k_rl_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_f, desc_f, counts_f, cap, grid_start, grid_idx,
+    hipLaunchKernelGGL(k_claim<RlPol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_f, desc_f, counts_f, cap, grid_start, grid_idx,
                        min_x, min_y, inv_w, inv_h, f_row, f_blocked, R, P, topCnt, topKeys, topR, topWin, acc, match, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
+int orbm_search_by_projection_sim3_batch_async(orbm_t* m, int npairs,
+                                               int nkf_rows, int cap, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                               const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                               const int32_t* kf_row, const uint8_t* matched_in, const float* tcw, const float* ow,
+                                               const int32_t* nq, int q_stride, const uint8_t* valid, const float* pw, const float* normal,
+                                               const float* min_dist, const float* max_dist, const uint8_t* qdesc,
+                                               const float* k_host, const float* bounds_host, int th, float ratio_hamming, int proj_form,
+                                               const float* scale_factors_host, float log_scale_factor, int nlevels,
+                                               int32_t* match, int32_t* nmatches) {
+    if (!m || !kps_kf || !desc_kf || !counts_kf || !grid_start || !grid_idx || !tcw || !ow || !nq || !valid || !pw || !normal || !min_dist ||
+        !max_dist || !qdesc || !k_host || !bounds_host || !scale_factors_host || !match || !nmatches) {
+        set_merr("SearchByProjection Sim3 batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    const float maxDist = ORBM_TH_LOW * ratio_hamming;                       // the reference's float product (:651, :773)
+    if (npairs < 1 || nkf_rows < 1 || cap < 1 || q_stride < 1 || nlevels < 1 || !std::isfinite(ratio_hamming) || !(maxDist < 256.f) ||
+        (proj_form != 0 && proj_form != 1)) {
+        set_merr("SearchByProjection Sim3 batch: npairs, nkf_rows, cap, q_stride and nlevels must be >= 1, ratio_hamming finite with "
+                 "50 * ratio_hamming < 256, proj_form 0 or 1");
+        return ORBM_E_INVALID;
+    }
+    if (const int rc = lp_capacity("SearchByProjection Sim3 batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // k_claim's layout: blocked bits, histogram (unused here), the current 64 queries' lists
+    // scratch of the handle, as M5's: per query the window population, its TK_K best candidates, the radius and the window centre / level
+    const size_t rows = (size_t)npairs * q_stride;
+    const size_t bWin = rows * sizeof(float4), bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned),
+                 bR = rows * sizeof(float);
+    uint8_t* scr = batch_scratch(m, bWin + bCnt + bKeys + bR);
+    if (!scr) {
+        set_merr("SearchByProjection Sim3 batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bWin + bCnt + bKeys + bR);
+        return ORBM_E_HIP;
+    }
+    float4* topWin = (float4*)scr; int* topCnt = (int*)(scr + bWin); unsigned* topKeys = (unsigned*)(scr + bWin + bCnt);
+    float* topR = (float*)(scr + bWin + bCnt + bKeys);
+    FuseRows R;
+    R.nq = nq; R.valid = valid; R.pw = pw; R.normal = normal; R.min_dist = min_dist; R.max_dist = max_dist; R.qdesc = qdesc;
+    FuseParams P;
+    for (int i = 0; i < 4; ++i) { P.k[i] = k_host[i]; P.bounds[i] = bounds_host[i]; }
+    P.bf = 0.f; P.th = (float)th; P.logSF = log_scale_factor;
+    P.nlevels = nlevels; P.q_stride = q_stride; P.q_shared = 0; P.chi2 = 0; P.nkf_rows = nkf_rows;
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    for (int i = 0; i < 12; ++i) { P.sf[i] = st.sf[i]; P.isg[i] = 0.f; }
+    const S3Claim Cp{q_stride, nkf_rows, maxDist};
+    MHIPCHK(rec_time(m, m->e0));
+    const dim3 tg((q_stride + 3) / 4, npairs);
+    if (proj_form)
+        hipLaunchKernelGGL(k_s3_topk<1>, tg, dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
+    else
+        hipLaunchKernelGGL(k_s3_topk<0>, tg, dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
+    hipLaunchKernelGGL(k_claim<S3Pol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_kf, desc_kf, counts_kf, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, kf_row, matched_in, S3Rows{nq, qdesc}, Cp, topCnt, topKeys, topR, topWin, (unsigned*)nullptr, match, nmatches);
     MHIPCHK(rec_time(m, m->e1));
     MHIPCHK(hipGetLastError());
     m->timed = true;
@@ -2003,12 +2063,47 @@ int orbm_search_by_bow_batch_async(orbm_t* m, int npairs,
     // above 48 KB the launch needs the attribute on the current device; always the largest legal size, so that a graph captured
     // earlier with bigger rows still launches after a call with smaller ones
     if (lds > 48 * 1024)
-        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bow_search_lds(ORBM_BOW_MAX_CAP, ORBM_BOW_MAX_CAP)));
+        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bow_search_lds(ORBM_BOW_MAX_CAP, ORBM_BOW_MAX_CAP)));
     BowSide K{(const KpIn*)kps_kf, desc_kf, counts_kf, node_kf, weight_kf, good_kf, nkf_rows, cap_kf};
     BowSide F{(const KpIn*)kps_f, desc_f, counts_f, node_f, weight_f, nullptr, nf_rows, cap_f};
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_bow_search, dim3(npairs), dim3(BOW_WAVES * 64), lds, m->stream, npairs, K, F, kf_row, f_row, nnratio,
+    hipLaunchKernelGGL(k_bow_search<false>, dim3(npairs), dim3(BOW_WAVES * 64), lds, m->stream, npairs, K, F, kf_row, f_row, nnratio,
                        check_orientation, f_match, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
+int orbm_search_by_bow_kf_batch_async(orbm_t* m, int npairs,
+                                      int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                      const int32_t* node1, const double* weight1, const uint8_t* good1,
+                                      int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                      const int32_t* node2, const double* weight2, const uint8_t* good2,
+                                      const int32_t* row1, const int32_t* row2, float nnratio, int check_orientation,
+                                      int32_t* matches12, int32_t* nmatches) {
+    if (!m || !kps1 || !desc1 || !counts1 || !node1 || !good1 || !kps2 || !desc2 || !counts2 || !node2 || !good2 || !matches12 || !nmatches) {
+        set_merr("SearchByBoW KF batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nrows1 < 1 || nrows2 < 1 || cap1 < 1 || cap2 < 1 || !std::isfinite(nnratio)) {
+        set_merr("SearchByBoW KF batch: npairs, nrows1, nrows2, cap1 and cap2 must be >= 1 and nnratio finite");
+        return ORBM_E_INVALID;
+    }
+    if (cap1 > ORBM_BOW_MAX_CAP || cap2 > ORBM_BOW_MAX_CAP) {
+        set_merr("SearchByBoW KF batch: cap1 %d / cap2 %d above %d (the bucket lists and the claimed row live in LDS)", cap1, cap2, (int)ORBM_BOW_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (npairs > 65535) { set_merr("SearchByBoW KF batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t lds = bow_search_lds(cap1, cap2);
+    if (lds > 48 * 1024)                                                     // as orbm_search_by_bow_batch_async: always the largest legal size
+        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_search<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bow_search_lds(ORBM_BOW_MAX_CAP, ORBM_BOW_MAX_CAP)));
+    BowSide K{(const KpIn*)kps1, desc1, counts1, node1, weight1, good1, nrows1, cap1};
+    BowSide F{(const KpIn*)kps2, desc2, counts2, node2, weight2, good2, nrows2, cap2};
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_bow_search<true>, dim3(npairs), dim3(BOW_WAVES * 64), lds, m->stream, npairs, K, F, row1, row2, nnratio,
+                       check_orientation, matches12, nmatches);
     MHIPCHK(rec_time(m, m->e1));
     MHIPCHK(hipGetLastError());
     m->timed = true;

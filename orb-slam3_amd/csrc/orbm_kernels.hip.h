@@ -2353,6 +2353,8 @@ struct FuseGate {
 // through mm_dot3 + t, z < 0 rejects, invz = 1 / z, pinhole u = fx * x / z + cx, KeyFrame::IsInImage (half-open, KeyFrame.cc:965-968),
 // ur = u - bf * invz, dist3D the float of a double norm against [0.8 min, 1.2 max], PO . Pn (double) >= 0.5 dist3D, then PredictScale as
 // k_frustum computes it.  Returns the predicted level, or -1.
+// FORM 1 is the projection of SearchByProjection's vpPointsKFs overload (:724-729): x * invz first, then fx * x + cx; it rounds differently.
+template <int FORM = 0>
 __device__ __forceinline__ int fuse_project(const float* T, const float* O, const float* X, const float* N, float minDist, float maxDist,
                                             const FuseParams& P, float& u, float& v, float& ur) {
     const float x0 = X[0], x1 = X[1], x2 = X[2];
@@ -2361,8 +2363,14 @@ __device__ __forceinline__ int fuse_project(const float* T, const float* O, cons
     const float zc = mm_dot3(T[8], T[9], T[10], x0, x1, x2) + T[11];
     if (zc < 0.0f) return -1;
     const float invz = 1.0f / zc;
-    u = P.k[0] * xc / zc + P.k[2];
-    v = P.k[1] * yc / zc + P.k[3];
+    if (FORM == 1) {
+        const float x = xc * invz, y = yc * invz;
+        u = P.k[0] * x + P.k[2];
+        v = P.k[1] * y + P.k[3];
+    } else {
+        u = P.k[0] * xc / zc + P.k[2];
+        v = P.k[1] * yc / zc + P.k[3];
+    }
     if (!(u >= P.bounds[0] && u < P.bounds[1] && v >= P.bounds[2] && v < P.bounds[3])) return -1;
     ur = u - P.bf * invz;
     const float maxD = 1.2f * maxDist, minD = 0.8f * minDist;
@@ -2435,7 +2443,7 @@ __global__ __launch_bounds__(256) void k_fuse_count(const int* __restrict__ best
 //   Frame::GetFeaturesInArea(u, v, th * scale[level], level - 1, level + 1) (:2778) is one win_sweep with the rotation-bin payload of
 //   angle_kf - angle_f (:2829-2833).  Out, as k_mm_topk: the window population, its TK_K best candidate words, the radius, and the
 //   window centre and level a rescan needs.
-// k_rl_claim: one wave per pair replays the claims in query order, as k_mm_claim: the first unblocked listed candidate is the query's
+// k_claim<RlPol> (k_rl_claim until the replay was shared with M6): one wave per pair replays the claims in query order, as k_mm_claim: the first unblocked listed candidate is the query's
 //   `dist < bestDist` winner among the free slots; a truncated list whose candidates are all blocked is rescanned with the blocked set
 //   applied.  Unlike M4, EVERY claim blocks its slot (:2793, mvpMapPoints[i2] is set for every match), so a slot is assigned at most once
 //   and the rotation cull prunes each assignment once.  bestDist <= ORBdist accepts.
@@ -2482,7 +2490,7 @@ __global__ __launch_bounds__(256) void k_rl_topk(const KpIn* __restrict__ kps, c
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y;
     const int row = f_row ? f_row[p] : p;
-    if (row < 0 || row >= P.nf_rows) return;                                 // k_rl_claim reads nothing of this pair
+    if (row < 0 || row >= P.nf_rows) return;                                 // the claim replay reads nothing of this pair
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int nq = min(max(R.nq[p], 0), P.q_stride);
     if (q >= nq) return;
@@ -2509,10 +2517,22 @@ __global__ __launch_bounds__(256) void k_rl_topk(const KpIn* __restrict__ kps, c
     }
 }
 
-__global__ __launch_bounds__(64) void k_rl_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+// The replay is k_claim<Pol>; Pol carries what differs between the searches that share it: the per-query rows and parameters, the upper
+// end of the level band, the sweep's payload, the acceptance test and whether a rotation histogram is kept.  RlPol is M5 (k_rl_claim).
+struct RlPol {
+    using Rows = RlRows;
+    using Params = RlParams;
+    __device__ static int hi(int lvl) { return lvl + 1; }
+    __device__ static RotBinPay pay(const Rows& R, size_t o, const Params& P) { return RotBinPay{R.angle[o], P.factor}; }
+    __device__ static bool accept(unsigned int best, const Params& P) { return (int)(best >> 21) <= P.orb_dist; }   // bestDist <= ORBdist (:2789)
+    __device__ static bool ori(const Params& P) { return P.check_ori; }
+};
+
+template <class Pol>
+__global__ __launch_bounds__(64) void k_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
                                                  float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row,
-                                                 const uint8_t* __restrict__ f_blocked, RlRows R, RlParams P,
+                                                 const uint8_t* __restrict__ f_blocked, typename Pol::Rows R, typename Pol::Params P,
                                                  const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
                                                  const float4* __restrict__ topWin, unsigned int* __restrict__ accepted,
                                                  int* __restrict__ match, int* __restrict__ nmatches) {
@@ -2577,16 +2597,16 @@ __global__ __launch_bounds__(64) void k_rl_claim(const KpIn* __restrict__ kps, c
                 const size_t o = rowBase + W0 + i;
                 const float4 cw = topWin[o];
                 const int lvl = __float_as_int(cw.w);
-                const Win w = {cw.x, cw.y, topR[o], 0.f, lvl - 1, lvl + 1};
+                const Win w = {cw.x, cw.y, topR[o], 0.f, lvl - 1, Pol::hi(lvl)};
                 u64 a[4], top[TK_K];
                 load_desc(R.qdesc + o * 32, a);
                 int c2;
-                win_sweep<false>(w, RotBinPay{R.angle[o], P.factor}, kt, dt, nullptr, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                win_sweep<false>(w, Pol::pay(R, o, P), kt, dt, nullptr, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
                 best = cand_word(top[0]);
             }
-            if (best == INV || (int)(best >> 21) > P.orb_dist) continue;    // bestDist <= ORBdist (:2789)
+            if (best == INV || !Pol::accept(best, P)) continue;
             const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
-            const bool withBin = P.check_ori && bin != TK_NOBIN;
+            const bool withBin = Pol::ori(P) && bin != TK_NOBIN;
             if (lane == 0) {
                 mrow[k] = W0 + i;
                 blk[k >> 5] |= 1u << (k & 31);                               // every claim blocks its slot (:2791-2793)
@@ -2601,9 +2621,71 @@ __global__ __launch_bounds__(64) void k_rl_claim(const KpIn* __restrict__ kps, c
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
-    if (P.check_ori) nm -= rot_cull(hist, acc, nacc, mrow, lane);
+    if (Pol::ori(P)) nm -= rot_cull(hist, acc, nacc, mrow, lane);
     if (lane == 0) nmatches[p] = nm;
 }
+
+// ------------------------------------------------------------------------------------------------
+// Batched Sim3 SearchByProjection -- M6, SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (ORBmatcher.cc:549-679) and its
+// vpPointsKFs overload (:681-797) of LoopClosing::DetectCommonRegionsFromBoW / FindMatchesByProjection -- for (KeyFrame row, Sim3 pose,
+// MapPoint row) triples, pinhole, Nleft == -1.  The shape of M5 on the inputs of M13:
+// k_s3_topk: a wave per (pair, query).  fuse_project<FORM> is the projection with every gate (FORM 0: mpCamera->project, :602; FORM 1:
+//   x * invz, :724-729); the window KeyFrame::GetFeaturesInArea(u, v, th * scale[level]) is one win_sweep with the level band
+//   [level-1, level] (:637, :759).  Out, as k_rl_topk: the window population, its TK_K best candidate words, the radius, centre and level.
+// k_claim<S3Pol>: the claim replay M5 uses (k_claim<RlPol>), one wave per pair in query order.  The blocked set starts as matched_in (vpMatched[idx],
+//   :633, :755) and EVERY claim adds its slot (:653, :775: vpMatched[bestIdx] = pMP); (float)bestDist <= TH_LOW * ratioHamming accepts
+//   (max_dist is that float product, below 256 by the entry point's check); no rotation check.
+// ------------------------------------------------------------------------------------------------
+struct S3Claim { int q_stride, nf_rows; float max_dist; };
+
+template <int FORM>
+__global__ __launch_bounds__(256) void k_s3_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ kf_row,
+                                                 const float* __restrict__ tcw, const float* __restrict__ ow, FuseRows R, FuseParams P,
+                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r,
+                                                 float4* __restrict__ out_win) {
+    const int lane = threadIdx.x & 63;
+    const int p = blockIdx.y;
+    const int row = kf_row ? kf_row[p] : p;
+    if (row < 0 || row >= P.nkf_rows) return;                                // the claim replay reads nothing of this pair
+    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int nq = min(max(R.nq[p], 0), P.q_stride);
+    if (q >= nq) return;
+    const size_t o = (size_t)p * P.q_stride + q;
+    int lvl = -1, cnt = 0;
+    float u = 0.f, v = 0.f, ur = 0.f, r = 0.f;
+    u64 top[TK_K];
+    if (R.valid[o])
+        lvl = fuse_project<FORM>(tcw + (size_t)p * 12, ow + (size_t)p * 3, R.pw + o * 3, R.normal + o * 3, R.min_dist[o], R.max_dist[o], P, u, v, ur);
+    if (lvl >= 0) {
+        u64 a[4];
+        load_desc(R.qdesc + o * 32, a);
+        r = P.th * P.sf[lvl];                                                // radius = th * mvScaleFactors[nPredictedLevel], :622, :744
+        const Win w = {u, v, r, 0.f, lvl - 1, lvl};
+        win_sweep<true>(w, OctavePay{}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr,
+                        grid_start + (size_t)row * (64 * 48 + 1), grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr,
+                        lane, cnt, top);
+    } else {
+#pragma unroll
+        for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
+    }
+    if (lane == 0) {
+        put_topk(out_cnt, out_r, out_keys, o, cnt, r, top);
+        out_win[o] = make_float4(u, v, 0.f, __int_as_float(lvl));            // read back only by a rescan (count > TK_K)
+    }
+}
+
+// the claim replay of M6 (k_claim<S3Pol>): blocked bits from matched_in, band [level-1, level], no rotation bin, the float bound
+struct S3Rows { const int* nq; const uint8_t* qdesc; };
+struct S3Pol {
+    using Rows = S3Rows;
+    using Params = S3Claim;
+    __device__ static int hi(int lvl) { return lvl; }
+    __device__ static OctavePay pay(const Rows&, size_t, const Params&) { return OctavePay{}; }
+    __device__ static bool accept(unsigned int best, const Params& P) { return (float)(int)(best >> 21) <= P.max_dist; }   // bestDist <= TH_LOW * ratioHamming (:651, :773)
+    __device__ static bool ori(const Params&) { return false; }
+};
 
 // ------------------------------------------------------------------------------------------------
 // k_bow_transform2: DBoW2 TemplatedVocabulary::transform (TemplatedVocabulary.h:1196-1262) for a batch of descriptors: at every level the
@@ -2744,6 +2826,13 @@ __device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* st
     __syncthreads();
 }
 
+// KF = true is M8, ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (ORBmatcher.cc:955-1105, NLeft == -1): K is pKF1 (the outer
+// loop), F is pKF2 (the claimed side, vbMatched2), both sides drop features without a good MapPoint (F.good), bestDist1 < TH_LOW is
+// strict (:1054) and the result is indexed by idx1: the claimed-side LDS row is transposed into matches12 [npairs][K.cap] at the end
+// (the output row is filled with -1 first), so no third LDS row is needed.  The fill and the scatter are global stores of different
+// threads of one workgroup: what orders them is that __syncthreads() is a workgroup-scope release / acquire FENCE on global memory as well
+// as a barrier (bow_buckets and the claim phase hold several).  A bare s_barrier builtin in their place would not order them.
+template <bool KF>
 __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSide K, BowSide F, const int* __restrict__ kf_row,
                                                                const int* __restrict__ f_row, float nnratio, int check_ori,
                                                                int* __restrict__ f_match, int* __restrict__ nmatches) {
@@ -2757,12 +2846,15 @@ __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSi
     unsigned short* flist = klist + K.cap;
     unsigned short* row = flist + F.cap;
     const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    int* out = f_match + (size_t)p * F.cap;
+    const int ocap = KF ? K.cap : F.cap;
+    int* out = f_match + (size_t)p * ocap;
     const int kr = kf_row ? kf_row[p] : p, fr = f_row ? f_row[p] : p;
-    if (kr < 0 || kr >= K.nrows || fr < 0 || fr >= F.nrows) {              // (block-uniform) an empty row
-        for (int j = tid; j < F.cap; j += BOW_WAVES * 64) out[j] = -1;
-        if (tid == 0) nmatches[p] = 0;
-        return;
+    if (KF || kr < 0 || kr >= K.nrows || fr < 0 || fr >= F.nrows) {        // (block-uniform) an empty row; M8 scatters into it below
+        for (int j = tid; j < ocap; j += BOW_WAVES * 64) out[j] = -1;
+        if (kr < 0 || kr >= K.nrows || fr < 0 || fr >= F.nrows) {
+            if (tid == 0) nmatches[p] = 0;
+            return;
+        }
     }
     const size_t ko = (size_t)kr * K.cap, fo = (size_t)fr * F.cap;
     const int nk = min(max(K.counts[kr], 0), K.cap), nf = min(max(F.counts[fr], 0), F.cap);
@@ -2805,7 +2897,7 @@ __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSi
                 if (m1 == INV) continue;
                 const unsigned m2 = wave_min_u32(b1 == m1 ? b2 : b1);       // the winner's lane offers its runner-up
                 const int d1 = (int)(m1 >> 16), d2 = m2 == INV ? 256 : (int)(m2 >> 16);
-                if (d1 <= 50 && (float)d1 < nnratio * (float)d2) {           // TH_LOW, :436-442
+                if ((KF ? d1 < 50 : d1 <= 50) && (float)d1 < nnratio * (float)d2) {   // TH_LOW, :436-442; strict for M8, :1054
                     if (lane == 0) row[flist[fs + (m1 & 0xFFFFu)]] = (unsigned short)(i + 1);
                     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                     __builtin_amdgcn_wave_barrier();
@@ -2844,7 +2936,8 @@ __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSi
     for (int j0 = w * 64; j0 < F.cap; j0 += BOW_WAVES * 64) {
         const int j = j0 + lane;
         const int v = j < F.cap ? (int)row[j] : 0;
-        if (j < F.cap) out[j] = v - 1;
+        if (KF) { if (v) out[v - 1] = j; }                                   // vpMatches12[idx1] = idx2
+        else if (j < F.cap) out[j] = v - 1;
         nm += __popcll(__ballot(v != 0));
     }
     if (lane == 0 && nm) atomicAdd(&red[0], nm);
