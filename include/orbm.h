@@ -544,6 +544,43 @@ int orbm_search_by_projection_sim3_batch_async(orbm_t*, int npairs,
                                                const float* k_host, const float* bounds_host, int th, float ratio_hamming, int proj_form,
                                                const float* scale_factors_host, float log_scale_factor, int nlevels,
                                                int32_t* match, int32_t* nmatches);
+/* orbm_search_for_triangulation_batch_async: M10 SearchForTriangulation_(pKF1, pKF2, vMatchedPairs, bOnlyStereo, bCoarse) --
+ * LocalMapping::CreateNewMapPoints (LocalMapping.cc:492-495, 542-592: the new KeyFrame against its 10 / 20 best covisible neighbours) -- END
+ * TO END on the device for `npairs` (pKF1 row, pKF2 row, F12, epipole) pairs (ORBmatcher.cc:1388-1629), pinhole cameras, Nleft == -1; the
+ * second-camera and non-pinhole paths stay with orbm_search_for_triangulation_gated.  Two pools of rows as in
+ * orbm_search_by_bow_kf_batch_async: pool 1 has nrows1 rows of cap1 slots -- kps1 (mvKeysUn), desc1 [..][32], counts1 [nrows1], node1 /
+ * weight1 (orbm_bow_transform_batch_async over the rows; weight NULL = no stopped word), has_mp1 [nrows1][cap1] (GetMapPoint(idx) != NULL,
+ * per ROW), uright1 [nrows1][cap1] (mvuRight; NULL = no stereo feature) --, pool 2 the same arrays with nrows2 / cap2; a caller with one
+ * pool passes it twice.  Pair p matches row row1[p] of pool 1 (pKF1) against row row2[p] of pool 2 (pKF2); NULL = row p;
+ * CreateNewMapPoints repeats row1.  Per pair geometry is device data the caller computes on the host as the facade's
+ * SearchForTriangulation_ does: F12 [npairs][9] row-major, ep [npairs][2] = pKF2->mpCamera->project(R2w * Cw + t2w); a non-finite epipole
+ * (sideways motion: z == 0) is legal and compares as IEEE does.  Semantics per pair are exactly those of orbm_search_for_triangulation: a
+ * FeatureVector bucket is the features of one node id without the stopped words (weight <= 0), without slots >= count and without
+ * features that have a MapPoint, on both sides; with only_stereo also without non-stereo features (uright < 0).  Per pKF1 feature: dist >
+ * TH_LOW rejects (inclusive bound); where neither feature is stereo, distex^2 + distey^2 < 100 * scale_factors2[kp2.octave] rejects;
+ * Pinhole::epipolarConstrain_ with den == 0 rejecting and dsqr < 3.84 * level_sigma2_2[kp2.octave] compared against the double product,
+ * `coarse` accepts whatever it says; the survivor is the smallest distance among the gate-passing candidates and, on a tie, the LAST in
+ * ascending idx2.  vbMatched2 is not kept by this overload (:1567): several idx1 may share an idx2, features are independent.
+ * check_orientation: rot = angle1 - angle2 (+360 if negative), bin = round(rot * (1.0f / 30)) as written at :1441, bin 30 -> 0, then the
+ * three-maxima cull; a culled idx1 becomes -1 and is not counted.  A pKF2 feature whose octave lies outside [0, nlevels) never matches: the
+ * kernels do not index the level tables with it (the host entry point would).  Outputs (device): matches12 [npairs][cap1] = idx2 or -1
+ * (the row orbm_search_for_triangulation returns, padded with -1 to cap1), nmatches [npairs] = its return value, computed from the
+ * finished row (nothing accumulates across graph replays).  A pair whose row1 or row2 lies outside [0, nrows1) / [0, nrows2) gets an all
+ * -1 row and 0.  The baseline / median-depth tests, the triangulation and AddMapPoint stay with the caller (the
+ * cross-pair rule).  All pointers are device pointers except the *_host tables; enqueue-only: the handle's work buffers (the bucket lists per
+ * pool-2 row) are allocated by the first eager call and reused, so after one eager call of the
+ * same or a smaller shape the call can be captured (orbx_capture_begin) and allocates nothing.  ORBM_E_INVALID: a NULL required array
+ * (the weights, urights and row arrays may be NULL), npairs, nrows1, nrows2, cap1, cap2 or nlevels < 1; ORBM_E_CAPACITY: cap1 or cap2 >
+ * 65535 (16-bit bucket lists), nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_for_triangulation_batch_async(orbm_t*, int npairs,
+                                              int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                              const int32_t* node1, const double* weight1, const uint8_t* has_mp1, const float* uright1,
+                                              int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                              const int32_t* node2, const double* weight2, const uint8_t* has_mp2, const float* uright2,
+                                              const int32_t* row1, const int32_t* row2, const float* F12, const float* ep,
+                                              const float* scale_factors2_host, const float* level_sigma2_2_host, int nlevels,
+                                              int only_stereo, int coarse, int check_orientation,
+                                              int32_t* matches12, int32_t* nmatches);
 
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the

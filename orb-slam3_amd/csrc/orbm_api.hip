@@ -2134,6 +2134,54 @@ int orbm_triangulation_batch_async(orbm_t* m, int npairs, int cap,
     return ORBM_OK;
 }
 
+int orbm_search_for_triangulation_batch_async(orbm_t* m, int npairs,
+                                              int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                              const int32_t* node1, const double* weight1, const uint8_t* has_mp1, const float* uright1,
+                                              int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                              const int32_t* node2, const double* weight2, const uint8_t* has_mp2, const float* uright2,
+                                              const int32_t* row1, const int32_t* row2, const float* F12, const float* ep,
+                                              const float* scale_factors2_host, const float* level_sigma2_2_host, int nlevels,
+                                              int only_stereo, int coarse, int check_orientation,
+                                              int32_t* matches12, int32_t* nmatches) {
+    if (!m || !kps1 || !desc1 || !counts1 || !node1 || !has_mp1 || !kps2 || !desc2 || !counts2 || !node2 || !has_mp2 || !F12 || !ep ||
+        !scale_factors2_host || !level_sigma2_2_host || !matches12 || !nmatches) {
+        set_merr("SearchForTriangulation batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nrows1 < 1 || nrows2 < 1 || cap1 < 1 || cap2 < 1 || nlevels < 1) {
+        set_merr("SearchForTriangulation batch: npairs, nrows1, nrows2, cap1, cap2 and nlevels must be >= 1");
+        return ORBM_E_INVALID;
+    }
+    if (cap1 > 65535 || cap2 > 65535) { set_merr("SearchForTriangulation batch: cap1 %d / cap2 %d above 65535 (16-bit bucket lists)", cap1, cap2); return ORBM_E_CAPACITY; }
+    if (nlevels > 12) { set_merr("SearchForTriangulation batch: %d pyramid levels (at most 12)", nlevels); return ORBM_E_CAPACITY; }
+    if (npairs > 65535) { set_merr("SearchForTriangulation batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    TriBatchParams P;
+    for (int i = 0; i < 12; ++i) { P.sf2[i] = scale_factors2_host[std::min(i, nlevels - 1)]; P.sigma2[i] = level_sigma2_2_host[std::min(i, nlevels - 1)]; }
+    P.nlevels = nlevels; P.onlyStereo = only_stereo != 0; P.coarse = coarse != 0; P.npairs = npairs;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t bS = pad((size_t)nrows2 * 257 * sizeof(int)), bE = pad((size_t)nrows2 * cap2 * sizeof(uint2));
+    uint8_t* scr = batch_scratch(m, bS + bE);
+    if (!scr) { set_merr("SearchForTriangulation batch: scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bS + bE); return ORBM_E_HIP; }
+    int* bStart = (int*)scr; uint2* bEnt = (uint2*)(scr + bS);
+    const TriSide A{(const KpIn*)kps1, desc1, counts1, node1, weight1, has_mp1, uright1, nrows1, cap1};
+    const TriSide B{(const KpIn*)kps2, desc2, counts2, node2, weight2, has_mp2, uright2, nrows2, cap2};
+    int lpf = 16;                                                            // lanes per pKF1 feature: the measured choice (profiles/NOTES.md); 1 and 4 for A/B runs
+    if (const char* e = ab_env("ORBM_TRI_LPF")) { const int v = atoi(e); if (v == 1 || v == 4) lpf = v; }   // anything else keeps 16: the grid below is sized by lpf
+    MHIPCHK(rec_time(m, m->e0));
+    MHIPCHK(hipMemsetAsync(matches12, 0xFF, sizeof(int32_t) * (size_t)npairs * cap1, m->stream));   // every entry -1
+    hipLaunchKernelGGL(k_trib_buckets, dim3(nrows2), dim3(256), 0, m->stream, B, row2, P, bStart, bEnt);
+    const dim3 grid(((size_t)cap1 * lpf + 255) / 256, npairs);
+#define TRIB_SEARCH(L) hipLaunchKernelGGL(k_trib_search<L>, grid, dim3(256), 0, m->stream, A, B, row1, row2, F12, ep, P, bStart, bEnt, matches12)
+    if (lpf == 1) TRIB_SEARCH(1); else if (lpf == 4) TRIB_SEARCH(4); else TRIB_SEARCH(16);
+#undef TRIB_SEARCH
+    hipLaunchKernelGGL(k_trib_tail, dim3(npairs), dim3(256), 0, m->stream, A, B, row1, row2, check_orientation, matches12, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 // ---- SURVEY 8(f).2 / 8(f).3 ------------------------------------------------------------------------------
 static bool fill_undist(UndistParams& P, const float* k, const float* dist, int ndist, const float* newk) {
     for (double& d : P.k) d = 0.0;

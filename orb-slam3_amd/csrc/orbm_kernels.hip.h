@@ -2946,6 +2946,176 @@ __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSi
 }
 
 // ------------------------------------------------------------------------------------------------
+// M10 SearchForTriangulation_ (ORBmatcher.cc:1388-1629; pinhole, Nleft == -1) for a batch of (pKF1 row, pKF2 row, F12, epipole) pairs:
+// orbm_search_for_triangulation_batch_async.  LocalMapping::CreateNewMapPoints is one pKF1 row against 10-20 neighbour rows, each with
+// its own geometry, and most features of a real KeyFrame already hold a MapPoint and are skipped on both sides (:1456-1462, :1487-1491).
+//  - k_trib_buckets, one workgroup per pool-2 ROW that some pair names: the (node & 255) lists of k_tri_buckets with every per-feature
+//    filter folded in -- slots >= count, stopped words, features with a MapPoint, non-stereo features under only_stereo and octaves
+//    outside [0, nlevels) are not listed, so the search reads none of those arrays and never indexes the level tables out of range.
+//    An entry is (idx2 | stereo2 << 16, node id): the search needs nothing else of a candidate before its descriptor.
+//  - k_trib_search: LPF lanes per pKF1 feature (16: profiles/NOTES.md; one thread per feature spends its time on the chain of dependent
+//    loads, and compacting the features that search at all first gained nothing) walk its bucket LPF candidates at a time; a feature
+//    beyond the count, with a stopped word, with a MapPoint or, under only_stereo, without a stereo match leaves at once; the survivor is the minimum of
+//    (dist << 16 | 0xFFFF - idx2) over the gate-passing candidates -- the smallest distance and, on ties, the LAST idx2, which is what
+//    the reference's `dist > TH_LOW || dist > bestDist` walk keeps.  F12 and the epipole are read per pair from memory.  The output
+//    rows are -1 beforehand (a memset node); only matches are written.
+//  - k_trib_tail, one workgroup per pair: the orientation check (rot = angle1 - angle2, factor 1.0f / HISTO_LENGTH as written at
+//    :1441, so only bins 0..12 occur; three_maxima; the other bins' matches become -1) and the count, computed from the finished row:
+//    nothing accumulates across launches.
+// ------------------------------------------------------------------------------------------------
+struct TriSide {                                           // one pool: rows of cap slots
+    const KpIn* kps; const uint8_t* desc; const int* counts; const int* node; const double* weight; const uint8_t* has_mp; const float* ur;
+    int nrows, cap;
+};
+struct TriBatchParams { float sf2[12], sigma2[12]; int nlevels, onlyStereo, coarse, npairs; };
+
+// does some pair name row r? (whole workgroup; rows == NULL: pair p names row p)
+__device__ __forceinline__ bool trib_named(const int* __restrict__ rows, int npairs, int r) {
+    if (!rows) return r < npairs;
+    int hit = 0;
+    for (int p = threadIdx.x; p < npairs; p += 256) hit |= rows[p] == r;
+    return __syncthreads_or(hit) != 0;
+}
+__device__ __forceinline__ bool trib_searches(const TriSide& s, size_t o, int i, int onlyStereo) {
+    return (!s.weight || s.weight[o + i] > 0) && !s.has_mp[o + i] && !(onlyStereo && !(s.ur && s.ur[o + i] >= 0));
+}
+
+__global__ __launch_bounds__(256) void k_trib_buckets(TriSide S, const int* __restrict__ row2, TriBatchParams P,
+                                                      int* __restrict__ bStart, uint2* __restrict__ bEnt) {
+    __shared__ int hist[257], cur[256];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (!trib_named(row2, P.npairs, r)) return;
+    const size_t o = (size_t)r * S.cap;
+    const int n = min(max(S.counts[r], 0), S.cap);
+    auto listed = [&](int i) { return trib_searches(S, o, i, P.onlyStereo) && (unsigned)S.kps[o + i].octave < (unsigned)P.nlevels; };
+    hist[tid] = 0; if (tid == 0) hist[256] = 0;
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) if (listed(i)) atomicAdd(&hist[S.node[o + i] & 255], 1);
+    __syncthreads();
+    if (tid < 64) {
+        int carry = 0;
+        for (int b0 = 0; b0 < 256; b0 += 64) {
+            const int v = hist[b0 + tid];
+            int tot;
+            const int ex = wave_excl_scan(v, &tot);
+            hist[b0 + tid] = carry + ex;
+            carry += tot;
+        }
+        if (tid == 0) hist[256] = carry;
+    }
+    __syncthreads();
+    bStart[(size_t)r * 257 + tid] = hist[tid]; if (tid == 0) bStart[(size_t)r * 257 + 256] = hist[256];
+    cur[tid] = hist[tid];
+    __syncthreads();
+    for (int i = tid; i < n; i += 256)
+        if (listed(i)) {
+            const int nd = S.node[o + i];
+            const unsigned st = S.ur && S.ur[o + i] >= 0 ? 0x10000u : 0u;
+            bEnt[o + atomicAdd(&cur[nd & 255], 1)] = make_uint2((unsigned)i | st, (unsigned)nd);
+        }
+}
+
+template <int LPF>
+__global__ __launch_bounds__(256) void k_trib_search(TriSide A, TriSide B, const int* __restrict__ row1, const int* __restrict__ row2,
+                                                     const float* __restrict__ F12, const float* __restrict__ ep, TriBatchParams P,
+                                                     const int* __restrict__ bStart, const uint2* __restrict__ bEnt,
+                                                     int* __restrict__ matches12) {
+    const int p = blockIdx.y;
+    const int r1 = row1 ? row1[p] : p, r2 = row2 ? row2[p] : p;
+    if (r1 < 0 || r1 >= A.nrows || r2 < 0 || r2 >= B.nrows) return;          // (block-uniform) the row stays -1
+    const int i1 = (blockIdx.x * 256 + threadIdx.x) / LPF, sub = threadIdx.x % LPF;
+    const size_t o1 = (size_t)r1 * A.cap, o2 = (size_t)r2 * B.cap;
+    if (i1 >= min(A.counts[r1], A.cap) || !trib_searches(A, o1, i1, P.onlyStereo)) return;   // uniform over the LPF lanes of a feature
+    const KpIn kp1 = A.kps[o1 + i1];
+    const int nd = A.node[o1 + i1];
+    const bool bStereo1 = A.ur && A.ur[o1 + i1] >= 0;
+    u64 a[4];
+    load_desc(A.desc + (o1 + i1) * 32, a);
+    const float* F = F12 + (size_t)p * 9;
+    const float epx = ep[2 * p], epy = ep[2 * p + 1];
+    // the epipolar line of kp1 in image 2 (Pinhole::epipolarConstrain_, Pinhole.cpp:281-287)
+    const float la = kp1.x * F[0] + kp1.y * F[3] + F[6];
+    const float lb = kp1.x * F[1] + kp1.y * F[4] + F[7];
+    const float lc = kp1.x * F[2] + kp1.y * F[5] + F[8];
+    const float den = la * la + lb * lb;
+    const int c0 = bStart[(size_t)r2 * 257 + (nd & 255)], c1 = bStart[(size_t)r2 * 257 + (nd & 255) + 1];
+    unsigned int best = 0xFFFFFFFFu;
+    for (int ci = c0 + sub; ci < c1; ci += LPF) {
+        const uint2 e = bEnt[o2 + ci];
+        if ((int)e.y != nd) continue;
+        const int i2 = (int)(e.x & 0xFFFFu);
+        u64 b[4];
+        load_desc(B.desc + (o2 + i2) * 32, b);
+        const int d = ham256(a, b[0], b[1], b[2], b[3]);
+        if (d > 50) continue;                                                // TH_LOW, inclusive
+        const KpIn kp2 = B.kps[o2 + i2];                                     // its octave is inside [0, nlevels): k_trib_buckets
+        if (!bStereo1 && !(e.x >> 16)) {
+            const float distex = epx - kp2.x, distey = epy - kp2.y;          // a non-finite epipole compares as IEEE does: never closer
+            if (distex * distex + distey * distey < 100 * P.sf2[kp2.octave]) continue;
+        }
+        bool epi = false;
+        if (den != 0) {
+            const float num = la * kp2.x + lb * kp2.y + lc;
+            const float dsqr = num * num / den;
+            epi = (double)dsqr < 3.84 * (double)P.sigma2[kp2.octave];         // float compared with the double product, as written (Pinhole.cpp:295)
+        }
+        if (epi || P.coarse) best = min(best, ((unsigned)d << 16) | (0xFFFFu - (unsigned)i2));
+    }
+#pragma unroll
+    for (int s = LPF >> 1; s > 0; s >>= 1) best = min(best, (unsigned)__shfl_xor((int)best, s));
+    if (sub == 0 && best != 0xFFFFFFFFu) matches12[(size_t)p * A.cap + i1] = (int)(0xFFFFu - (best & 0xFFFFu));
+}
+
+__global__ __launch_bounds__(256) void k_trib_tail(TriSide A, TriSide B, const int* __restrict__ row1, const int* __restrict__ row2,
+                                                   int check_ori, int* __restrict__ matches12, int* __restrict__ nmatches) {
+    __shared__ unsigned int hist[32];
+    __shared__ int total;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int r1 = row1 ? row1[p] : p, r2 = row2 ? row2[p] : p;
+    if (r1 < 0 || r1 >= A.nrows || r2 < 0 || r2 >= B.nrows) { if (tid == 0) nmatches[p] = 0; return; }
+    const size_t o1 = (size_t)r1 * A.cap, o2 = (size_t)r2 * B.cap;
+    const int n1 = min(max(A.counts[r1], 0), A.cap);
+    int* row = matches12 + (size_t)p * A.cap;
+    if (tid < 32) hist[tid] = 0;
+    if (tid == 0) total = 0;
+    __syncthreads();
+    // rot_cull wants the assignments as a list of (slot | bin << 16) words, which the claim kernels keep in LDS; here the row over cap1
+    // is the only record, so the histogram and the cull are two passes over it around three_maxima.  A bin outside [0, 30) (a NaN
+    // angle; the reference asserts) enters no histogram bin and is never culled: the match stays and is counted, as on the host.
+    const float factor = 1.0f / 30;                                          // 1.0f / HISTO_LENGTH, :1441 (sic)
+    auto bin_of = [&](int i, int j) {
+        float rot = A.kps[o1 + i].angle - B.kps[o2 + j].angle;
+        if (rot < 0.0f) rot += 360.0f;
+        int bin = (int)roundf(rot * factor);
+        if (bin == 30) bin = 0;
+        return bin;
+    };
+    int mine = 0;
+    if (check_ori) {
+        for (int i = tid; i < n1; i += 256) {
+            const int j = row[i];
+            if (j >= 0) { const int bin = bin_of(i, j); if (bin >= 0 && bin < 30) atomicAdd(&hist[bin], 1u); }
+        }
+        __syncthreads();
+        const Max3 m3 = three_maxima(hist);
+        for (int i = tid; i < n1; i += 256) {
+            const int j = row[i];
+            if (j < 0) continue;
+            const int bin = bin_of(i, j);
+            if (bin >= 0 && bin < 30 && bin != m3.i1 && bin != m3.i2 && bin != m3.i3) row[i] = -1;
+            else ++mine;
+        }
+    } else {
+        for (int i = tid; i < n1; i += 256) mine += row[i] >= 0;
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) mine += __shfl_xor(mine, s);
+    if ((tid & 63) == 0 && mine) atomicAdd(&total, mine);
+    __syncthreads();
+    if (tid == 0) nmatches[p] = total;
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_undistort: Frame::UndistortKeyPoints (Frame.cc:924-970) = cv::undistortPoints(K, D, R = I, P = newK), one thread per
 // keypoint, double arithmetic in OpenCV's operation order (5 fixed-point iterations; compiled without contraction).
 // ------------------------------------------------------------------------------------------------
