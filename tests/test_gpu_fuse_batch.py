@@ -133,6 +133,18 @@ class Scenes:
         self.pw, self.normal, self.min_dist, self.max_dist, self.qdesc, self.block = mappoints(lefts, disp, self.sf, rng)
         self.Q = len(self.pw)
 
+    @classmethod
+    def gathered(cls, pkg, m, kps_ptr, desc_ptr, nrows, cap, gs, gi, sf, isg, uright):
+        """A KeyFrame pool the caller laid out and built the grid of (device pointers kps_ptr / desc_ptr of nrows x cap slots, grid
+        buffers gs / gi, host tables sf / isg, host uright [nrows][cap]) in place of the extractor block: every field Call reads."""
+        S = cls.__new__(cls)
+        S.pkg, S.nb, S.L, S.m, S.cap = pkg, nrows, pkg.lib(), m, cap
+        S.r = dict(kps=kps_ptr, desc=desc_ptr)
+        S.gs, S.gi = gs, gi
+        S.sf, S.isg = np.ascontiguousarray(sf, np.float32), np.ascontiguousarray(isg, np.float32)
+        S.uright = np.ascontiguousarray(uright, np.float32); S.d_uright = _dev(pkg, S.uright)
+        return S
+
     def extract(self):
         self.ex.enqueue_device(self.arr, W, H, self.stride, np.zeros(4 * self.nb, np.int32))
 
