@@ -1183,6 +1183,12 @@ int orbm_search_by_projection_batch_async(orbm_t* m, const orbm_kp_t* kps, const
 #endif
     {
         hipLaunchKernelGGL(k_track_pack, dim3((cap + 255) / 256, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, cap, grid_start, grid_idx, t_first, ent);
+#ifdef ORBX_AB
+        if (ab_env("ORBM_TOPK16_V1"))                                       // A/B: descriptors and distances for every grid entry
+            hipLaunchKernelGGL(k_track_topk16_v1, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
+                               grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys);
+        else
+#endif
         hipLaunchKernelGGL(k_track_topk16, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
                            grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys);
     }

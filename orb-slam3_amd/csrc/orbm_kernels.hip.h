@@ -1433,19 +1433,150 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
 // k_track_topk16: the same lists with SIXTEEN lanes per query (four queries per wave).  A mono window (th = 15) holds 6 grid entries at
 // level 0 and ~40 at level 7 (14 on average over a 1000-feature frame), so a wave per query keeps most lanes idle and the kernel is bound
 // by the number of waves it can keep in flight across five dependent round trips.  A lane owns entries t = base + 16 j + l (j < NJ <= 4:
-// up to 64 entries per query and pass); column ranges sit in LDS (row-local prefix sums by DPP row_shr); the eight best come from
-// row-wide minimum reductions (DPP row_ror) whose winner writes its own word to the LDS list -- or, with one entry per lane, from
-// each lane counting the smaller keys of its row -- and later passes (windows of more than 64 grid entries) feed the list back in as
-// one more key per lane.  The pass body is BRANCH-FREE per NJ (inactive entries read row 0 instead of being predicated off), so that
-// the NJ loads of every step are in flight together; consecutive queries sit on the same pyramid level (similar windows), so NJ is
-// chosen per wave.
+// up to 64 entries per query and pass); column ranges sit in LDS (row-local prefix sums by DPP row_shr); the entries that pass the
+// level and window tests are packed to one per lane before their descriptors are read (tk16_pass); the eight best come from each
+// lane counting the smaller keys of its row (DPP row_ror), and later passes (windows of more than 64 grid entries) and further
+// rounds (rows of more than 16 candidates) merge into the LDS list by row-wide minimum reductions whose winner writes its own word,
+// the list competing as one more key per lane.  The record loads are BRANCH-FREE per NJ (inactive entries read row 0 instead of
+// being predicated off), so that the NJ loads of a pass are in flight together; consecutive queries sit on the same pyramid level
+// (similar windows), so NJ is chosen per wave.
 struct Tk16 {
     const uint4* ent; const uint8_t* dt; int cap;
     float x, y, r, qangle, factor; int minLevel, maxLevel;
     int total, ncols, qr, l16, wr;
 };
+// one candidate of a lane: the distance, the rotation bin (ORBmatcher.cc:2596-2603), the key (distance << 16 | position) and the word
+__device__ __forceinline__ void tk16_cand(const Tk16& c, const u64 (&a)[4], const uint4& lo, const uint4& hi, float ang, int k, int pos, bool ok,
+                                          unsigned& key, unsigned& word) {
+    const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32), (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
+    float rot = c.qangle - ang;
+    if (rot < 0.0f) rot += 360.0f;
+    int bin = (int)roundf(rot * c.factor);
+    if (bin == 30) bin = 0;
+    if (bin < 0 || bin >= 30) bin = TK_NOBIN;
+    key = ok ? ((unsigned)d << 16) | (unsigned)pos : 0xFFFFFFFFu;            // positions < 65536 (cap)
+    word = ((unsigned)d << 21) | ((unsigned)bin << 16) | (unsigned)k;
+}
+
+// the row's list so far (one entry in each of its first TK_K lanes: pk, pw) merged with one more candidate per lane (k1, w1): TK_K row-wide
+// minimum reductions, in rank order, whose winner writes its own word to the list
+__device__ __forceinline__ void tk16_merge(const Tk16& c, unsigned k1, unsigned w1, unsigned pk, unsigned pw, uint2 (*sTop)[TK_K]) {
+    const unsigned INV = 0xFFFFFFFFu;
+#pragma unroll
+    for (int i = 0; i < TK_K; ++i) {
+        const unsigned mine = min(k1, pk);
+        const unsigned m = row16_min_u32(mine);
+        if (!__any(m != INV)) break;
+        if (mine == m && m != INV) {                                        // keys are unique (position): exactly one lane of the row
+            sTop[c.qr][i] = make_uint2(m, pk == m ? pw : w1);
+            if (pk == m) pk = INV; else k1 = INV;
+        }
+    }
+}
+
+// A pass FILTERS before it fetches: the level band and the window test need only an entry's 16-byte record, and of a window's entries
+// about a quarter pass them.  So the records are loaded and tested first, the row positions taken from the ballots, and the survivors
+// (keypoint, angle, position) packed through LDS to one per lane -- in visiting order -- before any descriptor is read: one descriptor
+// load, one distance, one rotation bin and one key per LANE instead of one per ENTRY, and no descriptor held in registers per entry.
 template <int NJ, bool FB>
 __device__ __forceinline__ void tk16_pass(const Tk16& c, const u64 (&a)[4], int base, int& cnt, const int2 (*sCol)[64], const int (*sAdj)[64], uint2 (*sK)[16], uint2 (*sTop)[TK_K]) {
+    const unsigned INV = 0xFFFFFFFFu;
+    int t[NJ], eidx[NJ];
+    const int cnt0 = cnt;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) t[j] = base + 16 * j + c.l16;
+    if (!FB) {
+        // first 64 entries of a window: the prologue left (grid position - list position) of every entry in LDS
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) eidx[j] = t[j] < c.total ? t[j] + sAdj[c.qr][t[j]] : 0;
+    } else {
+        // later passes: each entry's column is the last one whose offset is <= t (columns ascending, empty ones share an offset)
+        int off[NJ], j0[NJ];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) { off[j] = 0; j0[j] = 0; }
+        for (int col = 0; __any(col < c.ncols); ++col) {
+            const int2 e = sCol[c.qr][col];
+            const bool in = col < c.ncols;
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) if (in && t[j] >= e.x) { off[j] = e.x; j0[j] = e.y; }
+        }
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) eidx[j] = t[j] < c.total ? j0[j] + (t[j] - off[j]) : 0;
+    }
+    // one 16-byte record per grid entry, in the grid's own order (k_track_pack): (x, y, angle, octave << 16 | keypoint) -- the entry and
+    // its keypoint in ONE load from consecutive addresses instead of an index and three dependent scattered ones
+    int k[NJ];
+    float kx[NJ], ky[NJ], ang[NJ];
+    int oct[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        const uint4 e = c.ent[eidx[j]];
+        kx[j] = __uint_as_float(e.x); ky[j] = __uint_as_float(e.y); ang[j] = __uint_as_float(e.z);
+        oct[j] = (int)(e.w >> 16); k[j] = (int)(e.w & 0xFFFFu);
+    }
+    const unsigned below = (1u << c.l16) - 1u;
+    bool ok[NJ];
+    int posj[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+        ok[j] = t[j] < c.total && !(oct[j] < c.minLevel) && !(oct[j] > c.maxLevel) && (fabsf(kx[j] - c.x) < c.r && fabsf(ky[j] - c.y) < c.r);   // bCheckLevels is true here
+        const unsigned rowbits = (unsigned)(__ballot(ok[j]) >> (16 * c.wr)) & 0xFFFFu;
+        posj[j] = cnt + __popc(rowbits & below);
+        cnt += __popc(rowbits);
+    }
+    // rounds of 16 survivors per row, one per lane.  The rule is ONE round; a wave in which some row has more than 16 survivors (many
+    // same-level keypoints inside one window) takes more, and every round after a window's first merges into the list like a later pass
+    const int nv = cnt - cnt0;
+#pragma unroll
+    for (int r = 0; r < NJ; ++r) {
+        if (r > 0 && !__any(nv > 16 * r)) break;
+        bool ok1 = ok[0];
+        int k1 = k[0], pos1 = posj[0];
+        float ang1 = ang[0];
+        if (NJ > 1) {
+#pragma unroll
+            for (int j = 0; j < NJ; ++j) {
+                const int rel = posj[j] - cnt0 - 16 * r;
+                if (ok[j] && (unsigned)rel < 16u) sK[c.qr][rel] = make_uint2(((unsigned)posj[j] << 16) | (unsigned)k[j], __float_as_uint(ang[j]));
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_wave_barrier();
+            const uint2 e = sK[c.qr][c.l16];
+            ok1 = 16 * r + c.l16 < nv; k1 = (int)(e.x & 0xFFFFu); pos1 = (int)(e.x >> 16); ang1 = __uint_as_float(e.y);
+        }
+        const uint4* tp = (const uint4*)(c.dt + (size_t)(ok1 ? k1 : 0) * 32);   // unconditional: a lane without a survivor reads row 0
+        const uint4 lo = tp[0], hi = tp[1];
+        unsigned key, word;
+        tk16_cand(c, a, lo, hi, ang1, k1, pos1, ok1, key, word);
+        if (!FB && r == 0) {
+            // the list is empty: each lane's rank is the number of smaller keys in its row (15 rotations; keys are unique by position)
+            int rank = 0;
+            unsigned rk = key;
+#pragma unroll
+            for (int i = 0; i < 15; ++i) {
+                rk = (unsigned)__builtin_amdgcn_update_dpp((int)rk, (int)rk, 0x121, 0xf, 0xf, false);   // row_ror:1
+                rank += rk < key ? 1 : 0;
+            }
+            if (key != INV && rank < TK_K) sTop[c.qr][rank] = make_uint2(key, word);
+        } else {
+            unsigned pk = INV, pw = INV;
+            if (c.l16 < TK_K) { const uint2 pv = sTop[c.qr][c.l16]; pk = pv.x; pw = pv.y; }   // the list so far competes again
+            tk16_merge(c, key, word, pk, pw, sTop);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // (the next round or pass reads the list and writes sK)
+        __builtin_amdgcn_wave_barrier();
+    }
+}
+struct Tk16Filter {
+    template <int NJ, bool FB>
+    static __device__ __forceinline__ void run(const Tk16& c, const u64 (&a)[4], int base, int& cnt, const int2 (*sCol)[64], const int (*sAdj)[64], uint2 (*sK)[16], uint2 (*sTop)[TK_K]) {
+        tk16_pass<NJ, FB>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+    }
+};
+
+#ifdef ORBX_AB   /* A/B reference (descriptors and distances for every grid entry of the window), not in the product library */
+template <int NJ, bool FB>
+__device__ __forceinline__ void tk16_pass_v1(const Tk16& c, const u64 (&a)[4], int base, int& cnt, const int2 (*sCol)[64], const int (*sAdj)[64], uint2 (*sK)[16], uint2 (*sTop)[TK_K]) {
     const unsigned INV = 0xFFFFFFFFu;
     int t[NJ], eidx[NJ];
     const int cnt0 = cnt;
@@ -1552,6 +1683,13 @@ __device__ __forceinline__ void tk16_pass(const Tk16& c, const u64 (&a)[4], int 
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
 }
+struct Tk16FetchAll {
+    template <int NJ, bool FB>
+    static __device__ __forceinline__ void run(const Tk16& c, const u64 (&a)[4], int base, int& cnt, const int2 (*sCol)[64], const int (*sAdj)[64], uint2 (*sK)[16], uint2 (*sTop)[TK_K]) {
+        tk16_pass_v1<NJ, FB>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+    }
+};
+#endif  /* ORBX_AB */
 
 // k_track_pack: the searched frames' grid entries as 16-byte records in grid order (see tk16_pass)
 __global__ __launch_bounds__(256) void k_track_pack(const KpIn* __restrict__ kps, int cap, const int* __restrict__ grid_start,
@@ -1565,11 +1703,13 @@ __global__ __launch_bounds__(256) void k_track_pack(const KpIn* __restrict__ kps
     ent[(size_t)pair * cap + pos] = make_uint4(__float_as_uint(kp.x), __float_as_uint(kp.y), __float_as_uint(kp.angle), ((unsigned)kp.octave << 16) | (unsigned)k);
 }
 
-__global__ __launch_bounds__(256) void k_track_topk16(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                                      const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
-                                                      const uint4* __restrict__ ent, float min_x, float min_y, float inv_w, float inv_h,
-                                                      int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
-                                                      int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys) {
+// the kernel's body; Pass: how a pass of up to 64 entries per query turns into candidates (Tk16Filter; the A/B build also has Tk16FetchAll)
+template <class Pass>
+__device__ __forceinline__ void tk16_body(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
+                                          const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
+                                          const uint4* __restrict__ ent, float min_x, float min_y, float inv_w, float inv_h,
+                                          int q_first, int t_first, float th, const ScaleTab& st, float dx, float dy, float factor,
+                                          int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys) {
     __shared__ int2 sCol[16][64];                                           // per query: (offset in the flattened list, first grid entry) of each window column
     __shared__ uint2 sTop[16][TK_K];                                        // per query: (distance << 16 | position, output word), ascending
     __shared__ int sAdj[16][64];                                            // per query: grid position - list position of the first 64 window entries
@@ -1628,13 +1768,13 @@ __global__ __launch_bounds__(256) void k_track_topk16(const KpIn* __restrict__ k
     for (int base = 0; base < maxTotal; base += 64) {
         const int nj = min(4, (maxTotal - base + 15) >> 4);                 // wave-uniform
         if (base == 0) {
-            if (nj == 1) tk16_pass<1, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
-            else if (nj == 2) tk16_pass<2, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
-            else if (nj == 3) tk16_pass<3, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
-            else tk16_pass<4, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            if (nj == 1) Pass::template run<1, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            else if (nj == 2) Pass::template run<2, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            else if (nj == 3) Pass::template run<3, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            else Pass::template run<4, false>(c, a, base, cnt, sCol, sAdj, sK, sTop);
         } else {
-            if (nj <= 2) tk16_pass<2, true>(c, a, base, cnt, sCol, sAdj, sK, sTop);
-            else tk16_pass<4, true>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            if (nj <= 2) Pass::template run<2, true>(c, a, base, cnt, sCol, sAdj, sK, sTop);
+            else Pass::template run<4, true>(c, a, base, cnt, sCol, sAdj, sK, sTop);
         }
     }
     if (live) {
@@ -1643,6 +1783,18 @@ __global__ __launch_bounds__(256) void k_track_topk16(const KpIn* __restrict__ k
         if (l16 < TK_K) { const uint2 e = sTop[qr][l16]; out_keys[o * TK_K + l16] = e.x == INV ? INV : e.y; }
     }
 }
+
+#define TK16_PARAMS const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,                 \
+                    const int* __restrict__ grid_start, const uint4* __restrict__ ent, float min_x, float min_y, float inv_w, float inv_h,    \
+                    int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor, int* __restrict__ out_cnt,             \
+                    unsigned int* __restrict__ out_keys
+#define TK16_ARGS kps, desc, counts, cap, grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, out_cnt, out_keys
+__global__ __launch_bounds__(256) void k_track_topk16(TK16_PARAMS) { tk16_body<Tk16Filter>(TK16_ARGS); }
+#ifdef ORBX_AB   /* A/B reference, not in the product library */
+__global__ __launch_bounds__(256) void k_track_topk16_v1(TK16_PARAMS) { tk16_body<Tk16FetchAll>(TK16_ARGS); }
+#endif
+#undef TK16_PARAMS
+#undef TK16_ARGS
 
 #ifdef ORBX_AB   /* A/B reference (eight queries per step), not in the product library */
 __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
