@@ -581,6 +581,52 @@ int orbm_search_for_triangulation_batch_async(orbm_t*, int npairs,
                                               const float* scale_factors2_host, const float* level_sigma2_2_host, int nlevels,
                                               int only_stereo, int coarse, int check_orientation,
                                               int32_t* matches12, int32_t* nmatches);
+/* orbm_search_for_initialization_batch_async: M9 SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize) --
+ * Tracking::MonocularInitialization (Tracking.cc:2684-2688: the initial frame against the current one, window 100, nnratio 0.9, orientation
+ * checked) -- END TO END on the device for `npairs` (initial frame row, current frame row, vbPrevMatched row) triples
+ * (ORBmatcher.cc:799-943).  Two pools of rows as in orbm_search_for_triangulation_batch_async: pool 1 (initial frames) has nrows1 rows of
+ * cap1 slots -- kps1 (mvKeysUn), desc1 [..][32], counts1 [nrows1] --, pool 2 (current frames) the same arrays with nrows2 / cap2 plus the grid
+ * of orbm_grid_build_batch_async over the pool (grid_start [nrows2][3073], grid_idx [nrows2][cap2], indexed by row; min_x, min_y, inv_w,
+ * inv_h as given there): the grid is how the search reaches a slot, so slots at or beyond a row's count are never read.  An extractor
+ * result block is a valid pool; a caller with one pool passes it twice.  Pair p matches row row1[p] of pool 1 against row row2[p] of pool
+ * 2; NULL = row p.  prev_in [npairs][cap1][2] is vbPrevMatched of pair p (x, y per F1 keypoint; after Tracking.cc:2635-2637 the initial
+ * frame's own mvKeysUn[i].pt).  Semantics per pair are exactly those of orbm_search_for_initialization, line for line :799-943:
+ *  - level-0 rule: only F1 keypoints with octave == 0 search (:825 skips level1 > 0), and they see only octave == 0 slots of F2:
+ *    GetFeaturesInArea(prev.x, prev.y, window_size, 0, 0) checks the levels, walks the grid cells column-major and a cell's slots in
+ *    insertion order, and keeps |dx| < window_size and |dy| < window_size, both strict.  (An octave below 0 searches every level, as the
+ *    generic level rule of Frame.cc:828 says; no extractor produces one.)
+ *  - the vMatchedDistance skip: a candidate whose slot is already claimed at a distance <= this one is passed over (:853), BEFORE best
+ *    and second are updated, so a query may accept its second-nearest slot; best and second use strict <, the first candidate of least
+ *    distance in visiting order wins; accepted when bestDist <= TH_LOW and bestDist < (float)bestDist2 * nnratio (float32 product,
+ *    bestDist2 = INT_MAX without a second).  A claim of an owned slot is a steal: the former owner's vnMatches12 becomes -1 (:876-880).
+ *  - the robbed-entry histogram rule: with check_orientation, rot = angle1 - angle2 (+360 if negative), bin = round(rot * (30 / 360.0f)),
+ *    bin 30 -> 0, is counted WHEN THE CLAIM IS MADE and never taken back -- rotHist keeps a query that was robbed later (:902) -- so
+ *    ComputeThreeMaxima sees bin sizes that cannot be recomputed from the finished row; culling a robbed entry does not count down a
+ *    second time (:926).  A bin outside [0, 30) (a NaN angle; the reference asserts) is neither counted nor culled.
+ * Outputs (device): matches12 [npairs][cap1] = vnMatches12 (idx2 or ORBM_NO_MATCH; slots at or beyond the row's count are ORBM_NO_MATCH),
+ * nmatches [npairs] = the return value, prev_out [npairs][cap1][2] = vbPrevMatched after :938-940: entries below the row's count that
+ * ended matched carry the matched F2 keypoint's position, the others carry prev_in's value; entries at or beyond the count are not
+ * written.  In-place prev: prev_out == prev_in is allowed, as the reference updates vbPrevMatched in place -- replaying a captured graph
+ * in place is then NOT idempotent (every replay searches around the last replay's matches, which is what the initialiser wants from frame
+ * to frame); a caller who wants idempotent replays passes two buffers.  Partly overlapping buffers are not allowed.  A pair whose row1 or
+ * row2 lies outside [0, nrows1) / [0, nrows2), or whose row is empty, gets count 0 and an all ORBM_NO_MATCH row.  The decisions around the
+ * search stay with the caller (MonocularInitialization on the device).  All pointers are device pointers; enqueue-only:
+ * the handle's work buffer (the candidate lists of the pairs in flight) is min(npairs, 128) * (cap2 + 262144) * 4 bytes of device memory
+ * -- 1.1 MB per pair in flight at cap2 = 5 000, 68 MB for 64 such pairs, 151 MB at most (128 pairs at the cap) --, grow-only and kept for
+ * the handle's life; it is allocated by the first eager call and reused, so after one eager call of the same or a smaller shape the
+ * call can be captured (orbx_capture_begin) and allocates nothing.  There is no cap on
+ * the candidates of a query: a window that holds every level-0 slot of the row works (the lists are produced and consumed in chunks of
+ * queries).  ORBM_E_INVALID: a NULL required array (row1 / row2 may be NULL), npairs, nrows1, nrows2, cap1 or cap2 < 1, window_size < 0;
+ * ORBM_E_CAPACITY: cap1 or cap2 > ORBM_INIT_MAX_CAP (16-bit owner indices; the claimed row over cap2 takes 4 B per slot of the 160 KB of
+ * LDS), npairs > 65535.  Nothing is enqueued then. */
+enum { ORBM_INIT_MAX_CAP = 32768 };
+int orbm_search_for_initialization_batch_async(orbm_t*, int npairs,
+                                               int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                               int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                               const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                               const int32_t* row1, const int32_t* row2, const float* prev_in,
+                                               int window_size, float nnratio, int check_orientation,
+                                               int32_t* matches12, int32_t* nmatches, float* prev_out);
 
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the

@@ -858,6 +858,11 @@ def _install_search():
                                                             ci, ci, vp, vp, vp, vp, vp, vp, vp,            # pool 2 (pKF2)
                                                             vp, vp, vp, vp, vp, vp, ci,                    # row1, row2, F12, ep, sf2, sigma2, nlevels
                                                             ci, ci, ci, vp, vp]                            # only_stereo, coarse, check_ori, outputs
+    L.orbm_search_for_initialization_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,                  # pairs, pool 1 (initial frames)
+                                                             ci, ci, vp, vp, vp,                          # pool 2 (current frames)
+                                                             vp, vp, cf, cf, cf, cf,                      # its grid, bounds
+                                                             vp, vp, vp, ci, cf, ci,                      # row1, row2, prev_in, window, nnratio, check_ori
+                                                             vp, vp, vp]                                  # matches12, nmatches, prev_out
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -936,7 +941,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
             "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
             "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",
-            "orbm_search_for_triangulation_batch_async", "orbm_search_by_projection_frame_fisheye",
+            "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib

@@ -37,6 +37,7 @@ struct orbm {
     hipStream_t ownStream = nullptr;                           // the stream created with the handle (orbm_set_stream may point `stream` elsewhere)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     bool timed = false, gridFirst = false;
+    bool initLds = false;                                      // k_init_search's dynamic LDS limit has been raised (orbm_search_for_initialization_batch_async)
     // Scratch arena of the single-frame entry points: ONE device block and a pinned host mirror of the same size.  Uploads are
     // staged in the mirror and sent with one asynchronous copy before the kernel, results come back with one copy after it
     // (a dozen hipMalloc / small pageable copies per call cost over a millisecond).
@@ -2182,6 +2183,56 @@ int orbm_search_for_triangulation_batch_async(orbm_t* m, int npairs,
     if (lpf == 1) TRIB_SEARCH(1); else if (lpf == 4) TRIB_SEARCH(4); else TRIB_SEARCH(16);
 #undef TRIB_SEARCH
     hipLaunchKernelGGL(k_trib_tail, dim3(npairs), dim3(256), 0, m->stream, A, B, row1, row2, check_orientation, matches12, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
+int orbm_search_for_initialization_batch_async(orbm_t* m, int npairs,
+                                               int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
+                                               int nrows2, int cap2, const orbm_kp_t* kps2, const uint8_t* desc2, const int32_t* counts2,
+                                               const int32_t* grid_start, const int32_t* grid_idx, float min_x, float min_y, float inv_w, float inv_h,
+                                               const int32_t* row1, const int32_t* row2, const float* prev_in,
+                                               int window_size, float nnratio, int check_orientation,
+                                               int32_t* matches12, int32_t* nmatches, float* prev_out) {
+    if (!m || !kps1 || !desc1 || !counts1 || !kps2 || !desc2 || !counts2 || !grid_start || !grid_idx || !prev_in || !matches12 || !nmatches || !prev_out) {
+        set_merr("SearchForInitialization batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nrows1 < 1 || nrows2 < 1 || cap1 < 1 || cap2 < 1 || window_size < 0) {
+        set_merr("SearchForInitialization batch: npairs, nrows1, nrows2, cap1 and cap2 must be >= 1, window_size >= 0");
+        return ORBM_E_INVALID;
+    }
+    if (cap1 > ORBM_INIT_MAX_CAP || cap2 > ORBM_INIT_MAX_CAP) {
+        set_merr("SearchForInitialization batch: cap1 %d / cap2 %d above %d (16-bit owners; the claimed row over cap2 lives in LDS)", cap1, cap2, (int)ORBM_INIT_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (npairs > 65535) { set_merr("SearchForInitialization batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    // candidate lists: per workgroup the first query's region (cap2) + room for the rest of a chunk; no list is capped, a full scratch ends a chunk
+    const int nwg = std::min(npairs, 128);
+    InitParams P{min_x, min_y, inv_w, inv_h, (float)window_size, nnratio, ORBM_HISTO_LENGTH / 360.0f, check_orientation != 0, npairs,
+                 (unsigned)cap2 + (256u << 10)};
+    if (const char* e = ab_env("ORBM_INIT_ROOM")) P.budget = (unsigned)cap2 + (unsigned)std::max(0, atoi(e));   // test knob: a chunk per query at 0
+    const size_t bytes = (size_t)nwg * P.budget * sizeof(unsigned int);
+    uint8_t* scr = batch_scratch(m, bytes);
+    if (!scr) { set_merr("SearchForInitialization batch: scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bytes); return ORBM_E_HIP; }
+    const size_t lds = (size_t)cap2 * sizeof(unsigned int);
+    if (!m->initLds) {                                                       // once per handle, on its first (eager) call: the largest legal size
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(m->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+            set_merr("SearchForInitialization batch: inside a capture, run the call once eagerly first");
+            return ORBM_E_HIP;
+        }
+        MHIPCHK(hipFuncSetAttribute((const void*)k_init_search, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ORBM_INIT_MAX_CAP * sizeof(unsigned int))));
+        m->initLds = true;
+    }
+    const InitSide A{(const KpIn*)kps1, desc1, counts1, nrows1, cap1};
+    const InitSide B{(const KpIn*)kps2, desc2, counts2, nrows2, cap2};
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_init_search, dim3(nwg), dim3(INIT_WAVES * 64), lds, m->stream, A, B, grid_start, grid_idx, row1, row2, prev_in, prev_out, P,
+                       (unsigned int*)scr, matches12, nmatches);
     MHIPCHK(rec_time(m, m->e1));
     MHIPCHK(hipGetLastError());
     m->timed = true;

@@ -3268,6 +3268,204 @@ __global__ __launch_bounds__(256) void k_trib_tail(TriSide A, TriSide B, const i
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_init_search: M9 ORBmatcher::SearchForInitialization (ORBmatcher.cc:799-943) END TO END, one workgroup of INIT_WAVES waves per
+// pair (a persistent grid walks the pairs when there are more pairs than workgroups).
+// The claim loop is sequential in i1 -- which slots earlier queries hold, and at what distance, decides a later query's best and
+// second (:853) -- but the distances are not, so the pair's queries are taken in CHUNKS of up to INIT_CHUNK consecutive i1:
+// 1. candidate pass (all waves, a wave per query): the window's grid columns are flattened as in win_sweep (one column per lane, prefix
+//    sum), every entry is tested (slot < n2, level, strict box) BEFORE its descriptor is fetched, and the survivors are written in grid
+//    order -- the reference's visiting order -- as words dist << 21 | rotation bin << 16 | slot.  There is no cap per query: a query
+//    reserves the population of its window's cells (an upper bound of its list) from the workgroup's scratch, the first query of a chunk
+//    owns a region of cap2 words of its own (a list cannot be longer), and a query that finds the scratch full ends the chunk in front
+//    of itself (sStop) and is searched again by the next chunk.
+// 2. replay (wave 0, queries in order): the lanes share a query's list; a candidate whose slot is held at a lower-or-equal distance is
+//    skipped (:853); the smallest (distance, visiting position) key is "the first of least distance", the smallest key of the others
+//    (the winner's lane offers its runner-up) is bestDist2 of the if / else-if chain.  bestDist <= TH_LOW and bestDist < (float)bestDist2
+//    * nnratio (INT_MAX where there is no second) accept; lane 0 writes vMatchedDistance << 16 | vnMatches21 of the slot into the LDS row
+//    over cap2 -- overwriting the owner IS the steal of :876-880 -- and counts the rotation bin.  The bin counts are taken at claim time
+//    and never reduced: the reference's rotHist keeps a query that was robbed later (:902 is not undone), so ComputeThreeMaxima sees it.
+// 3. tail (all waves): matches12 is the transposed LDS row (filled with -1 before, scattered after); three_maxima on the claim-time
+//    counts; a live entry of another bin is culled, a robbed one has no entry left to cull (:926); the survivors are counted and carry
+//    the matched keypoint's position into prev_out, every other entry below the row's count carries prev_in.
+// Everything is recomputed per launch: nothing accumulates across graph replays.
+// LDS: the row over cap2 (4 B per slot, dynamic) + sQ [INIT_CHUNK] (offset, count) + the histogram.
+// ------------------------------------------------------------------------------------------------
+#define INIT_WAVES 16
+#define INIT_CHUNK 1024
+struct InitSide { const KpIn* kps; const uint8_t* desc; const int* counts; int nrows, cap; };
+struct InitParams { float min_x, min_y, inv_w, inv_h, r, nnratio, factor; int check_ori, npairs; unsigned int budget; };
+
+__global__ __launch_bounds__(INIT_WAVES * 64) void k_init_search(InitSide A, InitSide B, const int* __restrict__ grid_start,
+                                                                const int* __restrict__ grid_idx, const int* __restrict__ row1,
+                                                                const int* __restrict__ row2, const float* prev_in, float* prev_out,
+                                                                InitParams P, unsigned int* scratch, int* matches12, int* __restrict__ nmatches) {
+    extern __shared__ unsigned int sState[];                                 // per slot: vMatchedDistance << 16 | vnMatches21; 0xFFFF = INT_MAX / -1
+    __shared__ int2 sQ[INIT_CHUNK];
+    __shared__ unsigned int sHist[32];
+    __shared__ int sUsed, sStop, sTotal;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int NT = INIT_WAVES * 64;
+    unsigned int* scr = scratch + (size_t)blockIdx.x * P.budget;
+    for (int p = blockIdx.x; p < P.npairs; p += gridDim.x) {
+        const int r1 = row1 ? row1[p] : p, r2 = row2 ? row2[p] : p;
+        const bool ok1 = r1 >= 0 && r1 < A.nrows, ok2 = r2 >= 0 && r2 < B.nrows;
+        const int n1 = ok1 ? min(max(A.counts[r1], 0), A.cap) : 0, n2 = ok2 ? min(max(B.counts[r2], 0), B.cap) : 0;
+        const size_t o1 = (size_t)(ok1 ? r1 : 0) * A.cap, o2 = (size_t)(ok2 ? r2 : 0) * B.cap, op = (size_t)p * A.cap;
+        int* row = matches12 + op;
+        const float* pin = prev_in + 2 * op;
+        float* pout = prev_out + 2 * op;
+        for (int i = tid; i < A.cap; i += NT) row[i] = -1;
+        for (int i = tid; i < 2 * n1; i += NT) pout[i] = pin[i];             // (in place: the same value)
+        if (n1 == 0 || n2 == 0) {                                           // (workgroup-uniform)
+            if (tid == 0) nmatches[p] = 0;
+            continue;
+        }
+        for (int i = tid; i < n2; i += NT) sState[i] = 0xFFFFFFFFu;
+        if (tid < 32) sHist[tid] = 0;
+        if (tid == 0) sTotal = 0;
+        const KpIn* kt = B.kps + o2;
+        const uint8_t* dt = B.desc + o2 * 32;
+        const int* gs = grid_start + (size_t)r2 * (GRID_CELLS + 1);
+        const int* gi = grid_idx + o2;
+        for (int c0 = 0; c0 < n1;) {
+            const int cend = min(c0 + INIT_CHUNK, n1);
+            __syncthreads();                                                // the row is initialised / the last chunk's replay is over
+            if (tid == 0) { sUsed = n2; sStop = cend; }
+            __syncthreads();
+            // ---- 1. candidate pass ----
+            for (int q = c0 + wave; q < cend; q += INIT_WAVES) {
+                if (q >= *(volatile int*)&sStop) break;                     // the chunk already ends in front of this query
+                int2 rec = make_int2(0, 0);
+                const KpIn kq = A.kps[o1 + q];
+                const int lvl = kq.octave;                                  // GetFeaturesInArea(x, y, r, level1, level1)
+                const float x = pin[2 * q], y = pin[2 * q + 1];
+                const int nMinCellX = max(0, (int)floorf((x - P.min_x - P.r) * P.inv_w));
+                const int nMaxCellX = min(63, (int)ceilf((x - P.min_x + P.r) * P.inv_w));
+                const int nMinCellY = max(0, (int)floorf((y - P.min_y - P.r) * P.inv_h));
+                const int nMaxCellY = min(47, (int)ceilf((y - P.min_y + P.r) * P.inv_h));
+                const bool window = lvl <= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX &&
+                                    nMinCellY <= nMaxCellY;                 // :825 level1 > 0 does not search
+                int total = 0, excl = 0, cj0 = 0;
+                const int ncols = nMaxCellX - nMinCellX + 1;
+                if (window) {
+                    int clen = 0;
+                    if (lane < ncols) {
+                        const int ix = nMinCellX + lane;
+                        cj0 = min(max(gs[ix * 48 + nMinCellY], 0), n2);     // (clamped: a foreign grid must not lead outside the row)
+                        clen = min(max(gs[ix * 48 + nMaxCellY + 1], cj0), n2) - cj0;
+                    }
+                    excl = wave_excl_scan(clen, &total);
+                    total = min(total, n2);                                 // columns of a grid built over this row are disjoint: only a foreign grid is cut
+                }
+                bool mine = total > 0;
+                unsigned int off = 0;
+                if (mine && q != c0) {                                      // the chunk's first query owns [0, n2)
+                    if (lane == 0) off = (unsigned)atomicAdd(&sUsed, total);
+                    off = (unsigned)__builtin_amdgcn_readfirstlane((int)off);
+                    if (off + (unsigned)total > P.budget) {
+                        if (lane == 0) atomicMin(&sStop, q);
+                        mine = false;
+                    }
+                }
+                if (mine) {
+                    const bool bCheckLevels = lvl >= 0;                     // (minLevel > 0) || (maxLevel >= 0) with both = level1 <= 0
+                    u64 a[4];
+                    load_desc(A.desc + (o1 + q) * 32, a);
+                    const RotBinPay pay{kq.angle, P.factor};
+                    int cnt = 0;
+                    for (int base = 0; base < total; base += 64) {
+                        const int t = base + lane;
+                        int cs = 0, cb = 0;
+                        for (int c = 0; c < ncols; ++c) {                   // t's column: the last one starting at or before t
+                            const int e = __builtin_amdgcn_readlane(excl, c), s = __builtin_amdgcn_readlane(cj0, c);
+                            if (t >= e) { cs = e; cb = s; }
+                        }
+                        bool ok = false;
+                        unsigned int word = 0;
+                        if (t < total) {
+                            const int k = gi[cb + (t - cs)];
+                            if ((unsigned)k < (unsigned)n2) {
+                                const KpIn kp = kt[k];
+                                ok = (!bCheckLevels || kp.octave == lvl) && fabsf(kp.x - x) < P.r && fabsf(kp.y - y) < P.r;
+                                if (ok) {
+                                    u64 b[4];
+                                    load_desc(dt + (size_t)k * 32, b);
+                                    word = ((unsigned)ham256(a, b[0], b[1], b[2], b[3]) << 21) | (pay(kp) << 16) | (unsigned)k;
+                                }
+                            }
+                        }
+                        const u64 bal = __ballot(ok);
+                        if (ok) scr[off + cnt + bow_rank(bal)] = word;
+                        cnt += __popcll(bal);
+                    }
+                    rec = make_int2((int)off, cnt);
+                }
+                if (lane == 0) sQ[q - c0] = rec;
+            }
+            __syncthreads();
+            const int stop = sStop;                                         // > c0: the first query never waits for room
+            // ---- 2. replay ----
+            if (wave == 0) {
+                for (int qb = c0; qb < stop; qb += 64) {
+                    const int2 oc = qb + lane < stop ? sQ[qb + lane - c0] : make_int2(0, 0);
+                    u64 live = __ballot(oc.y > 0);
+                    while (live) {
+                        const int l = __builtin_ctzll(live);
+                        live &= live - 1;
+                        const unsigned int off = (unsigned)__builtin_amdgcn_readlane(oc.x, l);
+                        const int cnt = __builtin_amdgcn_readlane(oc.y, l), i1 = qb + l;
+                        unsigned int b1 = 0xFFFFFFFFu, b2 = 0xFFFFFFFFu, e1 = 0;
+                        for (int pos = lane; pos < cnt; pos += 64) {
+                            const unsigned int e = scr[off + pos];
+                            const unsigned int d = e >> 21;
+                            if ((sState[e & 0xFFFFu] >> 16) <= d) continue;  // :853 vMatchedDistance[i2] <= dist
+                            const unsigned int key = (d << 16) | (unsigned)pos;
+                            if (key < b1) { b2 = b1; b1 = key; e1 = e; }
+                            else if (key < b2) b2 = key;
+                        }
+                        const unsigned int m1 = wave_min_u32(b1);
+                        if (m1 == 0xFFFFFFFFu) continue;                    // every candidate skipped
+                        const unsigned int m2 = wave_min_u32(b1 == m1 ? b2 : b1);
+                        const int bestDist = (int)(m1 >> 16), bestDist2 = m2 == 0xFFFFFFFFu ? INT_MAX : (int)(m2 >> 16);
+                        if (bestDist <= 50 && (float)bestDist < (float)bestDist2 * P.nnratio) {      // :870, :873
+                            const unsigned int e = (unsigned)__builtin_amdgcn_readlane((int)e1, __builtin_ctzll(__ballot(b1 == m1)));
+                            const unsigned int bin = (e >> 16) & 31u;
+                            if (lane == 0) {
+                                sState[e & 0xFFFFu] = ((unsigned)bestDist << 16) | (unsigned)i1;
+                                if (P.check_ori && bin < 30u) sHist[bin] += 1;
+                            }
+                        }
+                    }
+                }
+            }
+            c0 = stop;
+        }
+        __syncthreads();
+        // ---- 3. tail ----
+        const Max3 m3 = three_maxima(sHist);
+        int kept = 0;
+        for (int k = tid; k < n2; k += NT) {
+            const unsigned int i1 = sState[k] & 0xFFFFu;
+            if (i1 == 0xFFFFu) continue;
+            const KpIn kp2 = kt[k];
+            if (P.check_ori) {
+                const int bin = (int)RotBinPay{A.kps[o1 + i1].angle, P.factor}(kp2);
+                if (bin < 30 && bin != m3.i1 && bin != m3.i2 && bin != m3.i3) continue;   // culled (:926-930)
+            }
+            row[i1] = k;
+            pout[2 * i1] = kp2.x; pout[2 * i1 + 1] = kp2.y;                  // :938-940
+            ++kept;
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1) kept += __shfl_xor(kept, s);
+        if (lane == 0 && kept) atomicAdd(&sTotal, kept);
+        __syncthreads();
+        if (tid == 0) nmatches[p] = sTotal;
+        __syncthreads();                                                    // sTotal and the row are reused by the next pair
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // k_undistort: Frame::UndistortKeyPoints (Frame.cc:924-970) = cv::undistortPoints(K, D, R = I, P = newK), one thread per
 // keypoint, double arithmetic in OpenCV's operation order (5 fixed-point iterations; compiled without contraction).
 // ------------------------------------------------------------------------------------------------
