@@ -628,6 +628,64 @@ int orbm_search_for_initialization_batch_async(orbm_t*, int npairs,
                                                int window_size, float nnratio, int check_orientation,
                                                int32_t* matches12, int32_t* nmatches, float* prev_out);
 
+/* ---- RGB-D frames (the third sensor family: Frame's RGB-D constructor, Frame.cc:228-314).
+ * orbm_stereo_from_rgbd / orbm_stereo_from_rgbd_batch_async: Frame::ComputeStereoFromRGBD (Frame.cc:1279-1309) with
+ * Tracking::GrabImageRGBD's imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) (Tracking.cc:1353-1354) folded into the sample: the
+ * caller passes the UNCONVERTED depth image and mDepthMapFactor; only the pixels under keypoints are read, and converting one pixel gives
+ * the value converting the image gives.  Per keypoint i, line for line :1288-1308:
+ *  - Pixel: row = (int)kps[i].y, col = (int)kps[i].x -- the float-to-int truncation that imDepth.at<float>(v, u) performs on its float
+ *    arguments (towards zero, so a coordinate in (-1, 0) reads index 0).  kps is mvKeys, the raw keypoints; kps_un is mvKeysUn and may be
+ *    the same array when there is no distortion.  A keypoint whose row or column lies outside the image, or whose coordinate is NaN,
+ *    reads nothing and gets uright = depth = -1; the reference reads out of bounds there.
+ *  - Conversion: the raw pixel is used as it is only when depth_type == ORBM_DEPTH_F32 and fabs(depth_factor - 1.0f) > 1e-5 is false
+ *    (:1353 as written); in every other case d = (float)raw * depth_factor, one float32 multiply without contraction and without an
+ *    offset -- what cv::Mat::convertTo yields for 16U -> 32F and 32F -> 32F with beta == 0.
+ *  - Result: d > 0 gives depth[i] = d and uright[i] = kps_un[i].x - mbf / d (float32 IEEE division, then a float32 subtraction);
+ *    otherwise both are -1.0f: 0, negatives and NaN.  +inf passes: uright = kps_un[i].x.
+ * depth_img / the images: rows of stride_bytes bytes, w x h elements of uint16 (ORBM_DEPTH_U16) or float (ORBM_DEPTH_F32), aligned to the
+ * element; stride_bytes is a multiple of the element size, as every cv::Mat step is.
+ * Host form: host pointers, one frame, synchronous; uright / depth [n]; returns the number of keypoints with depth > 0.
+ * Device form: enqueue-only, all pointers device pointers.  Frame f of the call is block frame first + f of kps, kps_un and counts -- an
+ * extractor result block (orbx_result_device) and the block orbm_undistort_keypoints(ORBM_DEVICE) wrote from it, rows of cap slots.
+ * depth_imgs is a DEVICE array of nframes device pointers: a captured graph follows a caller who rewrites the table (or the pixels)
+ * between replays.  Outputs have one row per frame of the call: uright, depth [nframes][cap], with slots at or beyond the frame's count
+ * written -1 as well, so a row is fully defined; nvalid [nframes] = keypoints with depth > 0.  The rows follow the convention of the
+ * uright that orbm_stereo_batch_async writes: they go straight into orbm_search_by_projection_frame_batch_async (M4, with mbf) and
+ * orbm_search_by_projection_points_batch_async (M3) when t_first == first.  nvalid is computed from the finished row (one workgroup per
+ * frame; ballot, popcount, LDS reduction, one store): nothing accumulates across graph replays and nothing needs a memset.  No scratch:
+ * capturable after one eager call (orbx_capture_begin), as the other batched forms.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL array; nframes, cap, w or h < 1; first < 0; stride_bytes < w * element size or not a
+ * multiple of it; an unknown depth_type; a non-finite depth_factor. */
+enum { ORBM_DEPTH_U16 = 0, ORBM_DEPTH_F32 = 1 };
+int orbm_stereo_from_rgbd(orbm_t*, int n, const orbm_kp_t* kps, const orbm_kp_t* kps_un,
+                          const void* depth_img, int depth_type, int w, int h, int stride_bytes,
+                          float depth_factor, float mbf, float* uright, float* depth);
+int orbm_stereo_from_rgbd_batch_async(orbm_t*, int nframes, int first, int cap,
+                                      const orbm_kp_t* kps, const orbm_kp_t* kps_un, const int32_t* counts,
+                                      const void* const* depth_imgs, int depth_type, int w, int h, int stride_bytes,
+                                      float depth_factor, float mbf,
+                                      float* uright, float* depth, int32_t* nvalid);
+/* orbm_unproject_stereo / orbm_unproject_stereo_batch_async: Frame::UnprojectStereo (Frame.cc:1312-1326) for every keypoint of a frame
+ * -- what StereoInitialization, UpdateLastFrame and CreateNewKeyFrame call per depth point in RGB-D and stereo tracking.  k / k_host =
+ * (fx, fy, cx, cy) on the host; twc is the row-major 3x4 [Rwc | Ow] (mRwc, mOw).  Per slot with z = depth > 0 (:1314-1322): invfx =
+ * 1.0f / fx computed once; x = (u - cx) * z * invfx evaluated left to right in float without contraction, y likewise, (u, v) =
+ * kps_un.pt; x3Dw[r] = (float)(double sum over k of Rwc[r][k] * x3Dc[k]) + Ow[r], the cv::Mat product rule of facade/cvcompat.h as
+ * orbm_project_last_frame_batch_async states it (not the Matx rule of orbm_is_in_frustum); has_depth = 1.  Any other slot (0, negative,
+ * NaN; the reference returns an empty Mat) gets has_depth = 0 and x3dw = (0, 0, 0).
+ * Host form: host pointers, one frame, synchronous; x3dw [n][3], has_depth [n]; returns the number of points.
+ * Device form: enqueue-only, device pointers except k_host.  Row r of the call is block frame first + r of kps_un and counts (rows of
+ * cap); depth [nrows][cap] has one row per row of the call, as orbm_stereo_from_rgbd_batch_async and orbm_stereo_batch_async write it;
+ * twc [nrows][12] is device data, so a replay follows new poses.  Outputs x3dw [nrows][cap][3], has_depth [nrows][cap]; slots at or
+ * beyond the count get 0 and (0, 0, 0) too.  With q_stride == cap they are valid x3dw / has_mp inputs of
+ * orbm_project_last_frame_batch_async.  Which depth points become temporal MapPoints stays with the caller (UpdateLastFrame takes the
+ * 100 closest and those under mThDepth): the caller ANDs its own selection into has_depth.  No scratch: capturable after one eager
+ * call (orbx_capture_begin).  ORBM_E_INVALID: a NULL array, nrows or cap < 1, first < 0; ORBM_E_CAPACITY: nrows > 65535. */
+int orbm_unproject_stereo(orbm_t*, int n, const orbm_kp_t* kps_un, const float* depth, const float* twc12,
+                          const float* k, float* x3dw, uint8_t* has_depth);
+int orbm_unproject_stereo_batch_async(orbm_t*, int nrows, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                                      const float* depth, const float* twc, const float* k_host,
+                                      float* x3dw, uint8_t* has_depth);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -20,6 +20,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 
 HOST, DEVICE = 0, 1
+DEPTH_U16, DEPTH_F32 = 0, 1                          # include/orbm.h: ORBM_DEPTH_*
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -863,6 +864,11 @@ def _install_search():
                                                              vp, vp, cf, cf, cf, cf,                      # its grid, bounds
                                                              vp, vp, vp, ci, cf, ci,                      # row1, row2, prev_in, window, nnratio, check_ori
                                                              vp, vp, vp]                                  # matches12, nmatches, prev_out
+    L.orbm_stereo_from_rgbd.argtypes = [vp, ci, vp, vp, vp, ci, ci, ci, ci, cf, cf, vp, vp]   # n, kps, kps_un, image, type, w, h, stride, factor, mbf, outputs
+    L.orbm_stereo_from_rgbd_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,                # nframes, first, cap, kps, kps_un, counts
+                                                    vp, ci, ci, ci, ci, cf, cf, vp, vp, vp]    # image table, type, w, h, stride, factor, mbf, outputs
+    L.orbm_unproject_stereo.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.orbm_unproject_stereo_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -870,8 +876,48 @@ def _install_search():
     L.orbm_bow_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_bow_vectors.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]
+
+    def stereo_from_rgbd(self, kps, kps_un, depth_img, depth_factor, mbf):
+        """Frame::ComputeStereoFromRGBD (Frame.cc:1279-1309) on the UNCONVERTED depth image (2-D uint16 or float32, any row stride) and
+        mDepthMapFactor (Tracking.cc:1353-1354) -> (number of keypoints with depth, mvuRight, mvDepth)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE); un = kps if kps_un is None else np.ascontiguousarray(kps_un, KP_DTYPE)
+        img = np.asarray(depth_img)
+        if img.ndim != 2 or img.dtype not in (np.uint16, np.float32) or img.strides[1] != img.itemsize:
+            raise OrbError("depth image must be a 2-D uint16 or float32 array with contiguous rows")
+        n = len(kps)
+        ur = np.zeros(max(n, 1), np.float32); dp = np.zeros(max(n, 1), np.float32)
+        rc = _chk(self.L.orbm_stereo_from_rgbd(self.h, n, _p(kps), _p(un), img.ctypes.data, DEPTH_F32 if img.dtype == np.float32 else DEPTH_U16,
+                                               img.shape[1], img.shape[0], img.strides[0], float(depth_factor), float(mbf), _p(ur), _p(dp)),
+                  "orbm_stereo_from_rgbd")
+        return rc, ur[:n], dp[:n]
+
+    def stereo_from_rgbd_batch_async(self, nframes, first, cap, kps, kps_un, counts, depth_imgs, depth_type, w, h, stride_bytes, depth_factor, mbf,
+                                     uright, depth, nvalid):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_stereo_from_rgbd_batch_async)."""
+        return _chk(self.L.orbm_stereo_from_rgbd_batch_async(self.h, nframes, first, cap, kps, kps_un, counts, depth_imgs, depth_type, w, h, stride_bytes,
+                                                             float(depth_factor), float(mbf), uright, depth, nvalid), "orbm_stereo_from_rgbd_batch_async")
+
+    def unproject_stereo(self, kps_un, depth, twc, K):
+        """Frame::UnprojectStereo (Frame.cc:1312-1326) for every keypoint: twc = row-major 3x4 [Rwc | Ow], K = (fx, fy, cx, cy) ->
+        (number of points, x3Dw [n][3], has_depth [n])."""
+        un = np.ascontiguousarray(kps_un, KP_DTYPE); n = len(un)
+        d = np.ascontiguousarray(depth, np.float32); T = np.ascontiguousarray(twc, np.float32).reshape(12); K = np.ascontiguousarray(K, np.float32)
+        x = np.zeros((max(n, 1), 3), np.float32); hd = np.zeros(max(n, 1), np.uint8)
+        rc = _chk(self.L.orbm_unproject_stereo(self.h, n, _p(un), _p(d), _p(T), _p(K), _p(x), _p(hd)), "orbm_unproject_stereo")
+        return rc, x[:n], hd[:n]
+
+    def unproject_stereo_batch_async(self, nrows, first, cap, kps_un, counts, depth, twc, K, x3dw, has_depth):
+        """Device form, enqueue only: device pointers except K (include/orbm.h: orbm_unproject_stereo_batch_async)."""
+        K = np.ascontiguousarray(K, np.float32)
+        return _chk(self.L.orbm_unproject_stereo_batch_async(self.h, nrows, first, cap, kps_un, counts, depth, twc, _p(K), x3dw, has_depth),
+                    "orbm_unproject_stereo_batch_async")
+
     ORBmatcher.window_candidates = window_candidates
     ORBmatcher.ComputeStereoMatches = stereo_matches
+    ORBmatcher.ComputeStereoFromRGBD = stereo_from_rgbd
+    ORBmatcher.ComputeStereoFromRGBDBatchAsync = stereo_from_rgbd_batch_async
+    ORBmatcher.UnprojectStereo = unproject_stereo
+    ORBmatcher.UnprojectStereoBatchAsync = unproject_stereo_batch_async
     _bind_frame_geometry(L, "orbm_")
     for name, fn in _frame_geometry_methods("orbm_").items():
         setattr(ORBmatcher, name, fn)
@@ -943,6 +989,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",
             "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
+            "orbm_stereo_from_rgbd", "orbm_stereo_from_rgbd_batch_async", "orbm_unproject_stereo", "orbm_unproject_stereo_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

@@ -2326,4 +2326,114 @@ int orbm_is_in_frustum(orbm_t* m, int space, int n, const float* pw, const float
     return cnt;
 }
 
+// ---- RGB-D frames: Frame::ComputeStereoFromRGBD and Frame::UnprojectStereo ----------------------------------
+// the argument tests the host and the device form share; fills the kernel's parameter block
+static int rgbd_params(const char* who, int first, int cap, int depth_type, int w, int h, int stride_bytes, float depth_factor, float mbf, RgbdParams& P) {
+    if (depth_type != ORBM_DEPTH_U16 && depth_type != ORBM_DEPTH_F32) { set_merr("%s: unknown depth_type %d", who, depth_type); return ORBM_E_INVALID; }
+    const int es = depth_type == ORBM_DEPTH_F32 ? 4 : 2;
+    if (cap < 1 || w < 1 || h < 1 || first < 0) { set_merr("%s: cap, w and h must be >= 1 and first >= 0", who); return ORBM_E_INVALID; }
+    if ((long long)stride_bytes < (long long)w * es || stride_bytes % es) {
+        set_merr("%s: stride_bytes %d is below w * %d or not a multiple of the %d-byte element", who, stride_bytes, es, es);
+        return ORBM_E_INVALID;
+    }
+    if (!std::isfinite(depth_factor)) { set_merr("%s: depth_factor is not finite", who); return ORBM_E_INVALID; }
+    P.first = first; P.cap = cap; P.w = w; P.h = h; P.stride_bytes = stride_bytes;
+    P.f32 = depth_type == ORBM_DEPTH_F32;
+    P.scale = !P.f32 || std::fabs(depth_factor - 1.0f) > 1e-5;             // Tracking.cc:1353, the condition as written
+    P.factor = depth_factor; P.mbf = mbf;
+    return ORBM_OK;
+}
+
+int orbm_stereo_from_rgbd_batch_async(orbm_t* m, int nframes, int first, int cap,
+                                      const orbm_kp_t* kps, const orbm_kp_t* kps_un, const int32_t* counts,
+                                      const void* const* depth_imgs, int depth_type, int w, int h, int stride_bytes,
+                                      float depth_factor, float mbf, float* uright, float* depth, int32_t* nvalid) {
+    if (!m || !kps || !kps_un || !counts || !depth_imgs || !uright || !depth || !nvalid) {
+        set_merr("ComputeStereoFromRGBD batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nframes < 1) { set_merr("ComputeStereoFromRGBD batch: nframes must be >= 1"); return ORBM_E_INVALID; }
+    RgbdParams P;
+    const int rc = rgbd_params("ComputeStereoFromRGBD batch", first, cap, depth_type, w, h, stride_bytes, depth_factor, mbf, P);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    hipLaunchKernelGGL(k_rgbd_stereo, dim3(nframes), dim3(256), 0, m->stream, (const KpIn*)kps, (const KpIn*)kps_un, counts, depth_imgs, P,
+                       uright, depth, nvalid);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_stereo_from_rgbd(orbm_t* m, int n, const orbm_kp_t* kps, const orbm_kp_t* kps_un,
+                          const void* depth_img, int depth_type, int w, int h, int stride_bytes,
+                          float depth_factor, float mbf, float* uright, float* depth) {
+    if (!m || n < 0 || !depth_img || (n > 0 && (!kps || !kps_un || !uright || !depth))) {
+        set_merr("ComputeStereoFromRGBD: a required array is NULL or n < 0");
+        return ORBM_E_INVALID;
+    }
+    RgbdParams P;
+    const int rc = rgbd_params("ComputeStereoFromRGBD", 0, std::max(n, 1), depth_type, w, h, stride_bytes, depth_factor, mbf, P);
+    if (rc) return rc;
+    if (n == 0) return 0;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t img_bytes = (size_t)(h - 1) * stride_bytes + (size_t)w * (P.f32 ? 4 : 2);   // the last row's padding is not the caller's to give
+    const void* tab0 = nullptr;
+    DevBuf dk, du, dc, dimg, dtab, dur, ddp, dnv;
+    arena_reset(m);
+    UP(dk, kps, sizeof(KpIn) * n);
+    if (kps_un != kps) UP(du, kps_un, sizeof(KpIn) * n);
+    UP(dc, &n, sizeof(int)); UP(dimg, depth_img, img_bytes); UP(dtab, &tab0, sizeof(void*));
+    AL(dur, sizeof(float) * n); AL(ddp, sizeof(float) * n); AL(dnv, sizeof(int));
+    const void* dev_img = dimg.ptr();                                       // the arena no longer moves: the table can name the image
+    memcpy(m->arPin + dtab.off, &dev_img, sizeof(void*));
+    ARENA_FLUSH(m);
+    hipLaunchKernelGGL(k_rgbd_stereo, dim3(1), dim3(256), 0, m->stream, dk.as<KpIn>(), kps_un != kps ? du.as<KpIn>() : dk.as<KpIn>(), dc.as<int>(),
+                       dtab.as<const void*>(), P, dur.as<float>(), ddp.as<float>(), dnv.as<int>());
+    MHIPCHK(hipGetLastError());
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(uright, dur.host(), sizeof(float) * n); memcpy(depth, ddp.host(), sizeof(float) * n);
+    return *(const int*)dnv.host();
+}
+
+int orbm_unproject_stereo_batch_async(orbm_t* m, int nrows, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                                      const float* depth, const float* twc, const float* k_host, float* x3dw, uint8_t* has_depth) {
+    if (!m || !kps_un || !counts || !depth || !twc || !k_host || !x3dw || !has_depth) {
+        set_merr("UnprojectStereo batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nrows < 1 || cap < 1 || first < 0) { set_merr("UnprojectStereo batch: nrows and cap must be >= 1 and first >= 0"); return ORBM_E_INVALID; }
+    if (nrows > 65535) { set_merr("UnprojectStereo batch: %d rows in one call (at most 65535)", nrows); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    const UnprojParams P{first, cap, k_host[2], k_host[3], 1.0f / k_host[0], 1.0f / k_host[1]};   // invfx = 1.0f / fx (Frame.cc:301-302)
+    hipLaunchKernelGGL(k_unproject_stereo, dim3((cap + 255) / 256, nrows), dim3(256), 0, m->stream, (const KpIn*)kps_un, counts, depth, twc, P,
+                       x3dw, has_depth);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_unproject_stereo(orbm_t* m, int n, const orbm_kp_t* kps_un, const float* depth, const float* twc12, const float* k,
+                          float* x3dw, uint8_t* has_depth) {
+    if (!m || n < 0 || !twc12 || !k || (n > 0 && (!kps_un || !depth || !x3dw || !has_depth))) {
+        set_merr("UnprojectStereo: a required array is NULL or n < 0");
+        return ORBM_E_INVALID;
+    }
+    if (n == 0) return 0;
+    MHIPCHK(hipSetDevice(m->device));
+    DevBuf dk, dc, dd, dt, dx, dh;
+    arena_reset(m);
+    UP(dk, kps_un, sizeof(KpIn) * n); UP(dc, &n, sizeof(int)); UP(dd, depth, sizeof(float) * n); UP(dt, twc12, sizeof(float) * 12);
+    AL(dx, sizeof(float) * 3 * n); AL(dh, n);
+    ARENA_FLUSH(m);
+    const UnprojParams P{0, n, k[2], k[3], 1.0f / k[0], 1.0f / k[1]};
+    hipLaunchKernelGGL(k_unproject_stereo, dim3((n + 255) / 256, 1), dim3(256), 0, m->stream, dk.as<KpIn>(), dc.as<int>(), dd.as<float>(), dt.as<float>(), P,
+                       dx.as<float>(), dh.as<uint8_t>());
+    MHIPCHK(hipGetLastError());
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(x3dw, dx.host(), sizeof(float) * 3 * n); memcpy(has_depth, dh.host(), n);
+    int cnt = 0;
+    for (int i = 0; i < n; ++i) cnt += has_depth[i] ? 1 : 0;
+    return cnt;
+}
+
 }  // extern "C"

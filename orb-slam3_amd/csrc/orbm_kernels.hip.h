@@ -3548,6 +3548,83 @@ __global__ __launch_bounds__(256) void k_frustum(int n, const float* __restrict_
     inView[i] = 1; projXR[i] = u - F.bf * invz; depth[i] = PcDist; level[i] = ns; viewCos[i] = vc;
 }
 
+// ------------------------------------------------------------------------------------------------
+// RGB-D frames.  k_rgbd_stereo: Frame::ComputeStereoFromRGBD (Frame.cc:1279-1309) with GrabImageRGBD's convertTo
+// (Tracking.cc:1353-1354) folded into the sample: only the pixels under keypoints are read, and converting one pixel gives what
+// converting the image gives.  One workgroup per frame of the call strides over the row's `cap` slots, so that the count of valid
+// depths is a reduction over the finished row (ballot + popcount per wave, LDS across the waves, one plain store): nothing
+// accumulates across graph replays and nothing has to be cleared.
+//   pixel   row = (int)kp.y, col = (int)kp.x of the RAW keypoint (the truncation of Mat::at<float>(float, float)); a coordinate whose
+//           truncation lies outside the image, or a NaN, reads nothing and gives -1 / -1 (the reference reads out of bounds there)
+//   d       scale ? (float)raw * factor : raw  -- one float32 multiply (convertTo's alpha in float, beta == 0)
+//   d > 0   depth = d, uright = kpU.x - mbf / d (IEEE float division, float subtraction); else -1 / -1 (0, negatives, NaN)
+// Slots at or beyond the frame's count get -1 / -1 too.
+// ------------------------------------------------------------------------------------------------
+struct RgbdParams { int first, cap, w, h, stride_bytes, f32, scale; float factor, mbf; };
+
+__global__ __launch_bounds__(256) void k_rgbd_stereo(const KpIn* __restrict__ kps, const KpIn* __restrict__ kps_un, const int* __restrict__ counts,
+                                                     const void* const* __restrict__ depth_imgs, RgbdParams P,
+                                                     float* __restrict__ uright, float* __restrict__ depth, int* __restrict__ nvalid) {
+    __shared__ int sCnt[4];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const size_t in0 = (size_t)(P.first + f) * P.cap, out0 = (size_t)f * P.cap;
+    const int n = min(max(counts[P.first + f], 0), P.cap);
+    const uint8_t* img = (const uint8_t*)depth_imgs[f];
+    const float fw = (float)P.w, fh = (float)P.h;
+    int cnt = 0;
+    for (int base = 0; base < P.cap; base += 256) {                          // uniform trip count: every lane reaches the ballot
+        const int i = base + tid;
+        float ur = -1.0f, dp = -1.0f;
+        if (i < n) {
+            const float x = kps[in0 + i].x, y = kps[in0 + i].y;
+            if (x > -1.0f && x < fw && y > -1.0f && y < fh) {                // (int) truncates towards zero: (-1, 0) reads index 0; NaN fails
+                const uint8_t* p = img + (size_t)(int)y * P.stride_bytes;
+                const float raw = P.f32 ? ((const float*)p)[(int)x] : (float)((const uint16_t*)p)[(int)x];
+                const float d = P.scale ? raw * P.factor : raw;
+                if (d > 0) { dp = d; ur = kps_un[in0 + i].x - P.mbf / d; }
+            }
+        }
+        if (i < P.cap) { uright[out0 + i] = ur; depth[out0 + i] = dp; }
+        cnt += __popcll(__ballot(dp > 0));                                   // wave-uniform: -1 marks every slot without depth
+    }
+    if ((tid & 63) == 0) sCnt[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) nvalid[f] = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
+}
+
+// k_unproject_stereo: Frame::UnprojectStereo (Frame.cc:1312-1326) for every slot of every row.  z = depth > 0: x = (u - cx) * z * invfx
+// and y likewise, left to right in float; x3Dw = mRwc * x3Dc + mOw by the cv::Mat product rule (double sum rounded once to float, then
+// a float add: mm_dot3, as k_mm_project) -- not the Matx rule of k_frustum.  Any other slot, and slots at or beyond the count, get
+// has_depth = 0 and (0, 0, 0).  twc: [nrows][12] row-major 3x4 [Rwc | Ow].
+struct UnprojParams { int first, cap; float cx, cy, invfx, invfy; };
+
+__global__ __launch_bounds__(256) void k_unproject_stereo(const KpIn* __restrict__ kps_un, const int* __restrict__ counts, const float* __restrict__ depth,
+                                                          const float* __restrict__ twc, UnprojParams P, float* __restrict__ x3dw,
+                                                          uint8_t* __restrict__ has_depth) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= P.cap) return;
+    const size_t o = (size_t)r * P.cap + i;
+    const int n = min(max(counts[P.first + r], 0), P.cap);
+    float X = 0.f, Y = 0.f, Z = 0.f;
+    uint8_t ok = 0;
+    if (i < n) {
+        const float z = depth[o];
+        if (z > 0) {
+            const KpIn& kp = kps_un[(size_t)(P.first + r) * P.cap + i];
+            const float x = (kp.x - P.cx) * z * P.invfx;
+            const float y = (kp.y - P.cy) * z * P.invfy;
+            const float* T = twc + (size_t)r * 12;
+            X = mm_dot3(T[0], T[1], T[2], x, y, z) + T[3];
+            Y = mm_dot3(T[4], T[5], T[6], x, y, z) + T[7];
+            Z = mm_dot3(T[8], T[9], T[10], x, y, z) + T[11];
+            ok = 1;
+        }
+    }
+    x3dw[o * 3] = X; x3dw[o * 3 + 1] = Y; x3dw[o * 3 + 2] = Z;
+    has_depth[o] = ok;
+}
+
 // k_gather_rows: packs the used prefix of every row of the two [nq][cap] candidate arrays into [nq][maxc] (one contiguous
 // device-to-host copy instead of nq*cap entries or a strided copy).
 __global__ __launch_bounds__(256) void k_gather_rows(const int* __restrict__ idx, const int* __restrict__ dist, int nq, int cap, int maxc,

@@ -3,8 +3,11 @@
 //   Frame::ComputeImageBounds   (src/Frame.cc:977-1021)  -> ComputeImageBounds()
 //   Frame::isInFrustum for all local map points (src/Frame.cc:603-671, src/Tracking.cc:3808-3862) -> IsInFrustumBatch()
 //   cvtColor(..., COLOR_*2GRAY) (src/Tracking.cc:1264-1290) -> see orbx_gray_from_color in include/orbx.h
+//   Frame::ComputeStereoFromRGBD (src/Frame.cc:1279-1309) + the depth conversion of GrabImageRGBD (src/Tracking.cc:1353-1354) -> ComputeStereoFromRGBD()
+//   Frame::UnprojectStereo for every keypoint (src/Frame.cc:1312-1326) -> UnprojectStereoAll()
 // The bodies only flatten the reference's containers into plain arrays; all arithmetic runs in liborbslam3_amd.so.
 #pragma once
+#include <cstdint>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -52,6 +55,45 @@ inline int IsInFrustumBatch(orbm_t* m, const std::vector<float>& Pw3, const std:
                                       viewingCosLimit, logScaleFactor, nScaleLevels, out.inView.data(), out.projX.data(), out.projY.data(),
                                       out.projXR.data(), out.depth.data(), out.level.data(), out.viewCos.data());
     if (rc < 0) throw std::runtime_error(std::string("orbm_is_in_frustum: ") + orbm_last_error());
+    return rc;
+}
+
+// mvuRight, mvDepth of an RGB-D frame from the UNCONVERTED depth image and mDepthMapFactor: the caller drops its own
+// imDepth.convertTo(imDepth, CV_32F, mDepthMapFactor) (Tracking.cc:1353-1354; the conversion is applied to the sampled pixels), or
+// passes the converted CV_32F image with factor 1.  depthType = ORBM_DEPTH_U16 | ORBM_DEPTH_F32, stepBytes = imDepth.step.
+// Returns the number of keypoints with depth.
+inline int ComputeStereoFromRGBD(orbm_t* m, const std::vector<cv::KeyPoint>& keys, const std::vector<cv::KeyPoint>& keysUn,
+                                 const void* depth, int depthType, int cols, int rows, size_t stepBytes, float depthMapFactor, float bf,
+                                 std::vector<float>& uRight, std::vector<float>& vDepth) {
+    static_assert(sizeof(cv::KeyPoint) == sizeof(orbm_kp_t), "cv::KeyPoint layout");
+    if (keysUn.size() != keys.size()) throw std::runtime_error("ComputeStereoFromRGBD: mvKeys and mvKeysUn differ in size");
+    uRight.assign(keys.size(), -1.f); vDepth.assign(keys.size(), -1.f);               // Frame.cc:1284-1285
+    if (keys.empty()) return 0;
+    const int rc = orbm_stereo_from_rgbd(m, (int)keys.size(), (const orbm_kp_t*)keys.data(), (const orbm_kp_t*)keysUn.data(), depth, depthType, cols, rows,
+                                         (int)stepBytes, depthMapFactor, bf, uRight.data(), vDepth.data());
+    if (rc < 0) throw std::runtime_error(std::string("orbm_stereo_from_rgbd: ") + orbm_last_error());
+    return rc;
+}
+#ifdef ORBX_WITH_OPENCV
+inline int ComputeStereoFromRGBD(orbm_t* m, const std::vector<cv::KeyPoint>& keys, const std::vector<cv::KeyPoint>& keysUn, const cv::Mat& imDepth,
+                                 float depthMapFactor, float bf, std::vector<float>& uRight, std::vector<float>& vDepth) {
+    if (imDepth.type() != CV_16UC1 && imDepth.type() != CV_32FC1) throw std::runtime_error("ComputeStereoFromRGBD: the depth image must be CV_16UC1 or CV_32FC1");
+    return ComputeStereoFromRGBD(m, keys, keysUn, imDepth.data, imDepth.type() == CV_32FC1 ? ORBM_DEPTH_F32 : ORBM_DEPTH_U16, imDepth.cols, imDepth.rows,
+                                 imDepth.step, depthMapFactor, bf, uRight, vDepth);
+}
+#endif
+
+// One call for `for (i < N) x3D = UnprojectStereo(i)` (Tracking.cc: StereoInitialization, UpdateLastFrame, CreateNewKeyFrame).
+// Rwc / Ow = mRwc (row-major) / mOw, K = (fx, fy, cx, cy).  x3Dw holds 3 floats per keypoint; hasDepth[i] = 0 (and a zero point) where the
+// reference returns an empty Mat.  Returns the number of points.
+inline int UnprojectStereoAll(orbm_t* m, const std::vector<cv::KeyPoint>& keysUn, const std::vector<float>& vDepth, const float Rwc[9], const float Ow[3],
+                              const float K[4], std::vector<float>& x3Dw, std::vector<uint8_t>& hasDepth) {
+    if (vDepth.size() != keysUn.size()) throw std::runtime_error("UnprojectStereoAll: mvKeysUn and mvDepth differ in size");
+    x3Dw.assign(3 * keysUn.size(), 0.f); hasDepth.assign(keysUn.size(), 0);
+    if (keysUn.empty()) return 0;
+    const float twc[12] = {Rwc[0], Rwc[1], Rwc[2], Ow[0], Rwc[3], Rwc[4], Rwc[5], Ow[1], Rwc[6], Rwc[7], Rwc[8], Ow[2]};
+    const int rc = orbm_unproject_stereo(m, (int)keysUn.size(), (const orbm_kp_t*)keysUn.data(), vDepth.data(), twc, K, x3Dw.data(), hasDepth.data());
+    if (rc < 0) throw std::runtime_error(std::string("orbm_unproject_stereo: ") + orbm_last_error());
     return rc;
 }
 
