@@ -2,8 +2,9 @@
 stereo pair: every search is driven once with the argument shapes the GPU parity tests use and checked against properties
 the reference's loops guarantee (counts, index ranges, one-to-one claims, thresholds).  It keeps the checker itself under
 test without a GPU and is the workload tests/test_oracle_sanitize.py replays under ASan/UBSan.  The entry-for-entry check of the
-searches that have batched device forms is tests/test_second_reading_cpu.py; the searches only this file drives (M9, M11, M12,
-SearchBySim3, the fisheye forms, ComputeStereoMatches) have no independent statement."""
+searches that have batched device forms is tests/test_second_reading_cpu.py, that of ComputeStereoMatches
+tests/test_second_reading_stereo_cpu.py; the searches only this file drives (M9, M11, M12, SearchBySim3, the fisheye forms) have no
+independent statement."""
 import numpy as np
 import pytest
 
