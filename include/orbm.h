@@ -303,7 +303,7 @@ int orbm_search_by_projection_points_batch_async(orbm_t*, const orbm_kp_t* kps, 
                                                  int32_t* match, int32_t* nmatches);
 /* orbm_search_by_projection_frame_batch_async: M4 SearchByProjection(CurrentFrame, LastFrame, th, bMono) -- Tracking::TrackWithMotionModel
  * -- END TO END on the device for `npairs` pairs (ORBmatcher.cc:2469-2612 and the rotation check :2686-2708, the Nleft == -1 part; the
- * fisheye right-camera block stays with orbm_search_by_projection_frame_fisheye).  Pair p searches block frame t_first+p through its grid
+ * fisheye right-camera block is orbm_search_by_projection_frame_fisheye_batch_async).  Pair p searches block frame t_first+p through its grid
  * (orbm_grid_build_batch_async over the block, indexed by block frame id).  Per pair rows: uright [npairs][cap] (mvuRight, e.g.
  * orbm_stereo_batch_async with first_l == t_first; NULL = no stereo gate, invzc is then not read and may be NULL), t_blocked
  * [npairs][cap] (the slot holds a MapPoint with Observations() > 0; NULL = none), dir [npairs] (0 = levels o-1..o+1, 1 = bForward:
@@ -329,6 +329,45 @@ int orbm_search_by_projection_frame_batch_async(orbm_t*, const orbm_kp_t* kps, c
                                                 const float* invzc, const int32_t* octave, const float* angle, const uint8_t* qdesc,
                                                 const uint8_t* mp_obs, float th, int retry_below, const float* scale_factors_host, int nlevels,
                                                 int check_orientation, int32_t* match, int32_t* nmatches, uint8_t* retried);
+/* orbm_search_by_projection_frame_fisheye_batch_async: M4 SearchByProjection(CurrentFrame, LastFrame, th, bMono) with CurrentFrame.Nleft
+ * != -1 -- Tracking::TrackWithMotionModel on a fisheye stereo rig -- END TO END on the device for `npairs` pairs (ORBmatcher.cc:2469-2711,
+ * the right-camera block :2615-2680 included).  One pool of rows of `cap` slots (kps, desc, counts and the grid of
+ * orbm_grid_build_batch_async over it: an extractor result block or a caller-gathered array in that layout); pair p searches left row
+ * first_l+p (mvKeys, mGrid) and right row first_r+p (mvKeysRight, mGridRight), paired as orbm_stereo_batch_async pairs them; both grids
+ * share min_x, min_y, inv_w, inv_h (PosInGrid, Frame.cc:883-899).  Every other array has one row per pair of the call: blocked_l,
+ * blocked_r [npairs][cap] (mvpMapPoints[i2] / [i2 + Nleft] holds a MapPoint with Observations() > 0, :2565-2567 / :2643-2645; NULL =
+ * none), dir [npairs] (0 / 1 = bForward / 2 = bBackward, other values read as 0, NULL = all 0; the same level band for both cameras,
+ * :2544-2549 / :2628-2633), and the queries as in orbm_search_by_projection_frame_batch_async without invzc and uright -- there is no
+ * stereo gate when Nleft != -1 (:2569).  (u, v) is the left projection and (ur, vr) the projection of Trl * x3Dc into the right camera
+ * (:2616-2618); they stay with the caller, must be finite, and valid folds the caller-side tests of :2505-2528, which test the LEFT
+ * projection only -- a right window wholly outside the grid is simply empty (Frame.cc:802-824).  A query that is not valid, or whose
+ * octave lies outside [0, nlevels), reads nothing else of its row.  Per valid query, in query order, exactly as
+ * orbm_search_by_projection_frame_fisheye: radius th * scale[octave] (:2535, :2624) for both cameras; a left window without any
+ * candidate finishes the query, the right block included (the `continue` of :2551; candidates are counted before blocked slots are
+ * looked at); else the first candidate of least distance whose slot is not in the left blocked set is accepted at bestDist <= TH_HIGH
+ * (:2556-2593), written to match_l and counted -- a later claim may overwrite the slot and counts again, and only mp_obs blocks the
+ * slot for later queries --; then the same against the right row with its own blocked set, written to match_r (:2637-2661): a query
+ * may claim one slot in each camera.  check_orientation: ONE 30-bin histogram with factor 30 / 360.0f (:2480) takes both cameras'
+ * claims, the current keypoint's angle from the row that was claimed (:2602-2612, :2668-2677); ComputeThreeMaxima culls entries in
+ * either row to ORBM_MATCH_PRUNED and each culled entry counts down once (:2688-2708), a slot claimed twice sitting in it twice.
+ * retry_below > 0: a pair whose count is below it is searched again at 2 * th with both blocked sets empty (Tracking.cc:3213-3221);
+ * that result replaces both rows and the count and retried[p] = 1 (retried [npairs] or NULL; 0 for the other pairs).  Outputs
+ * (device): match_l, match_r [npairs][cap] (match_l[k] -> mvpMapPoints[k], match_r[k] -> mvpMapPoints[Nleft + k]; padded with
+ * ORBM_NO_MATCH; a pair whose left row is empty gets two all-ORBM_NO_MATCH rows and 0), nmatches [npairs].  All pointers are device
+ * pointers except scale_factors_host.  Enqueue-only: the scratch is the handle's grow-only one, so after one eager call the same or a
+ * smaller shape allocates nothing and can be captured (orbx_capture_begin).  ORBM_E_INVALID: a NULL required array (blocked_l,
+ * blocked_r, dir and retried may be NULL), a count < 1, first_l, first_r or retry_below < 0; ORBM_E_CAPACITY: cap > 65535, q_stride >
+ * ORBM_LP_MAX_QUERIES, nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                        const int32_t* grid_start, const int32_t* grid_idx,
+                                                        float min_x, float min_y, float inv_w, float inv_h,
+                                                        int first_l, int first_r, int npairs,
+                                                        const uint8_t* blocked_l, const uint8_t* blocked_r, const uint8_t* dir,
+                                                        const int32_t* nq, int q_stride, const uint8_t* valid,
+                                                        const float* u, const float* v, const float* ur, const float* vr,
+                                                        const int32_t* octave, const float* angle, const uint8_t* qdesc, const uint8_t* mp_obs,
+                                                        float th, int retry_below, const float* scale_factors_host, int nlevels, int check_orientation,
+                                                        int32_t* match_l, int32_t* match_r, int32_t* nmatches, uint8_t* retried);
 /* orbm_project_last_frame_batch_async: the projection half of M4 (ORBmatcher.cc:2481-2527) for a pinhole camera with Nleft == -1, the
  * producer of the rows above.  Per pair (device): tcw_cur, tcw_last [npairs][12] (row-major 3x4 [R | t]); per query (device): x3dw
  * [npairs][q_stride][3] (world position), has_mp [npairs][q_stride] (pMP && !mvbOutlier), nq [npairs].  Host: k_host = (fx, fy, cx, cy),

@@ -832,6 +832,10 @@ def _install_search():
                                                               vp, cf, vp, vp, vp, ci,                          # uright, mbf, t_blocked, dir, nq, q_stride
                                                               vp, vp, vp, vp, vp, vp, vp, vp,                  # valid, u, v, invzc, octave, angle, qdesc, mp_obs
                                                               cf, ci, vp, ci, ci, vp, vp, vp]                  # th, retry_below, sf, nlevels, check_ori, outputs
+    L.orbm_search_by_projection_frame_fisheye_batch_async.argtypes = [vp, vp, vp, vp, ci, vp, vp, cf, cf, cf, cf, ci, ci, ci,   # pool, grid, bounds, first_l, first_r, pairs
+                                                                      vp, vp, vp, vp, ci, vp,                       # blocked_l, blocked_r, dir, nq, q_stride, valid
+                                                                      vp, vp, vp, vp, vp, vp, vp, vp,               # u, v, ur, vr, octave, angle, qdesc, mp_obs
+                                                                      cf, ci, vp, ci, ci, vp, vp, vp, vp]           # th, retry_below, sf, nlevels, check_ori, outputs
     L.orbm_project_last_frame_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp]
     L.orbm_fuse_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,                 # pairs, KF pool (kps, desc, uright)
                                         vp, vp, cf, cf, cf, cf, vp, vp, vp,         # grid, bounds, kf_row, tcw, ow
@@ -985,6 +989,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_sim3", "orbm_fuse", "orbm_search_by_sim3",
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
+            "orbm_search_by_projection_frame_fisheye_batch_async",
             "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
             "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",
             "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",

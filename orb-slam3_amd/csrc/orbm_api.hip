@@ -1308,6 +1308,73 @@ int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps,
     return ORBM_OK;
 }
 
+int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                        const int32_t* grid_start, const int32_t* grid_idx,
+                                                        float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r, int npairs,
+                                                        const uint8_t* blocked_l, const uint8_t* blocked_r, const uint8_t* dir,
+                                                        const int32_t* nq, int q_stride, const uint8_t* valid,
+                                                        const float* u, const float* v, const float* ur, const float* vr,
+                                                        const int32_t* octave, const float* angle, const uint8_t* qdesc, const uint8_t* mp_obs,
+                                                        float th, int retry_below, const float* scale_factors_host, int nlevels, int check_orientation,
+                                                        int32_t* match_l, int32_t* match_r, int32_t* nmatches, uint8_t* retried) {
+    if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !nq || !valid || !u || !v || !ur || !vr || !octave || !angle || !qdesc ||
+        !mp_obs || !match_l || !match_r || !nmatches || !scale_factors_host) {
+        set_merr("SearchByProjection frame fisheye batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || cap < 1 || q_stride < 1 || first_l < 0 || first_r < 0 || nlevels < 1 || retry_below < 0) {
+        set_merr("SearchByProjection frame fisheye batch: npairs, cap, q_stride and nlevels must be >= 1, first_l, first_r and retry_below >= 0");
+        return ORBM_E_INVALID;
+    }
+    if (const int rc = lp_capacity("SearchByProjection frame fisheye batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    const size_t lds = (size_t)(2 * ((cap + 31) >> 5) + 32 + 2 * 64 * TK_K) * sizeof(unsigned);   // two blocked bit arrays, histogram, both cameras' lists of the current 64 queries
+    // scratch of the handle: per query and camera the window population, its TK_K best candidates and its radius; per query two slots of
+    // the accepted-assignment list
+    const size_t rows = (size_t)npairs * q_stride;
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = (rows * sizeof(float) + 255) & ~(size_t)255,
+                 bCam = bCnt + bKeys + bR, bAcc = 2 * rows * sizeof(unsigned);
+    uint8_t* scr = batch_scratch(m, 2 * bCam + bAcc);
+    if (!scr) { set_merr("SearchByProjection frame fisheye batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", 2 * bCam + bAcc); return ORBM_E_HIP; }
+    int* topCnt[2]; unsigned* topKeys[2]; float* topR[2];
+    for (int c = 0; c < 2; ++c) {
+        topCnt[c] = (int*)(scr + c * bCam); topKeys[c] = (unsigned*)(scr + c * bCam + bCnt); topR[c] = (float*)(scr + c * bCam + bCnt + bKeys);
+    }
+    unsigned* acc = (unsigned*)(scr + 2 * bCam);
+    MmRows R;
+    R.nq = nq; R.q_stride = q_stride;
+    R.valid = valid; R.u = u; R.v = v; R.invzc = nullptr; R.octave = octave; R.angle = angle;   // no stereo gate when Nleft != -1 (ORBmatcher.cc:2569)
+    R.qdesc = qdesc; R.mp_obs = mp_obs; R.dir = dir;
+    R.mbf = 0.f; R.factor = ORBM_HISTO_LENGTH / 360.0f;                     // ORBmatcher.cc:2480
+    R.nlevels = nlevels; R.retry_below = retry_below; R.check_ori = check_orientation != 0;
+    MmRows Rr = R;                                                          // the right camera's candidate pass: the same rows at (ur, vr), :2616-2633
+    Rr.u = ur; Rr.v = vr;
+    const MmfLists T{topCnt[0], topKeys[0], topR[0], topCnt[1], topKeys[1], topR[1]};
+    const dim3 gTop((q_stride + 3) / 4, npairs);
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, th, nmatches, topCnt[0], topKeys[0], topR[0]);
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, th, nmatches, topCnt[1], topKeys[1], topR[1]);
+    hipLaunchKernelGGL(k_mmf_claim<false>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, R, ur, vr, T, acc, match_l, match_r, nmatches, retried);
+    if (retry_below > 0) {                                                  // Tracking.cc:3213-3221, decided per pair on the device
+        const float th2 = 2 * th;
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, th2, nmatches, topCnt[0], topKeys[0], topR[0]);
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, th2, nmatches, topCnt[1], topKeys[1], topR[1]);
+        hipLaunchKernelGGL(k_mmf_claim<true>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                           min_x, min_y, inv_w, inv_h, first_l, first_r, (const uint8_t*)nullptr, (const uint8_t*)nullptr, R, ur, vr, T, acc,
+                           match_l, match_r, nmatches, retried);
+    }
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 int orbm_project_last_frame_batch_async(orbm_t* m, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
                                         const float* x3dw, const uint8_t* has_mp, const float* k_host, const float* bounds_host, float mb, int mono,
                                         uint8_t* valid, float* u, float* v, float* invzc, uint8_t* dir) {

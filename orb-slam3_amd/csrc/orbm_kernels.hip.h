@@ -2418,6 +2418,178 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// M4 with Nleft != -1 (a fisheye rig: ORBmatcher.cc:2469-2711 with the right-camera block :2615-2680), final rows on the device.  A pair
+// is a left row (mvKeys, mGrid) and a right row (mvKeysRight, mGridRight) of one pool; there is no stereo gate (:2569).  The candidate
+// pass is k_mm_topk once per camera -- (u, v) over the left rows, (ur, vr) over the right rows, each with its own count / key / radius
+// lists -- so the radius th * sf[octave] and the rotation bin are mm_query's and RotBinPay's, the bin against the angle of the row
+// that was searched (:2602-2604, :2668).
+// k_mmf_claim: one wave per pair replays the queries in order.  A query whose LEFT window is empty is finished: the `continue` of
+//   :2551 skips the right block too, and the window population is counted before blocked slots are looked at.  Otherwise it claims
+//   its first unblocked candidate of least distance in the left row (:2556-2593) and then, independently, in the right row
+//   (:2637-2661), each camera with its own blocked bit array in LDS (mvpMapPoints[i2] and [i2 + Nleft]); a listed-all-blocked window
+//   that holds more than TK_K is rescanned per camera (win_sweep<false>).  Both cameras' assignments go into ONE histogram and one
+//   accepted list (slot | bin << 16 | camera << 21, :2612 / :2677); the three-maxima cull (:2688-2708) writes ORBM_MATCH_PRUNED to
+//   the row the entry names and counts down once per entry.
+// RETRY: as k_mm_*: 2 * th, both blocked sets empty, only the pairs whose count is below retry_below (Tracking.cc:3213-3221).
+// ------------------------------------------------------------------------------------------------
+// one camera's rows of a pair and its projections
+struct MmfCam {
+    const KpIn* kt; const uint8_t* dt; const int* gs; const int* gi;
+    const float* px; const float* py;                                       // [npairs][q_stride]
+};
+
+// query i of the current 64 (row o) in one camera: the first listed candidate that is not blocked, or, when every listed one is
+// blocked and the window holds more, the window again with the blocked set applied.  0xFFFFFFFF: nothing to claim.
+__device__ __forceinline__ unsigned int mmf_best(const unsigned int* sk, int i, const unsigned int* blk, int cnt, float r, const MmfCam& cam,
+                                                 const MmRows& R, int p, size_t o, float min_x, float min_y, float inv_w, float inv_h, int lane) {
+    const unsigned INV = 0xFFFFFFFFu;
+    unsigned int key = INV;
+    bool fr = false;
+    if (lane < TK_K) {
+        key = sk[i * TK_K + lane];
+        const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
+        fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
+    }
+    const unsigned long long fb = __ballot(fr);
+    unsigned int best = fb ? (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1) : INV;
+    if (best == INV && cnt > TK_K) {
+        Win w;                                                               // the window k_mm_topk swept for this camera
+        w.r = r;
+        mm_levels(R, p, R.octave[o], o, false, w);
+        w.x = cam.px[o]; w.y = cam.py[o];
+        u64 a[4], top[TK_K];
+        load_desc(R.qdesc + o * 32, a);
+        int c2;
+        win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, cam.kt, cam.dt, nullptr, cam.gs, cam.gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+        best = cand_word(top[0]);
+    }
+    return best;
+}
+
+// rot_cull over two rows: entry = slot | bin << 16 | camera << 21
+__device__ __forceinline__ int rot_cull_lr(const unsigned int* hist, const unsigned int* acc, int nacc, int* mrow_l, int* mrow_r, int lane) {
+    const Max3 m3 = three_maxima(hist);
+    const int i1 = m3.i1, i2 = m3.i2, i3 = m3.i3;
+    int pruned = 0;
+    for (int e = lane; e < nacc; e += 64) {
+        const unsigned int v = acc[e];
+        const int bin = (int)((v >> 16) & 31u), k = (int)(v & 0xFFFFu);
+        if (bin != i1 && bin != i2 && bin != i3) { ((v >> 21) & 1u ? mrow_r : mrow_l)[k] = -2; ++pruned; }   // ORBM_MATCH_PRUNED
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pruned += __shfl_xor(pruned, o);
+    return pruned;
+}
+
+struct MmfLists {                                          // what the two k_mm_topk launches left, [npairs][q_stride] each
+    const int* cnt_l; const unsigned int* keys_l; const float* r_l;
+    const int* cnt_r; const unsigned int* keys_r; const float* r_r;
+};
+
+template <bool RETRY>
+__global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                  float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
+                                                  const uint8_t* __restrict__ blocked_l, const uint8_t* __restrict__ blocked_r, MmRows R,
+                                                  const float* __restrict__ ur, const float* __restrict__ vr, MmfLists T,
+                                                  unsigned int* __restrict__ accepted,
+                                                  int* __restrict__ match_l, int* __restrict__ match_r, int* __restrict__ nmatches,
+                                                  uint8_t* __restrict__ retried) {
+    extern __shared__ unsigned int mmf_lds[];                                // blocked bits left, right [ceil(cap / 32)] each, hist[32], the current 64 queries' lists [64][TK_K] per camera
+    const unsigned INV = 0xFFFFFFFFu;
+    const int lane = threadIdx.x, p = blockIdx.x, fl = first_l + p, fr = first_r + p;
+    if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // (wave-uniform) the first search of this pair stands
+    const int ntl = min(max(counts[fl], 0), cap), ntr = min(max(counts[fr], 0), cap);
+    const int nq = min(max(R.nq[p], 0), R.q_stride);
+    const int nwords = (cap + 31) >> 5;
+    unsigned int* blkL = mmf_lds;
+    unsigned int* blkR = blkL + nwords;
+    unsigned int* hist = blkR + nwords;
+    unsigned int* skL = hist + 32;
+    unsigned int* skR = skL + 64 * TK_K;
+    int* mrowL = match_l + (size_t)p * cap;
+    int* mrowR = match_r + (size_t)p * cap;
+    const uint8_t* tbl = !RETRY && blocked_l ? blocked_l + (size_t)p * cap : nullptr;   // the retry starts from an empty frame (Tracking.cc:3217)
+    const uint8_t* tbr = !RETRY && blocked_r ? blocked_r + (size_t)p * cap : nullptr;
+    for (int wd = lane; wd < nwords; wd += 64) { blkL[wd] = bits_word(tbl, ntl, wd, 0u); blkR[wd] = bits_word(tbr, ntr, wd, 0u); }
+    if (lane < 32) hist[lane] = 0;
+    for (int k = lane; k < cap; k += 64) { mrowL[k] = -1; mrowR[k] = -1; }  // ORBM_NO_MATCH
+    __syncthreads();
+    const size_t rowBase = (size_t)p * R.q_stride;
+    const MmfCam camL{kps + (size_t)fl * cap, desc + (size_t)fl * cap * 32, grid_start + (size_t)fl * (64 * 48 + 1), grid_idx + (size_t)fl * cap, R.u, R.v};
+    const MmfCam camR{kps + (size_t)fr * cap, desc + (size_t)fr * cap * 32, grid_start + (size_t)fr * (64 * 48 + 1), grid_idx + (size_t)fr * cap, ur, vr};
+    unsigned int* acc = accepted + rowBase * 2;                              // at most one entry per query and camera, in order
+    int nm = 0, nacc = 0;
+    // the next 64 queries' lists and counts of both cameras are in flight while the current ones are replayed (clamped, unconditional
+    // loads); mp_obs is read only for a query with left candidates (any other row reads nothing else)
+    const unsigned int* keyRowL = T.keys_l + rowBase * TK_K;
+    const unsigned int* keyRowR = T.keys_r + rowBase * TK_K;
+    const int* cntRowL = T.cnt_l + rowBase;
+    const int* cntRowR = T.cnt_r + rowBase;
+    const uint8_t* obRow = R.mp_obs + rowBase;
+    unsigned int pkL[TK_K], pkR[TK_K];
+    int pcL = 0, pcR = 0;
+    uint8_t pob = 0;
+    auto fetch = [&](int W0) {
+        const int last = nq * TK_K - 1;
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) {
+            const int e = min(W0 * TK_K + r * 64 + lane, last);
+            pkL[r] = keyRowL[e]; pkR[r] = keyRowR[e];
+        }
+        const int qc = min(W0 + lane, nq - 1);
+        pcL = cntRowL[qc]; pcR = cntRowR[qc];
+        pob = (W0 + lane < nq && pcL > 0) ? obRow[qc] : 0;
+    };
+    if (nq > 0) fetch(0);
+    for (int W0 = 0; W0 < nq; W0 += 64) {
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) { skL[r * 64 + lane] = pkL[r]; skR[r * 64 + lane] = pkR[r]; }   // query i's lists: sk?[i * TK_K .. + TK_K)
+        const int cntL = W0 + lane < nq ? pcL : 0;
+        const int cntR = pcR;                                                // read only where cntL > 0
+        const int ob = pob != 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (W0 + 64 < nq) fetch(W0 + 64);
+        unsigned long long todo = __ballot(cntL > 0);                       // skipped queries and empty LEFT windows: the right block is skipped too (:2551)
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const size_t o = rowBase + W0 + i;
+            const int obi = __builtin_amdgcn_readlane(ob, i);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {                                    // the left claim (:2556-2613), then the right one (:2637-2679)
+                const int cn = __builtin_amdgcn_readlane(c ? cntR : cntL, i);
+                if (cn <= 0) continue;                                       // (right) an empty window claims nothing
+                unsigned int* blk = c ? blkR : blkL;
+                const unsigned int best = mmf_best(c ? skR : skL, i, blk, cn, cn > TK_K ? (c ? T.r_r : T.r_l)[o] : 0.f, c ? camR : camL, R, p, o,
+                                                   min_x, min_y, inv_w, inv_h, lane);
+                if (best == INV || (best >> 21) > 100u) continue;            // TH_HIGH (:2590, :2658)
+                const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
+                const bool withBin = R.check_ori && bin != TK_NOBIN;
+                if (lane == 0) {
+                    (c ? mrowR : mrowL)[k] = W0 + i;                         // may overwrite a claim of a query without observations
+                    if (obi) blk[k >> 5] |= 1u << (k & 31);
+                    if (withBin) { acc[nacc] = k | (bin << 16) | ((unsigned)c << 21); hist[bin] += 1u; }
+                }
+                ++nm;                                                        // overwrites count, as the reference's nmatches++ does
+                if (withBin) ++nacc;
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // the next chunk's lists overwrite sk
+        __builtin_amdgcn_wave_barrier();
+    }
+    __syncthreads();
+    if (R.check_ori) nm -= rot_cull_lr(hist, acc, nacc, mrowL, mrowR, lane);
+    if (lane == 0) {
+        nmatches[p] = nm;
+        if (retried) retried[p] = RETRY ? 1 : 0;
+    }
+}
+
 // k_mm_project: the LastFrame MapPoints of every pair through the current pose (ORBmatcher.cc:2481-2527 as facade/ORBmatcher.h
 // evaluates it against cvcompat.h): a 3x3 * 3x1 product accumulates in double and rounds once to float, the translation is a float
 // add; invzc = (float)(1.0 / (double)z); pinhole u = fx * xc / zc + cx (Pinhole.cpp:33-37).  A rejected point (no MapPoint or an
