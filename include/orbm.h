@@ -477,7 +477,12 @@ int orbm_triangulation_batch_async(orbm_t*, int npairs, int cap,
  * The tree lives in HBM; orbm_bow_transform descends it for n descriptors (host pointers) and returns per feature the
  * word id, the node id `levelsup` levels above the leaves (the SearchByBoW bucket) and the word weight (0 = stopped).
  * orbm_bow_vectors assembles BowVector (TF-IDF, L1-normalised: the ORBvoc configuration) and FeatureVector (CSR) on the
- * host exactly as the std::map based classes do. */
+ * host exactly as the std::map based classes do.
+ * The text header is `k L scoring weighting`.  The reference switches transform on the last two (:1145-1193: TF / TF_IDF add
+ * weights, IDF / BINARY insert once; a scoring type that does not normalise divides by v.size()); orbm_bow_vectors implements
+ * TF_IDF + L1 only, so orbm_vocab_load_text refuses every header whose scoring / weighting pair is not `0 0` with ORBM_E_INVALID
+ * and a message that names the two fields.  A node may have at most 31 children (orbm_vocab_create; the text header's k is
+ * at most 20, :1359). */
 typedef struct orbm_vocab orbm_vocab_t;
 int orbm_vocab_load_text(orbm_t*, orbm_vocab_t** out, const char* path);     /* loadFromTextFile, :1338-1440 */
 int orbm_vocab_create(orbm_t*, orbm_vocab_t** out, int k, int L, int nnodes, const int32_t* parent, const uint8_t* is_leaf,

@@ -1630,6 +1630,13 @@ int orbm_vocab_load_text(orbm_t* m, orbm_vocab_t** out, const char* path) {
     if (fscanf(f, "%d %d %d %d", &k, &L, &n1, &n2) != 4 || k < 0 || k > 20 || L < 1 || L > 10 || n1 < 0 || n1 > 5 || n2 < 0 || n2 > 3) {
         fclose(f); set_merr("vocabulary %s: not a correct text file", path); return ORBM_E_INVALID;       // :1359-1363
     }
+    // the reference switches transform on the two fields (:1145-1193: addWeight or addIfNotExist, L1 / L2 / division by v.size());
+    // orbm_bow_vectors implements TF_IDF (0) + L1_NORM (0), ORBvoc's header, and nothing else
+    if (n1 != 0 || n2 != 0) {
+        fclose(f);
+        set_merr("vocabulary %s: scoring %d / weighting %d in the header; only scoring 0 (L1_NORM) with weighting 0 (TF_IDF) is implemented", path, n1, n2);
+        return ORBM_E_INVALID;
+    }
     std::vector<int> parent(1, 0);
     std::vector<uint8_t> leaf(1, 0), desc(32, 0);
     std::vector<double> weight(1, 0.0);

@@ -70,6 +70,20 @@ def test_vocab_errors(pkg, tmp_path):
     bad = tmp_path / "bad.txt"; bad.write_text("99 3 0 0\n")
     with pytest.raises(pkg.OrbError):
         pkg.ORBVocabulary(m, str(bad))
+    # the header's scoring / weighting pair: the reference switches transform on it (TemplatedVocabulary.h:1145-1193), orbm_bow_vectors
+    # implements `0 0` (L1_NORM, TF_IDF) only, so every other pair inside :1359's ranges is refused, by name
+    import ctypes as C
+    node = "0 1 " + " ".join(["7"] * 32) + " 1.5\n"
+    for scoring, weighting in ((1, 0), (0, 1), (5, 3), (0, 2), (2, 0)):
+        bad.write_text("10 3 %d %d\n" % (scoring, weighting) + node * 3)
+        h = C.c_void_p()
+        assert m.L.orbm_vocab_load_text(m.h, C.byref(h), str(bad).encode()) == -2 and not h.value      # ORBM_E_INVALID
+        msg = m.L.orbm_last_error().decode()
+        assert "scoring %d" % scoring in msg and "weighting %d" % weighting in msg, msg
+        with pytest.raises(pkg.OrbError):
+            pkg.ORBVocabulary(m, str(bad))
+    bad.write_text("10 3 0 0\n" + node * 3)
+    assert pkg.ORBVocabulary(m, str(bad)).info() == dict(k=10, L=3, nnodes=4, nwords=3)
 
 
 def test_bow_transform_at_orbvoc_scale(pkg, oracle, synth):
