@@ -505,7 +505,7 @@ int orbm_bow_transform_batch_async(orbm_t*, const orbm_vocab_t* vocab, const uin
 /* orbm_search_by_bow_batch_async: M7 SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) -- Tracking::TrackReferenceKeyFrame
  * (Tracking.cc:3002-3015, nnratio 0.7) and Tracking::Relocalization (Tracking.cc:4175-4215, nnratio 0.75, one call per candidate
  * KeyFrame) -- END TO END on the device for `npairs` pairs (ORBmatcher.cc:314-547, the Nleft == -1 part; the fisheye / right-camera
- * branch :406-433, :471-498 stays with orbm_search_by_bow_fisheye).  Two pools of rows: the KeyFrame pool has nkf_rows rows of cap_kf
+ * branch :406-433, :471-498 is orbm_search_by_bow_fisheye_batch_async below).  Two pools of rows: the KeyFrame pool has nkf_rows rows of cap_kf
  * slots -- kps_kf (mvKeysUn), desc_kf [..][32], counts_kf [nkf_rows], node_kf / weight_kf (orbm_bow_transform_batch_async over the
  * rows), good_kf (pMP && !pMP->isBad()) --, the frame pool nf_rows rows of cap_f slots with the same arrays but good.  An extractor
  * result block is one valid pool, a caller-gathered array of KeyFrame rows in the same layout another.  Pair p matches KF row kf_row[p]
@@ -529,6 +529,43 @@ int orbm_search_by_bow_batch_async(orbm_t*, int npairs,
                                    const int32_t* node_f, const double* weight_f,
                                    const int32_t* kf_row, const int32_t* f_row, float nnratio, int check_orientation,
                                    int32_t* f_match, int32_t* nmatches);
+/* orbm_search_by_bow_fisheye_batch_async: M7 SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) with F.Nleft != -1 (a two-camera rig:
+ * ORBmatcher.cc:343-545 with the else branch of :406-433 and the nested acceptance of :438-500) -- Tracking::TrackReferenceKeyFrame
+ * (Tracking.cc:3006) and one call per candidate KeyFrame of Tracking::Relocalization (Tracking.cc:4201) -- END TO END on the device for
+ * `npairs` pairs; the device form of orbm_search_by_bow_fisheye.  The KeyFrame pool is exactly that of orbm_search_by_bow_batch_async
+ * (nkf_rows rows of cap_kf slots, kf_row[p], NULL = row p); a two-camera KeyFrame is ONE stacked row, left features then right, as
+ * pKF->mDescriptors and vpMapPointsKF are stacked, and the caller puts the mvKeys / mvKeysRight angles into kps_kf (only `angle` is
+ * read, :447-450).  The frame pool has nf_rows rows of cap_f slots (kps_f, desc_f, counts_f, node_f, weight_f: an extractor result block
+ * and orbm_bow_transform_batch_async over its rows).  The three differences from orbm_search_by_bow_batch_async:
+ *  1. Two frame rows per pair.  Pair p uses left row fl_row[p] (mvKeys) and right row fr_row[p] (mvKeysRight); both arrays are required
+ *     (one lost frame meets N relocalization candidates by repeating its two rows).  realIdxF is j for left slot j and Nleft + j for
+ *     right slot j, Nleft = counts_f[fl_row[p]]: a bucket is walked left entries first, then right, each in ascending slot.
+ *  2. The nested acceptance.  Per KeyFrame feature in bucket order, over the bucket's unclaimed frame features of the same node, the left
+ *     candidates give bestDist1 / bestIdxF / bestDist2 and the right ones bestDist1R / bestIdxFR (first minimum in index order, the
+ *     if / else-if runner-up).  The left slot is claimed iff bestDist1 <= TH_LOW and (float)bestDist1 < nnratio * (float)bestDist2.  The
+ *     right slot is claimed iff bestDist1 <= TH_LOW (the LEFT distance) and bestDist1R <= TH_LOW: its ratio test is switched off by
+ *     `|| true` (:473), it does not wait for the left ratio test to pass, and it never happens where the node holds no unclaimed left
+ *     candidate.  A claimed slot of either camera is skipped by later KeyFrame features (:409).
+ *  3. Two output rows and ONE histogram.  check_orientation fills one 30-bin histogram with both cameras' claims (rot = angle_kf - angle
+ *     of the claimed row's keypoint, factor 30/360.0f, round, bin 30 -> 0); after the three-maxima cull an entry of another bin becomes
+ *     -1 in the row that holds it and counts down once.  Outputs (device): f_match_l, f_match_r [npairs][cap_f] = KeyFrame feature index
+ *     or -1, padded with -1; nmatches [npairs] = the return value of orbm_search_by_bow_fisheye.
+ * Stopped words (weight <= 0; NULL weight = none), KeyFrame features with good_kf == 0 and slots >= count are left out as in M7.  A pair
+ * whose kf_row, fl_row or fr_row is out of range gets two all -1 rows and 0.  The bucket lists and the claimed row run over both cameras
+ * in LDS as ushorts: 2 * cap_kf + 8 * cap_f + 10408 bytes <= 160 KB, published as cap_f <= ORBM_BOW_FISHEYE_MAX_CAP_F PER CAMERA with
+ * cap_kf <= ORBM_BOW_MAX_CAP (157864 bytes, the footprint of M7 at its own cap).  All pointers are device pointers; enqueue-only, no
+ * scratch: every call can be captured (orbx_capture_begin) once one eager call with the same or larger caps has run.  ORBM_E_INVALID: a
+ * NULL required array (kf_row and the weights may be NULL), npairs, nkf_rows, nf_rows, cap_kf or cap_f < 1, nnratio not finite;
+ * ORBM_E_CAPACITY: cap_kf > ORBM_BOW_MAX_CAP, cap_f > ORBM_BOW_FISHEYE_MAX_CAP_F, npairs > 65535.  Every check runs before the device is
+ * touched; nothing is enqueued then. */
+enum { ORBM_BOW_FISHEYE_MAX_CAP_F = 12288 };
+int orbm_search_by_bow_fisheye_batch_async(orbm_t*, int npairs,
+                                           int nkf_rows, int cap_kf, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                           const int32_t* node_kf, const double* weight_kf, const uint8_t* good_kf,
+                                           int nf_rows, int cap_f, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                           const int32_t* node_f, const double* weight_f,
+                                           const int32_t* kf_row, const int32_t* fl_row, const int32_t* fr_row, float nnratio, int check_orientation,
+                                           int32_t* f_match_l, int32_t* f_match_r, int32_t* nmatches);
 /* orbm_search_by_bow_kf_batch_async: M8 SearchByBoW(KeyFrame* pKF1, KeyFrame* pKF2, vpMatches12) -- LoopClosing::DetectCommonRegionsFromBoW
  * (LoopClosing.cc:822, matcher(0.9, true): the current KeyFrame against every candidate and its covisibles) -- END TO END on the device for
  * `npairs` pairs (ORBmatcher.cc:955-1105, Nleft == -1; fisheye KeyFrames stay with orbm_search_by_bow_kf).  Two pools of rows as in

@@ -710,6 +710,16 @@ class _SearchMixin:
                        float(nnratio), int(check_ori), _p(fm))
         return n, fm
 
+    def SearchByBoWFisheyeBatchAsync(self, npairs, nkf_rows, cap_kf, kps_kf, desc_kf, counts_kf, node_kf, weight_kf, good_kf,
+                                     nf_rows, cap_f, kps_f, desc_f, counts_f, node_f, weight_f, kf_row, fl_row, fr_row, nnratio, check_ori,
+                                     f_match_l, f_match_r, nmatches):
+        """SearchByBoWFisheye for a batch, enqueue only: every array argument is a device pointer (include/orbm.h:
+        orbm_search_by_bow_fisheye_batch_async).  The product only: the oracle has the single-pair form alone."""
+        return _chk(self.L.orbm_search_by_bow_fisheye_batch_async(self.h, npairs, nkf_rows, cap_kf, kps_kf, desc_kf, counts_kf, node_kf, weight_kf, good_kf,
+                                                                  nf_rows, cap_f, kps_f, desc_f, counts_f, node_f, weight_f, kf_row, fl_row, fr_row,
+                                                                  float(nnratio), int(check_ori), f_match_l, f_match_r, nmatches),
+                    "orbm_search_by_bow_fisheye_batch_async")
+
     def SearchBySim3(self, kf1, kf2, sf1, sf2, q1, q2, th):
         """q1 / q2: dicts with valid, u, v, level, qdesc for the KF1->KF2 and KF2->KF1 projections."""
         m12 = np.full(kf1.n, -1, np.int32)
@@ -789,7 +799,7 @@ def _install_search():
                                       C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
     for name in ("grid_build", "SearchByProjectionFrame", "SearchByProjectionPoints", "SearchForInitialization",
                  "SearchForTriangulation", "SearchForTriangulationGated", "SearchByBoW", "SearchByProjectionKF", "SearchByBoWKF", "SearchByProjectionSim3", "Fuse", "SearchBySim3", "SearchByProjectionFrameFisheye",
-                 "SearchByProjectionPointsFisheye", "SearchByBoWFisheye", "SearchByProjectionFrameResident", "SearchByProjectionPointsResident", "_call"):
+                 "SearchByProjectionPointsFisheye", "SearchByBoWFisheye", "SearchByBoWFisheyeBatchAsync", "SearchByProjectionFrameResident", "SearchByProjectionPointsResident", "_call"):
         setattr(ORBmatcher, name, getattr(_SearchMixin, name))
     ORBmatcher._prefix = "orbm_"
 
@@ -851,6 +861,9 @@ def _install_search():
     L.orbm_search_by_bow_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, KF pool
                                                  ci, ci, vp, vp, vp, vp, vp,               # frame pool
                                                  vp, vp, cf, ci, vp, vp]                   # kf_row, f_row, nnratio, check_ori, outputs
+    L.orbm_search_by_bow_fisheye_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, KF pool (stacked rows)
+                                                         ci, ci, vp, vp, vp, vp, vp,               # frame pool
+                                                         vp, vp, vp, cf, ci, vp, vp, vp]           # kf_row, fl_row, fr_row, nnratio, check_ori, outputs
     L.orbm_search_by_bow_kf_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp,   # pairs, pool 1 (pKF1)
                                                     ci, ci, vp, vp, vp, vp, vp, vp,            # pool 2 (pKF2)
                                                     vp, vp, cf, ci, vp, vp]                    # row1, row2, nnratio, check_ori, outputs
@@ -990,7 +1003,8 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
             "orbm_search_by_projection_frame_fisheye_batch_async",
-            "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_fuse_batch_async",
+            "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_search_by_bow_fisheye_batch_async",
+            "orbm_fuse_batch_async",
             "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",
             "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",

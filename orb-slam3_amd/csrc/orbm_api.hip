@@ -2156,6 +2156,44 @@ int orbm_search_by_bow_batch_async(orbm_t* m, int npairs,
     return ORBM_OK;
 }
 
+int orbm_search_by_bow_fisheye_batch_async(orbm_t* m, int npairs,
+                                           int nkf_rows, int cap_kf, const orbm_kp_t* kps_kf, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                           const int32_t* node_kf, const double* weight_kf, const uint8_t* good_kf,
+                                           int nf_rows, int cap_f, const orbm_kp_t* kps_f, const uint8_t* desc_f, const int32_t* counts_f,
+                                           const int32_t* node_f, const double* weight_f,
+                                           const int32_t* kf_row, const int32_t* fl_row, const int32_t* fr_row, float nnratio, int check_orientation,
+                                           int32_t* f_match_l, int32_t* f_match_r, int32_t* nmatches) {
+    if (!m || !kps_kf || !desc_kf || !counts_kf || !node_kf || !good_kf || !kps_f || !desc_f || !counts_f || !node_f || !fl_row || !fr_row ||
+        !f_match_l || !f_match_r || !nmatches) {
+        set_merr("SearchByBoW fisheye batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || nkf_rows < 1 || nf_rows < 1 || cap_kf < 1 || cap_f < 1 || !std::isfinite(nnratio)) {
+        set_merr("SearchByBoW fisheye batch: npairs, nkf_rows, nf_rows, cap_kf and cap_f must be >= 1 and nnratio finite");
+        return ORBM_E_INVALID;
+    }
+    if (cap_kf > ORBM_BOW_MAX_CAP || cap_f > ORBM_BOW_FISHEYE_MAX_CAP_F) {
+        set_merr("SearchByBoW fisheye batch: cap_kf %d above %d or cap_f %d above %d per camera (the bucket lists and the row over both cameras live in LDS)",
+                 cap_kf, (int)ORBM_BOW_MAX_CAP, cap_f, (int)ORBM_BOW_FISHEYE_MAX_CAP_F);
+        return ORBM_E_CAPACITY;
+    }
+    if (npairs > 65535) { set_merr("SearchByBoW fisheye batch: %d pairs in one call (at most 65535)", npairs); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t lds = bow_search_lds(cap_kf, 2 * cap_f);                   // the frame list and the claimed row run over both cameras
+    if (lds > 48 * 1024)                                                     // as orbm_search_by_bow_batch_async: always the largest legal size
+        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_search_fisheye, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)bow_search_lds(ORBM_BOW_MAX_CAP, 2 * ORBM_BOW_FISHEYE_MAX_CAP_F)));
+    BowSide K{(const KpIn*)kps_kf, desc_kf, counts_kf, node_kf, weight_kf, good_kf, nkf_rows, cap_kf};
+    BowSide F{(const KpIn*)kps_f, desc_f, counts_f, node_f, weight_f, nullptr, nf_rows, cap_f};
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_bow_search_fisheye, dim3(npairs), dim3(BOW_WAVES * 64), lds, m->stream, npairs, K, F, kf_row, fl_row, fr_row, nnratio,
+                       check_orientation, f_match_l, f_match_r, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 int orbm_search_by_bow_kf_batch_async(orbm_t* m, int npairs,
                                       int nrows1, int cap1, const orbm_kp_t* kps1, const uint8_t* desc1, const int32_t* counts1,
                                       const int32_t* node1, const double* weight1, const uint8_t* good1,

@@ -3099,8 +3099,28 @@ __device__ __forceinline__ bool bow_live(const BowSide& s, size_t o, int i, int 
     return i < n && (!s.weight || s.weight[o + i] > 0) && (!s.good || s.good[o + i]);
 }
 
-// the stable (node & 255) buckets of row `o` of side s: start [257], list [n live entries] (whole workgroup)
-__device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* start, int* red, unsigned short* list) {
+// One row of a pool as a bucket source: index i is slot i of row `o`.
+struct BowRow {
+    const BowSide& s; size_t o; int n;
+    __device__ __forceinline__ bool live(int i) const { return bow_live(s, o, i, n); }
+    __device__ __forceinline__ int node(int i) const { return s.node[o + i]; }
+};
+// Two rows of one pool as ONE index space [0, nl + nr): the reference's realIdxF of a two-camera Frame (left slot j is j, right slot j
+// is Nleft + j, ORBmatcher.cc:406).  at(i) is the pool offset of combined index i.
+struct BowRowPair {
+    const BowSide& s; size_t ol, orr; int nl, n;
+    __device__ __forceinline__ size_t at(int i) const { return i < nl ? ol + i : orr + (i - nl); }
+    __device__ __forceinline__ bool live(int i) const {
+        if (i >= n) return false;
+        const size_t g = at(i);
+        return !s.weight || s.weight[g] > 0;
+    }
+    __device__ __forceinline__ int node(int i) const { return s.node[at(i)]; }
+};
+
+// the stable (node & 255) buckets of the n indices of src: start [257], list [n live entries] (whole workgroup)
+template <class Src>
+__device__ void bow_buckets_of(const Src& src, int n, int* cur, int* start, int* red, unsigned short* list) {
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
     for (int e = tid; e < BOW_WAVES * 256; e += BOW_WAVES * 64) cur[e] = 0;
     __syncthreads();
@@ -3108,7 +3128,7 @@ __device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* st
     const int lo = min(w * per, n), hi = min(lo + per, n);
     for (int i0 = lo; i0 < hi; i0 += 64) {
         const int i = i0 + lane;
-        if (i < hi && bow_live(s, o, i, n)) atomicAdd(&cur[w * 256 + (s.node[o + i] & 255)], 1);
+        if (i < hi && src.live(i)) atomicAdd(&cur[w * 256 + (src.node(i) & 255)], 1);
     }
     __syncthreads();
     int c[BOW_WAVES], tot = 0, ex = 0;
@@ -3131,8 +3151,8 @@ __device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* st
     __syncthreads();
     for (int i0 = lo; i0 < hi; i0 += 64) {
         const int i = i0 + lane;
-        const bool ok = i < hi && bow_live(s, o, i, n);
-        const int h = ok ? (s.node[o + i] & 255) : 0;
+        const bool ok = i < hi && src.live(i);
+        const int h = ok ? (src.node(i) & 255) : 0;
         u64 eq = __ballot(ok);
 #pragma unroll
         for (int b = 0; b < 8; ++b) {
@@ -3148,6 +3168,9 @@ __device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* st
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
+}
+__device__ void bow_buckets(const BowSide& s, size_t o, int n, int* cur, int* start, int* red, unsigned short* list) {
+    bow_buckets_of(BowRow{s, o, n}, n, cur, start, red, list);
 }
 
 // KF = true is M8, ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12) (ORBmatcher.cc:955-1105, NLeft == -1): K is pKF1 (the outer
@@ -3263,6 +3286,140 @@ __global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search(int npairs, BowSi
         if (KF) { if (v) out[v - 1] = j; }                                   // vpMatches12[idx1] = idx2
         else if (j < F.cap) out[j] = v - 1;
         nm += __popcll(__ballot(v != 0));
+    }
+    if (lane == 0 && nm) atomicAdd(&red[0], nm);
+    __syncthreads();
+    if (tid == 0) nmatches[p] = red[0];
+}
+
+// k_bow_search_fisheye: M7 with F.Nleft != -1 (the else branch of ORBmatcher.cc:406-433 and the nested acceptance of :438-500) for a
+// batch of (KF row, left frame row, right frame row) triples; k_bow_search<false> with these differences.
+//  - The frame side is the COMBINED index space of BowRowPair, nl = count of the left row: one stable counting sort over [0, nl + nr)
+//    leaves every hash list in ascending realIdxF, left entries before right ones, as the reference walks a bucket.  flist and the
+//    claimed row hold combined indices (at most 2 * cap_f each; the caller sizes the LDS with bow_search_lds(cap_kf, 2 * cap_f)).
+//  - A lane keeps the two smallest keys of its LEFT candidates (bestDist1 / bestIdxF / bestDist2) and the smallest key of its RIGHT ones
+//    (bestDist1R / bestIdxFR).  bestDist2R feeds only a ratio test that `|| true` switches off (:473), so it is not computed.
+//  - bestDist1 <= TH_LOW opens both claims (:438): the left slot under the ratio test, the right slot under bestDist1R <= TH_LOW alone.
+//    A node without an unclaimed left candidate leaves bestDist1 at 256 and claims nothing in either camera.
+//  - One histogram over both cameras' claims, rebuilt from the finished row (a slot is claimed at most once, so the row holds one
+//    entry per rotHist entry); the tail splits the row into the two output rows, each padded with -1 to F.cap.
+__global__ __launch_bounds__(BOW_WAVES * 64) void k_bow_search_fisheye(int npairs, BowSide K, BowSide F, const int* __restrict__ kf_row,
+                                                                       const int* __restrict__ fl_row, const int* __restrict__ fr_row,
+                                                                       float nnratio, int check_ori, int* __restrict__ f_match_l,
+                                                                       int* __restrict__ f_match_r, int* __restrict__ nmatches) {
+    extern __shared__ int bow_lds[];
+    int* cur = bow_lds;
+    int* kstart = cur + BOW_WAVES * 256;
+    int* fstart = kstart + 257;
+    unsigned int* hist = (unsigned int*)(fstart + 257);
+    int* red = (int*)(hist + 32);
+    unsigned short* klist = (unsigned short*)(red + 8);
+    unsigned short* flist = klist + K.cap;
+    unsigned short* row = flist + 2 * F.cap;
+    const int p = blockIdx.x, tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+    int* out_l = f_match_l + (size_t)p * F.cap;
+    int* out_r = f_match_r + (size_t)p * F.cap;
+    const int kr = kf_row ? kf_row[p] : p, fl = fl_row[p], fr = fr_row[p];
+    if (kr < 0 || kr >= K.nrows || fl < 0 || fl >= F.nrows || fr < 0 || fr >= F.nrows) {   // (block-uniform) two empty rows
+        for (int j = tid; j < F.cap; j += BOW_WAVES * 64) { out_l[j] = -1; out_r[j] = -1; }
+        if (tid == 0) nmatches[p] = 0;
+        return;
+    }
+    const size_t ko = (size_t)kr * K.cap;
+    const int nk = min(max(K.counts[kr], 0), K.cap);
+    const int nl = min(max(F.counts[fl], 0), F.cap), nr = min(max(F.counts[fr], 0), F.cap), nf = nl + nr;
+    const BowRowPair FP{F, (size_t)fl * F.cap, (size_t)fr * F.cap, nl, nf};
+    for (int j = tid; j < 2 * F.cap; j += BOW_WAVES * 64) row[j] = 0;
+    bow_buckets(K, ko, nk, cur, kstart, red, klist);
+    bow_buckets_of(FP, nf, cur, fstart, red, flist);
+    const unsigned INV = 0xFFFFFFFFu;
+    for (int h = w; h < 256; h += BOW_WAVES) {
+        const int ks = kstart[h], ke = kstart[h + 1], fs = fstart[h], fe = fstart[h + 1];
+        if (ks == ke || fs == fe) continue;
+        int fj0 = -1, fn0 = 0;                                               // the first 64 frame candidates, for the whole bucket
+        u64 fd0[4] = {0, 0, 0, 0};
+        if (fs + lane < fe) { fj0 = flist[fs + lane]; const size_t g = FP.at(fj0); fn0 = F.node[g]; load_desc(F.desc + g * 32, fd0); }
+        for (int kb = ks; kb < ke; kb += 64) {
+            int ki = -1, kn = 0;
+            u64 kd[4] = {0, 0, 0, 0};
+            if (kb + lane < ke) { ki = klist[kb + lane]; kn = K.node[ko + ki]; load_desc(K.desc + (ko + ki) * 32, kd); }
+            const int kcnt = min(64, ke - kb);
+            for (int t = 0; t < kcnt; ++t) {
+                const int i = __builtin_amdgcn_readlane(ki, t), nd = __builtin_amdgcn_readlane(kn, t);
+                u64 a[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) a[q] = readlane64(kd[q], t);
+                unsigned l1 = INV, l2 = INV, r1 = INV;                       // left: the lane's two smallest keys; right: its smallest
+                if (fj0 >= 0 && fn0 == nd && row[fj0] == 0) {
+                    const unsigned key = ((unsigned)ham256(a, fd0[0], fd0[1], fd0[2], fd0[3]) << 16) | (unsigned)lane;
+                    if (fj0 < nl) l1 = key; else r1 = key;
+                }
+                for (int fb = fs + 64; fb < fe; fb += 64) {                  // buckets longer than 64
+                    const int pos = fb + lane;
+                    if (pos < fe) {
+                        const int j = flist[pos];
+                        const size_t g = FP.at(j);
+                        if (F.node[g] == nd && row[j] == 0) {
+                            u64 d4[4];
+                            load_desc(F.desc + g * 32, d4);
+                            const unsigned key = ((unsigned)ham256(a, d4[0], d4[1], d4[2], d4[3]) << 16) | (unsigned)(pos - fs);
+                            if (j >= nl) r1 = min(r1, key);
+                            else if (key < l1) { l2 = l1; l1 = key; }
+                            else if (key < l2) l2 = key;
+                        }
+                    }
+                }
+                const unsigned m1 = wave_min_u32(l1);
+                if (m1 == INV || (int)(m1 >> 16) > 50) continue;             // TH_LOW on the LEFT distance gates both cameras, :438
+                const unsigned m2 = wave_min_u32(l1 == m1 ? l2 : l1);       // the winner's lane offers its runner-up
+                const unsigned mr = wave_min_u32(r1);
+                const int d1 = (int)(m1 >> 16), d2 = m2 == INV ? 256 : (int)(m2 >> 16);
+                const bool takeL = (float)d1 < nnratio * (float)d2;         // :441
+                const bool takeR = mr != INV && (int)(mr >> 16) <= 50;      // :471; the ratio test of :473 is `|| true`
+                if (takeL || takeR) {
+                    if (lane == 0) {
+                        if (takeL) row[flist[fs + (m1 & 0xFFFFu)]] = (unsigned short)(i + 1);
+                        if (takeR) row[flist[fs + (mr & 0xFFFFu)]] = (unsigned short)(i + 1);
+                    }
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
+        }
+    }
+    __syncthreads();
+    const float factor = 30 / 360.0f;                                        // HISTO_LENGTH / 360.0f, :334
+    auto bin_of = [&](int j, int v) {                                        // :459-464 and :490-495: mvKeys / mvKeysRight by camera
+        float rot = K.kps[ko + v - 1].angle - F.kps[FP.at(j)].angle;
+        if (rot < 0.0f) rot += 360.0f;
+        int bin = (int)roundf(rot * factor);
+        if (bin == 30) bin = 0;
+        return bin;
+    };
+    if (check_ori) {
+        if (tid < 32) hist[tid] = 0;
+        __syncthreads();
+        for (int j = tid; j < nf; j += BOW_WAVES * 64) {
+            const int v = row[j];
+            if (v) { const int bin = bin_of(j, v); if (bin >= 0 && bin < 30) atomicAdd(&hist[bin], 1u); }
+        }
+        __syncthreads();
+        const Max3 m3 = three_maxima(hist);
+        const int i1 = m3.i1, i2 = m3.i2, i3 = m3.i3;
+        for (int j = tid; j < nf; j += BOW_WAVES * 64) {
+            const int v = row[j];
+            if (v) { const int bin = bin_of(j, v); if (bin >= 0 && bin < 30 && bin != i1 && bin != i2 && bin != i3) row[j] = 0; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) red[0] = 0;
+    __syncthreads();
+    int nm = 0;
+    for (int j0 = w * 64; j0 < F.cap; j0 += BOW_WAVES * 64) {                // every output slot is written once, by this thread alone
+        const int j = j0 + lane;
+        const int vl = j < nl ? (int)row[j] : 0, vr = j < nr ? (int)row[nl + j] : 0;
+        if (j < F.cap) { out_l[j] = vl - 1; out_r[j] = vr - 1; }
+        nm += __popcll(__ballot(vl != 0)) + __popcll(__ballot(vr != 0));
     }
     if (lane == 0 && nm) atomicAdd(&red[0], nm);
     __syncthreads();

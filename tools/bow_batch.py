@@ -11,7 +11,13 @@ line per measurement.
 
 --fuzz N: N random calls (pairs per call, feature counts, nnratio 0.5-1.0, rotation check, good-mask rate, levelsup 1 .. L on a (10, 3)
 or (10, 4) vocabulary, stopped words, NULL weights, out-of-range rows) compared pair by pair with the oracle's SearchByBoW; prints
-one JSON line with the mismatch count."""
+one JSON line with the mismatch count.
+
+--fisheye: the two-camera M7 (F.Nleft != -1) at the C4 shape -- 512 x 512, 1500 features per camera, the same vocabulary, levelsup 4 --
+for 1 / 8 / 64 (stacked KeyFrame row, left frame row, right frame row) triples: orbm_search_by_bow_fisheye_batch_async against the loop
+of host orbm_search_by_bow_fisheye calls it replaces, and against the one-camera orbm_search_by_bow_batch_async on the left rows
+alone.  The three are timed in alternation (host clock around enqueue + sync for the device calls), at least 30 calls each; medians
+with quartiles, one JSON line per measurement.  All rows must be equal."""
 import argparse
 import ctypes as C
 import importlib
@@ -42,16 +48,17 @@ def fv(nodes, keep):
 class Pool:
     """Device images -> one extractor result block -> node ids and weights of every slot."""
 
-    def __init__(self, imgs, nfeatures, m):
+    def __init__(self, imgs, nfeatures, m, w=W, h=H):
         self.L = pkg.lib()
-        stride = (W + 63) // 64 * 64
+        self.w, self.h = w, h
+        stride = (w + 63) // 64 * 64
         self.stride = stride
-        self.dev = pkg.DeviceBuffer(len(imgs) * stride * H)
+        self.dev = pkg.DeviceBuffer(len(imgs) * stride * h)
         for i, im in enumerate(imgs):
-            pad = np.zeros((H, stride), np.uint8); pad[:, :W] = im
-            self.dev.upload(pad, offset=i * stride * H)
-        self.arr = (C.c_void_p * len(imgs))(*[self.dev.ptr + i * stride * H for i in range(len(imgs))])
-        self.ex = pkg.ORBextractor(nfeatures, max_size=(W, H), max_batch=len(imgs))
+            pad = np.zeros((h, stride), np.uint8); pad[:, :w] = im
+            self.dev.upload(pad, offset=i * stride * h)
+        self.arr = (C.c_void_p * len(imgs))(*[self.dev.ptr + i * stride * h for i in range(len(imgs))])
+        self.ex = pkg.ORBextractor(nfeatures, max_size=(w, h), max_batch=len(imgs))
         self.extract()
         self.ex.sync()
         self.r = self.ex.result_device()
@@ -61,7 +68,7 @@ class Pool:
         self.m = m
 
     def extract(self):
-        self.ex.enqueue_device(self.arr, W, H, self.stride, np.zeros(4 * len(self.arr), np.int32))
+        self.ex.enqueue_device(self.arr, self.w, self.h, self.stride, np.zeros(4 * len(self.arr), np.int32))
 
     def transform(self, voc, levelsup):
         assert self.L.orbm_bow_transform_batch_async(self.m.h, voc.h, self.r["desc"], self.rows * self.cap, levelsup, None, self.node.ptr,
@@ -165,6 +172,94 @@ def bench():
     K.ex.close(); F.ex.close()
 
 
+def _q(t):
+    q = np.percentile(np.asarray(t, np.float64), [25, 50, 75])
+    return dict(median=float(q[1]), q25=float(q[0]), q75=float(q[2]), calls=len(t))
+
+
+def fisheye_bench(reps=30):
+    L = pkg.lib()
+    m = pkg.ORBmatcher(0.7)
+    voc = pkg.ORBVocabulary(m, synth.gen_vocabulary(10, 6, seed=7))
+    FW = FH = 512
+    NR, NFEAT = 64, 1500                                                    # rigs, features per camera
+    rng = np.random.default_rng(12)
+    kf_imgs = [synth.gen_stereo_pair(FW, FH, 1300 + i) for i in range(NR)]
+    later = lambda im: np.clip(np.roll(im, 3, axis=1).astype(np.float64) + rng.normal(0, 3.0, im.shape), 0, 255).astype(np.uint8)
+    # frame pool: one result block, rows 0 .. NR-1 left and NR .. 2 NR-1 right (the rig a little later)
+    F = Pool([later(p[0]) for p in kf_imgs] + [later(p[1]) for p in kf_imgs], NFEAT, m, FW, FH)
+    F.transform(voc, 4); F.host()
+    # KeyFrame pool: a caller-gathered pool of STACKED rows (left features then right) from a block of the KeyFrame images
+    G = Pool([p[0] for p in kf_imgs] + [p[1] for p in kf_imgs], NFEAT, m, FW, FH)
+    capk = 2 * G.cap
+    kps = np.zeros((NR, capk), pkg.KP_DTYPE); desc = np.zeros((NR, capk, 32), np.uint8); cnt = np.zeros(NR, np.int32)
+    for r in range(NR):
+        (_, kl, dl), (_, kr, dr) = G.res[r], G.res[NR + r]
+        n = len(kl) + len(kr); cnt[r] = n
+        kps[r, :n] = np.concatenate([kl, kr]); desc[r, :n] = np.concatenate([dl, dr])
+    G.ex.close()
+    dK = {k: pkg.DeviceBuffer(a.nbytes).upload(a) for k, a in (("kps", kps), ("desc", desc), ("counts", cnt))}
+    knode = pkg.DeviceBuffer(4 * NR * capk); kweight = pkg.DeviceBuffer(8 * NR * capk)
+    assert L.orbm_bow_transform_batch_async(m.h, voc.h, dK["desc"].ptr, NR * capk, 4, None, knode.ptr, kweight.ptr) == 0, L.orbm_last_error()
+    m.sync()
+    h_knode = knode.download(np.int32, NR * capk).reshape(NR, capk); h_kweight = kweight.download(np.float64, NR * capk).reshape(NR, capk)
+    good = np.ones((NR, capk), np.uint8); dg = pkg.DeviceBuffer(good.nbytes).upload(good)
+    for P in (1, 8, 64):
+        kf_row = np.arange(P, dtype=np.int32); fl_row = np.arange(P, dtype=np.int32); fr_row = (NR + np.arange(P)).astype(np.int32)
+        dk, dl, dr = [pkg.DeviceBuffer(4 * P).upload(a) for a in (kf_row, fl_row, fr_row)]
+        ml = pkg.DeviceBuffer(4 * P * F.cap); mr = pkg.DeviceBuffer(4 * P * F.cap); nm = pkg.DeviceBuffer(4 * P)
+        m1 = pkg.DeviceBuffer(4 * P * F.cap); n1 = pkg.DeviceBuffer(4 * P)
+
+        def batch():
+            rc = L.orbm_search_by_bow_fisheye_batch_async(m.h, P, NR, capk, dK["kps"].ptr, dK["desc"].ptr, dK["counts"].ptr, knode.ptr, kweight.ptr, dg.ptr,
+                                                          F.rows, F.cap, F.r["kps"], F.r["desc"], F.r["counts"], F.node.ptr, F.weight.ptr,
+                                                          dk.ptr, dl.ptr, dr.ptr, 0.7, 1, ml.ptr, mr.ptr, nm.ptr)
+            assert rc == 0, L.orbm_last_error()
+            m.sync()
+            return m.timing_ms()
+
+        def left_only():
+            rc = L.orbm_search_by_bow_batch_async(m.h, P, NR, capk, dK["kps"].ptr, dK["desc"].ptr, dK["counts"].ptr, knode.ptr, kweight.ptr, dg.ptr,
+                                                  F.rows, F.cap, F.r["kps"], F.r["desc"], F.r["counts"], F.node.ptr, F.weight.ptr,
+                                                  dk.ptr, dl.ptr, 0.7, 1, m1.ptr, n1.ptr)
+            assert rc == 0, L.orbm_last_error()
+            m.sync()
+            return m.timing_ms()
+
+        args = []
+        for p in range(P):
+            (_, kl, dl_), (_, kr, dr_) = F.res[p], F.res[NR + p]
+            nk, nl, nr = int(cnt[p]), len(kl), len(kr)
+            node_f = np.concatenate([F.h_node[p, :nl], F.h_node[NR + p, :nr]]); wt_f = np.concatenate([F.h_weight[p, :nl], F.h_weight[NR + p, :nr]])
+            args.append((np.ascontiguousarray(kps[p, :nk]), np.ascontiguousarray(desc[p, :nk]), good[p, :nk], fv(h_knode[p, :nk], h_kweight[p, :nk] > 0),
+                         np.concatenate([kl, kr]), np.concatenate([dl_, dr_]), nl, fv(node_f, wt_f > 0), 0.7, True))
+
+        def host_loop():
+            return [m.SearchByBoWFisheye(*a) for a in args]
+
+        for _ in range(3):                                                  # warm every path at this shape
+            batch(); left_only(); out = host_loop()
+        rows_l = ml.download(np.int32, P * F.cap).reshape(P, F.cap); rows_r = mr.download(np.int32, P * F.cap).reshape(P, F.cap)
+        counts = nm.download(np.int32, P)
+        same = all(int(counts[p]) == out[p][0] and np.array_equal(rows_l[p, :args[p][6]], out[p][1][:args[p][6]]) and
+                   np.array_equal(rows_r[p, :len(args[p][4]) - args[p][6]], out[p][1][args[p][6]:]) for p in range(P))
+        t = dict(batch_wall=[], batch_dev=[], left_wall=[], left_dev=[], host=[])
+        for _ in range(reps):                                               # alternate the three paths
+            t0 = time.perf_counter(); d = batch(); t["batch_wall"].append((time.perf_counter() - t0) * 1e3); t["batch_dev"].append(d)
+            t0 = time.perf_counter(); d = left_only(); t["left_wall"].append((time.perf_counter() - t0) * 1e3); t["left_dev"].append(d)
+            t0 = time.perf_counter(); host_loop(); t["host"].append((time.perf_counter() - t0) * 1e3)
+        common = dict(shape="c4_fisheye", pairs=P, width=FW, height=FH, features_per_camera=NFEAT, nnratio=0.7, levelsup=4,
+                      mean_left=float(np.mean([a[6] for a in args])), mean_right=float(np.mean([len(a[4]) - a[6] for a in args])))
+        print(json.dumps(dict(path="fisheye_batch", **common, wall_ms_per_call=_q(t["batch_wall"]), device_ms_per_call=_q(t["batch_dev"]),
+                              matches=int(counts.sum()), rows_equal_host=bool(same))), flush=True)
+        print(json.dumps(dict(path="one_camera_batch_left_rows", **common, wall_ms_per_call=_q(t["left_wall"]), device_ms_per_call=_q(t["left_dev"]),
+                              matches=int(n1.download(np.int32, P).sum()))), flush=True)
+        print(json.dumps(dict(path="fisheye_host_loop", **common, wall_ms_per_batch=_q(t["host"]),
+                              wall_ms_per_call=float(np.median(t["host"])) / P)), flush=True)
+        assert same, "batched rows differ from the host rows"
+    F.ex.close()
+
+
 def fuzz(n, seed):
     import orbref
     orbref.lib()
@@ -226,7 +321,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--fuzz", type=int, default=0)
     ap.add_argument("--seed", type=int, default=7)
+    ap.add_argument("--fisheye", action="store_true")
     a = ap.parse_args()
+    if a.fisheye:
+        fisheye_bench()
+        sys.exit(0)
     if a.fuzz:
         sys.exit(1 if fuzz(a.fuzz, a.seed) else 0)
     bench()
