@@ -276,7 +276,7 @@ int orbm_track_window_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* 
                                   float dx, float dy, int32_t* best_idx, int32_t* best_dist, int32_t* second_dist);
 /* orbm_search_by_projection_points_batch_async: M3 SearchByProjection(Frame, vector<MapPoint*>, th, bFarPoints, thFarPoints) --
  * Tracking::SearchLocalPoints -- END TO END on the device for `nframes` frames of one result block (ORBmatcher.cc:45-166, the
- * left-camera part; the Nleft != -1 block :170-236 stays with orbm_search_by_projection_points_fisheye).  Frame f of the call is
+ * left-camera part; the Nleft != -1 block :170-236 is orbm_search_by_projection_points_fisheye_batch_async below).  Frame f of the call is
  * block frame t_first+f; it is searched through its grid (orbm_grid_build_batch_async over the block, indexed by block frame id).
  * Every other per-frame array has one row per frame of the call: uright [nframes][cap] (mvuRight, e.g. orbm_stereo_batch_async with
  * first_l == t_first; NULL = no stereo gate), t_blocked [nframes][cap] (mvpMapPoints[i] && Observations() > 0; NULL = none).
@@ -368,6 +368,59 @@ int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t*, const orbm_kp_t
                                                         const int32_t* octave, const float* angle, const uint8_t* qdesc, const uint8_t* mp_obs,
                                                         float th, int retry_below, const float* scale_factors_host, int nlevels, int check_orientation,
                                                         int32_t* match_l, int32_t* match_r, int32_t* nmatches, uint8_t* retried);
+/* orbm_search_by_projection_points_fisheye_batch_async: M3 SearchByProjection(Frame, vector<MapPoint*>, th, bFarPoints, thFarPoints) with
+ * F.Nleft != -1 -- Tracking::SearchLocalPoints on a fisheye stereo rig -- END TO END on the device for `npairs` pairs
+ * (ORBmatcher.cc:45-239, the right-camera block :170-236 and the mvLeftToRightMatch / mvRightToLeftMatch cross writes included); the
+ * device form of orbm_search_by_projection_points_fisheye.  Pool and grid are those of
+ * orbm_search_by_projection_frame_fisheye_batch_async: one pool of rows of `cap` slots with the grid of orbm_grid_build_batch_async
+ * over it, pair p searches left row first_l+p and right row first_r+p.  Every other array has one row per pair of the call:
+ * blocked_l, blocked_r [npairs][cap] (mvpMapPoints[idx] / [idx + Nleft] holds a MapPoint with Observations() > 0, :102-104 /
+ * :194-196; NULL = none), l2r, r2l [npairs][cap] int32 (mvLeftToRightMatch / mvRightToLeftMatch: -1 or the partner slot; NULL = all
+ * -1), and the queries: nq [npairs] local map points per pair in rows of q_stride entries -- in_view, proj_x, proj_y, view_cos, level
+ * (mbTrackInView, mTrackProjX, mTrackProjY, mTrackViewCos, mnTrackScaleLevel) and in_view_r, proj_xr, proj_yr, view_cos_r, level_r
+ * (the ...R fields); the frustum test of a KannalaBrandt8 camera stays with the caller.  depth [npairs][q_stride] (mTrackDepth; NULL
+ * = bFarPoints off) with th_far; qdesc [..][32] and mp_obs [..] (Observations() > 0) are per pair rows too, or ONE row shared by
+ * every pair when q_shared != 0.  Per pair, in query order, exactly as orbm_search_by_projection_points_fisheye:
+ *   1. a query with neither in_view nor in_view_r, or with depth > th_far, is skipped (:56-60); a skipped query, or a skipped camera
+ *      block, reads nothing else of its row;
+ *   2. the left block (:65-168) runs when in_view is set and level lies in [0, nlevels): radius RadiusByViewingCos(view_cos) [* th if
+ *      th != 1] * scale[level], levels [level-1, level], no stereo gate (:107), best / second over the candidates whose slot is not in
+ *      the left blocked set by `dist < bestDist` / `else if dist < bestDist2` with the level of each (:125-141);
+ *   3. a left claim needs bestDist <= TH_HIGH (:147) and passes when the levels differ or bestDist <= nnratio * bestDist2 (:154): it
+ *      writes match_l[best] and counts 1, and if l2r[best] != -1 it also writes match_r[l2r[best]] and counts 1 more (:157-161); the
+ *      cross write does not look at the blocked set and overwrites whatever that slot holds;
+ *   4. a same-level ratio rejection in the left block is the `continue` of :151-152: it ends the query, right block included; an
+ *      empty left window (:85), a left best above TH_HIGH and a left window whose candidates are all blocked do not, the right block
+ *      still runs after them;
+ *   5. the right block (:170-236) runs when in_view_r is set and level_r lies in [0, nlevels) (level_r == -1 is the reference's own
+ *      skip, :172): radius RadiusByViewingCos(view_cos_r) * scale[level_r] with NO th factor (:173-176), the same best / second and
+ *      ratio rules (:203-222) against the right blocked set; a claim first writes match_l[r2l[best]] if that is not -1 and counts 1,
+ *      then writes match_r[best] and counts 1 (:224-233);
+ *   6. only a query with mp_obs blocks the slots it wrote -- the cross-written ones too, in the other camera's blocked set -- for
+ *      later searches; the right block of the same query already sees what its left block blocked; a later write may overwrite an
+ *      unblocked slot and counts again;
+ *   7. l2r[k] is honoured only where 0 <= l2r[k] < counts[right row], r2l[k] only where 0 <= r2l[k] < counts[left row]; any other
+ *      value reads as -1 (nothing is written outside a row);
+ *   8. an empty left row does not empty the pair: the right block still runs (unlike M4's :2551).
+ * Outputs (device): match_l, match_r [npairs][cap] = query index or ORBM_NO_MATCH, padded to cap (match_l[k] -> mvpMapPoints[k],
+ * match_r[k] -> mvpMapPoints[Nleft + k]); nmatches [npairs] = the return value of orbm_search_by_projection_points_fisheye.  All
+ * pointers are device pointers except scale_factors_host.  Enqueue-only: the scratch is the handle's grow-only one, so after one
+ * eager call the same or a smaller shape allocates nothing and can be captured (orbx_capture_begin).  ORBM_E_INVALID: a NULL handle
+ * (checked first), a NULL required array (blocked_l, blocked_r, l2r, r2l and depth may be NULL), a count < 1, first_l or first_r < 0;
+ * ORBM_E_CAPACITY: cap > 65535, q_stride > ORBM_LP_MAX_QUERIES, nlevels > 12, npairs > 65535.  Nothing is enqueued then. */
+int orbm_search_by_projection_points_fisheye_batch_async(orbm_t*, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                         const int32_t* grid_start, const int32_t* grid_idx,
+                                                         float min_x, float min_y, float inv_w, float inv_h,
+                                                         int first_l, int first_r, int npairs,
+                                                         const uint8_t* blocked_l, const uint8_t* blocked_r, const int32_t* l2r, const int32_t* r2l,
+                                                         const int32_t* nq, int q_stride,
+                                                         const uint8_t* in_view, const float* proj_x, const float* proj_y,
+                                                         const float* view_cos, const int32_t* level,
+                                                         const uint8_t* in_view_r, const float* proj_xr, const float* proj_yr,
+                                                         const float* view_cos_r, const int32_t* level_r,
+                                                         const float* depth, float th_far, const uint8_t* qdesc, const uint8_t* mp_obs, int q_shared,
+                                                         float th, float nnratio, const float* scale_factors_host, int nlevels,
+                                                         int32_t* match_l, int32_t* match_r, int32_t* nmatches);
 /* orbm_project_last_frame_batch_async: the projection half of M4 (ORBmatcher.cc:2481-2527) for a pinhole camera with Nleft == -1, the
  * producer of the rows above.  Per pair (device): tcw_cur, tcw_last [npairs][12] (row-major 3x4 [R | t]); per query (device): x3dw
  * [npairs][q_stride][3] (world position), has_mp [npairs][q_stride] (pMP && !mvbOutlier), nq [npairs].  Host: k_host = (fx, fy, cx, cy),

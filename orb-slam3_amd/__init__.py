@@ -846,6 +846,11 @@ def _install_search():
                                                                       vp, vp, vp, vp, ci, vp,                       # blocked_l, blocked_r, dir, nq, q_stride, valid
                                                                       vp, vp, vp, vp, vp, vp, vp, vp,               # u, v, ur, vr, octave, angle, qdesc, mp_obs
                                                                       cf, ci, vp, ci, ci, vp, vp, vp, vp]           # th, retry_below, sf, nlevels, check_ori, outputs
+    L.orbm_search_by_projection_points_fisheye_batch_async.argtypes = [vp, vp, vp, vp, ci, vp, vp, cf, cf, cf, cf, ci, ci, ci,   # pool, grid, bounds, first_l, first_r, pairs
+                                                                       vp, vp, vp, vp, vp, ci,                       # blocked_l, blocked_r, l2r, r2l, nq, q_stride
+                                                                       vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,       # the left, then the right frustum rows
+                                                                       vp, cf, vp, vp, ci,                           # depth, th_far, qdesc, mp_obs, q_shared
+                                                                       cf, cf, vp, ci, vp, vp, vp]                   # th, nnratio, sf, nlevels, outputs
     L.orbm_project_last_frame_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp]
     L.orbm_fuse_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp,                 # pairs, KF pool (kps, desc, uright)
                                         vp, vp, cf, cf, cf, cf, vp, vp, vp,         # grid, bounds, kf_row, tcw, ow
@@ -1002,7 +1007,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_by_projection_sim3", "orbm_fuse", "orbm_search_by_sim3",
             "orbm_grid_build_batch_async", "orbm_track_window_batch_async", "orbm_search_by_projection_batch_async",
             "orbm_search_by_projection_points_batch_async", "orbm_search_by_projection_frame_batch_async",
-            "orbm_search_by_projection_frame_fisheye_batch_async",
+            "orbm_search_by_projection_frame_fisheye_batch_async", "orbm_search_by_projection_points_fisheye_batch_async",
             "orbm_project_last_frame_batch_async", "orbm_bow_transform_batch_async", "orbm_search_by_bow_batch_async", "orbm_search_by_bow_fisheye_batch_async",
             "orbm_fuse_batch_async",
             "orbm_search_by_projection_kf_batch_async", "orbm_search_by_bow_kf_batch_async", "orbm_search_by_projection_sim3_batch_async",

@@ -1375,6 +1375,65 @@ int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t* m, const orbm_kp
     return ORBM_OK;
 }
 
+int orbm_search_by_projection_points_fisheye_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
+                                                         const int32_t* grid_start, const int32_t* grid_idx,
+                                                         float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r, int npairs,
+                                                         const uint8_t* blocked_l, const uint8_t* blocked_r, const int32_t* l2r, const int32_t* r2l,
+                                                         const int32_t* nq, int q_stride,
+                                                         const uint8_t* in_view, const float* proj_x, const float* proj_y, const float* view_cos, const int32_t* level,
+                                                         const uint8_t* in_view_r, const float* proj_xr, const float* proj_yr, const float* view_cos_r, const int32_t* level_r,
+                                                         const float* depth, float th_far, const uint8_t* qdesc, const uint8_t* mp_obs, int q_shared,
+                                                         float th, float nnratio, const float* scale_factors_host, int nlevels,
+                                                         int32_t* match_l, int32_t* match_r, int32_t* nmatches) {
+    if (!m) return ORBM_E_INVALID;
+    if (!kps || !desc || !counts || !grid_start || !grid_idx || !nq || !in_view || !proj_x || !proj_y || !view_cos || !level ||
+        !in_view_r || !proj_xr || !proj_yr || !view_cos_r || !level_r || !qdesc || !mp_obs || !match_l || !match_r || !nmatches ||
+        !scale_factors_host) {
+        set_merr("SearchByProjection points fisheye batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (npairs < 1 || cap < 1 || q_stride < 1 || first_l < 0 || first_r < 0 || nlevels < 1) {
+        set_merr("SearchByProjection points fisheye batch: npairs, cap, q_stride and nlevels must be >= 1, first_l and first_r >= 0");
+        return ORBM_E_INVALID;
+    }
+    if (const int rc = lp_capacity("SearchByProjection points fisheye batch", cap, q_stride, nlevels, npairs, "pairs")) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const ScaleTab st = scale_tab(scale_factors_host, nlevels);
+    const size_t lds = (size_t)(2 * ((cap + 31) >> 5) + 2 * 64 * TK_K) * sizeof(unsigned);   // two blocked bit arrays, both cameras' lists of the current 64 queries
+    // scratch of the handle: per query and camera the window population, its TK_K best candidates and its radius
+    const size_t rows = (size_t)npairs * q_stride;
+    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = (rows * sizeof(float) + 255) & ~(size_t)255,
+                 bCam = bCnt + bKeys + bR;
+    uint8_t* scr = batch_scratch(m, 2 * bCam);
+    if (!scr) { set_merr("SearchByProjection points fisheye batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", 2 * bCam); return ORBM_E_HIP; }
+    int* topCnt[2]; unsigned* topKeys[2]; float* topR[2];
+    for (int c = 0; c < 2; ++c) {
+        topCnt[c] = (int*)(scr + c * bCam); topKeys[c] = (unsigned*)(scr + c * bCam + bCnt); topR[c] = (float*)(scr + c * bCam + bCnt + bKeys);
+    }
+    LpRows R;
+    R.nq = nq; R.q_stride = q_stride;
+    R.in_view = in_view; R.px = proj_x; R.py = proj_y; R.pxr = nullptr; R.view_cos = view_cos; R.level = level;   // no stereo gate when Nleft != -1 (ORBmatcher.cc:107)
+    R.depth = depth; R.th_far = th_far;
+    R.qdesc = qdesc; R.mp_obs = mp_obs; R.q_shared = q_shared != 0;
+    R.th = th; R.nlevels = nlevels;
+    LpRows Rr = R;                                                          // the right camera's candidate pass: the mbTrackInViewR fields, no th factor (:173-176)
+    Rr.in_view = in_view_r; Rr.px = proj_xr; Rr.py = proj_yr; Rr.view_cos = view_cos_r; Rr.level = level_r;
+    Rr.th = 1.0f;
+    const MmfLists T{topCnt[0], topKeys[0], topR[0], topCnt[1], topKeys[1], topR[1]};
+    const dim3 gTop((q_stride + 3) / 4, npairs);
+    MHIPCHK(rec_time(m, m->e0));
+    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, topCnt[0], topKeys[0], topR[0]);
+    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, topCnt[1], topKeys[1], topR[1]);
+    hipLaunchKernelGGL(k_lpf_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
+                       min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, l2r, r2l, R, Rr, nnratio, T, match_l, match_r, nmatches);
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 int orbm_project_last_frame_batch_async(orbm_t* m, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
                                         const float* x3dw, const uint8_t* has_mp, const float* k_host, const float* bounds_host, float mb, int mono,
                                         uint8_t* valid, float* u, float* v, float* invzc, uint8_t* dir) {

@@ -2590,6 +2590,155 @@ __global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// M3 with Nleft != -1 (a fisheye rig: ORBmatcher.cc:45-239 with the right-camera block :170-236), final rows on the device.  A pair is
+// a left row and a right row of one pool as for k_mmf_claim; there is no stereo gate (:107).  The candidate pass is k_lp_topk once per
+// camera -- an LpRows over the left fields with th over the left rows, an LpRows over the right fields with th = 1 (:173-176 apply no
+// factor) over the right rows -- so lp_query's skips (not in view, bFarPoints, a level outside the table; -1 is the reference's own
+// skip of :172) arrive here as a zero count.
+// k_lpf_claim: one wave per pair replays the queries in order.  Per query the left list gives best and second among the slots not in
+//   the left blocked set (one ballot; a truncated list with fewer than two is rescanned, win_sweep<false>); TH_HIGH and the same-level
+//   ratio rule decide (:147-154).  A ratio rejection is the `continue` of :151-152: the query is finished, right block included.  A
+//   claim writes match_l[best] and, if mvLeftToRightMatch[best] names a right slot, match_r of that slot as well (:157-161, no look at
+//   the blocked set), each counted; with mp_obs every written slot is blocked in its camera's bit array, which the right block of the
+//   same query already sees.  The right block (:170-236) is the mirror over the right list: mvRightToLeftMatch[best] into match_l,
+//   then match_r[best].  Partner slots are read at claim time (wave-uniform) and honoured only inside the other row's count.
+// ------------------------------------------------------------------------------------------------
+struct LpfCam { const KpIn* kt; const uint8_t* dt; const int* gs; const int* gi; };
+
+// query i of the current 64 (row o, index q of its pair) in one camera: the first two listed candidates that are not blocked, or,
+// when the truncated list holds fewer than two, the window again with the blocked set applied.  0xFFFFFFFF: none.
+__device__ __forceinline__ void lpf_top2(const unsigned int* sk, int i, const unsigned int* blk, int cnt, const float* topR, const LpfCam& cam,
+                                         const LpRows& R, size_t o, int q, float min_x, float min_y, float inv_w, float inv_h, int lane,
+                                         unsigned int& w1, unsigned int& w2) {
+    const unsigned INV = 0xFFFFFFFFu;
+    unsigned int key = INV;
+    bool fr = false;
+    if (lane < TK_K) {
+        key = sk[i * TK_K + lane];
+        const unsigned int k = key == INV ? 0u : key & 0xFFFFu;
+        fr = key != INV && !((blk[k >> 5] >> (k & 31)) & 1u);
+    }
+    unsigned long long fb = __ballot(fr);
+    w1 = INV; w2 = INV;
+    if (fb) {
+        w1 = (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1);
+        fb &= fb - 1;
+        if (fb) w2 = (unsigned)__builtin_amdgcn_readlane((int)key, __ffsll((long long)fb) - 1);
+    }
+    if (w2 == INV && cnt > TK_K) {
+        const Win w = {R.px[o], R.py[o], topR[o], 0.f, R.level[o] - 1, R.level[o]};   // the window k_lp_topk swept for this camera
+        u64 a[4], top[TK_K];
+        load_desc(R.qdesc + (R.q_shared ? (size_t)q : o) * 32, a);
+        int c2;
+        win_sweep<false>(w, OctavePay{}, cam.kt, cam.dt, nullptr, cam.gs, cam.gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+        w1 = cand_word(top[0]); w2 = cand_word(top[1]);
+    }
+}
+
+__global__ __launch_bounds__(64) void k_lpf_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                  float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
+                                                  const uint8_t* __restrict__ blocked_l, const uint8_t* __restrict__ blocked_r,
+                                                  const int* __restrict__ l2r, const int* __restrict__ r2l, LpRows RL, LpRows RR, float nnratio,
+                                                  MmfLists T, int* __restrict__ match_l, int* __restrict__ match_r, int* __restrict__ nmatches) {
+    extern __shared__ unsigned int lpf_lds[];                                // blocked bits left, right [ceil(cap / 32)] each, the current 64 queries' lists [64][TK_K] per camera
+    const unsigned INV = 0xFFFFFFFFu;
+    const int lane = threadIdx.x, p = blockIdx.x, fl = first_l + p, fr = first_r + p;
+    const int ntl = min(max(counts[fl], 0), cap), ntr = min(max(counts[fr], 0), cap);
+    const int nq = min(max(RL.nq[p], 0), RL.q_stride);
+    const int nwords = (cap + 31) >> 5;
+    unsigned int* blkL = lpf_lds;
+    unsigned int* blkR = blkL + nwords;
+    unsigned int* skL = blkR + nwords;
+    unsigned int* skR = skL + 64 * TK_K;
+    int* mrowL = match_l + (size_t)p * cap;
+    int* mrowR = match_r + (size_t)p * cap;
+    const uint8_t* tbl = blocked_l ? blocked_l + (size_t)p * cap : nullptr;
+    const uint8_t* tbr = blocked_r ? blocked_r + (size_t)p * cap : nullptr;
+    for (int wd = lane; wd < nwords; wd += 64) { blkL[wd] = bits_word(tbl, ntl, wd, 0u); blkR[wd] = bits_word(tbr, ntr, wd, 0u); }
+    for (int k = lane; k < cap; k += 64) { mrowL[k] = -1; mrowR[k] = -1; }  // ORBM_NO_MATCH
+    __syncthreads();
+    const size_t rowBase = (size_t)p * RL.q_stride;
+    const LpfCam camL{kps + (size_t)fl * cap, desc + (size_t)fl * cap * 32, grid_start + (size_t)fl * (64 * 48 + 1), grid_idx + (size_t)fl * cap};
+    const LpfCam camR{kps + (size_t)fr * cap, desc + (size_t)fr * cap * 32, grid_start + (size_t)fr * (64 * 48 + 1), grid_idx + (size_t)fr * cap};
+    const int* l2rRow = l2r ? l2r + (size_t)p * cap : nullptr;               // mvLeftToRightMatch / mvRightToLeftMatch of the pair
+    const int* r2lRow = r2l ? r2l + (size_t)p * cap : nullptr;
+    int nm = 0;
+    // the next 64 queries' lists and counts of both cameras are in flight while the current ones are replayed (clamped, unconditional
+    // loads); mp_obs is read only for a query with candidates in either camera (any other row reads nothing else)
+    const unsigned int* keyRowL = T.keys_l + rowBase * TK_K;
+    const unsigned int* keyRowR = T.keys_r + rowBase * TK_K;
+    const int* cntRowL = T.cnt_l + rowBase;
+    const int* cntRowR = T.cnt_r + rowBase;
+    const uint8_t* obRow = RL.mp_obs + (RL.q_shared ? (size_t)0 : rowBase);
+    unsigned int pkL[TK_K], pkR[TK_K];
+    int pcL = 0, pcR = 0;
+    uint8_t pob = 0;
+    auto fetch = [&](int W0) {
+        const int last = nq * TK_K - 1;
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) {
+            const int e = min(W0 * TK_K + r * 64 + lane, last);
+            pkL[r] = keyRowL[e]; pkR[r] = keyRowR[e];
+        }
+        const int qc = min(W0 + lane, nq - 1);
+        pcL = cntRowL[qc]; pcR = cntRowR[qc];
+        pob = (W0 + lane < nq && (pcL > 0 || pcR > 0)) ? obRow[qc] : 0;
+    };
+    if (nq > 0) fetch(0);
+    for (int W0 = 0; W0 < nq; W0 += 64) {
+#pragma unroll
+        for (int r = 0; r < TK_K; ++r) { skL[r * 64 + lane] = pkL[r]; skR[r * 64 + lane] = pkR[r]; }   // query i's lists: sk?[i * TK_K .. + TK_K)
+        const int cntL = W0 + lane < nq ? pcL : 0;
+        const int cntR = W0 + lane < nq ? pcR : 0;
+        const int ob = pob != 0;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (W0 + 64 < nq) fetch(W0 + 64);
+        unsigned long long todo = __ballot(cntL > 0 || cntR > 0);           // skipped queries and two empty windows claim nothing; an empty LEFT window alone does not end the query
+        while (todo) {
+            const int i = __ffsll((long long)todo) - 1;
+            todo &= todo - 1;
+            const size_t o = rowBase + W0 + i;
+            const int obi = __builtin_amdgcn_readlane(ob, i);
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {                                    // the left block (:65-168), then the right one (:170-236)
+                const int cn = __builtin_amdgcn_readlane(c ? cntR : cntL, i);
+                if (cn <= 0) continue;                                       // block skipped, or an empty window (:85, :178)
+                unsigned int* blk = c ? blkR : blkL;
+                unsigned int* oblk = c ? blkL : blkR;
+                unsigned int w1, w2;
+                lpf_top2(c ? skR : skL, i, blk, cn, c ? T.r_r : T.r_l, c ? camR : camL, c ? RR : RL, o, W0 + i, min_x, min_y, inv_w, inv_h, lane, w1, w2);
+                if (w1 == INV) continue;                                     // every candidate blocked: bestDist stays 256
+                const int bestDist = (int)(w1 >> 21), bestLevel = (int)((w1 >> 16) & 31u) - 1;
+                const int bestDist2 = w2 == INV ? 256 : (int)(w2 >> 21), bestLevel2 = w2 == INV ? -1 : (int)((w2 >> 16) & 31u) - 1;
+                if (bestDist > 100) continue;                                // TH_HIGH (:147, :219)
+                if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) break;   // :151-152, :221-222: the query is finished
+                if (c == 0 && !(bestLevel != bestLevel2 || (float)bestDist <= nnratio * (float)bestDist2)) continue;   // :154
+                const unsigned int k = w1 & 0xFFFFu;
+                const int* prow = c ? r2lRow : l2rRow;
+                int partner = prow ? prow[k] : -1;                           // :157, :224 (wave-uniform)
+                if (partner < 0 || partner >= (c ? ntl : ntr)) partner = -1;
+                if (lane == 0) {
+                    (c ? mrowR : mrowL)[k] = W0 + i;                         // may overwrite a claim of a query without observations
+                    if (obi) blk[k >> 5] |= 1u << (k & 31);
+                    if (partner >= 0) {
+                        (c ? mrowL : mrowR)[partner] = W0 + i;               // :158, :225: whatever the slot holds
+                        if (obi) oblk[partner >> 5] |= 1u << (partner & 31);
+                    }
+                }
+                nm += partner >= 0 ? 2 : 1;                                  // overwrites count, as the reference's nmatches++ does
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");              // the next chunk's lists overwrite sk
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (lane == 0) nmatches[p] = nm;
+}
+
 // k_mm_project: the LastFrame MapPoints of every pair through the current pose (ORBmatcher.cc:2481-2527 as facade/ORBmatcher.h
 // evaluates it against cvcompat.h): a 3x3 * 3x1 product accumulates in double and rounds once to float, the translation is a float
 // add; invzc = (float)(1.0 / (double)z); pinhole u = fx * xc / zc + cx (Pinhole.cpp:33-37).  A rejected point (no MapPoint or an
