@@ -820,6 +820,75 @@ int orbm_unproject_stereo_batch_async(orbm_t*, int nrows, int first, int cap, co
                                       const float* depth, const float* twc, const float* k_host,
                                       float* x3dw, uint8_t* has_depth);
 
+/* ---- MapPoint refresh: the producer of the qdesc / normal / min_dist / max_dist rows that the batched searches read (M3, M4, M5, M6,
+ * M13, orbm_is_in_frustum), for a batch of MapPoints over a resident pool of KeyFrame rows.
+ * Shared inputs.  KeyFrame pool, the orbm_fuse_batch_async convention: nkf_rows rows of cap slots, desc_kf [nkf_rows][cap][32], kps_kf
+ * [nkf_rows][cap], counts_kf [nkf_rows]; a two-camera KeyFrame is ONE stacked row (left slots, then right, as mDescriptors after vconcat),
+ * so the reference's rightIndex is already a slot of the row.  ow_l [nkf_rows][3] = GetCameraCenter, ow_r [nkf_rows][3] =
+ * GetRightCameraCenter per row; ow_r may be NULL when no entry names the right camera (an entry that does so anyway is then skipped).
+ * Observations, a CSR over the MapPoints of the call: obs_off [nmp + 1] absolute offsets into obs_row / obs_slot / obs_flags [nobs]
+ * (obs_off[0] may be non-zero); per entry the pool row, the slot in that row and flags: bit 0 = a right-camera observation, bit 1 = the
+ * KeyFrame isBad().  The caller lays out a MapPoint's entries in the order its mObservations map is walked, the left entry before the
+ * right entry of the same KeyFrame (MapPoint.cc:481-486, :610-621); that order is pointer order in the reference, so the contract is "in
+ * the order given".  valid [nmp] is the !mbBad test (NULL = all valid): for a MapPoint that is not valid none of its rows is read.
+ * Skip rules (defined here, not by the reference): an entry is skipped by both functions when obs_row lies outside [0, nkf_rows) or
+ * obs_slot outside [0, min(counts_kf[row], cap)); a non-increasing obs_off pair, a pair that leaves [0, nobs] and a list of more than
+ * ORBM_MP_MAX_OBS entries are an empty list.  Nothing reads out of bounds on device data.
+ * Alignment: desc_kf must be 16-byte aligned (descriptor rows are read as two 128-bit words) and mp_desc 4-byte aligned (rows are
+ * written as eight 32-bit words); every other array is aligned to its element.  A sub-buffer that starts at a whole descriptor row of
+ * an allocation aligned to 32 bytes meets both.
+ *
+ * orbm_distinctive_descriptors / orbm_distinctive_descriptors_batch_async: MapPoint::ComputeDistinctiveDescriptors
+ * (MapPoint.cc:450-538).  Entries with bit 1 set are skipped as well (:477).  Over the N remaining descriptors every pairwise
+ * DescriptorDistance is taken; per row i the N distances, the 0 to itself included, are ordered and element (int)(0.5 * (N - 1)) is the
+ * row's median (:518-521): the lower median for even N.  Tie rule: the FIRST row of least median wins (strict <, :524).  A distance of
+ * 256 is a legal value (a descriptor and its complement) and is kept in 16 bits: it never wraps to 0.  Outputs: mp_desc [nmp][32] = the
+ * winning descriptor; best_obs [nmp] = the winner's position in the MapPoint's own entry list, skipped entries counted, or -1;
+ * best_median [nmp] (optional, NULL = not written) = 0..256, or -1.  With N == 0, or a MapPoint that is not valid, mp_desc keeps the
+ * caller's bytes (the reference returns without touching mDescriptor) and best_obs / best_median are -1.  There is no cap on N up to
+ * ORBM_MP_MAX_OBS = 65535: nothing is truncated and nothing falls back to the host (one wave per MapPoint; lists beyond 64 entries are
+ * walked in chunks of 64 rows by the four waves of the MapPoint's workgroup).  mp_desc is a valid qdesc of the batched searches when nmp matches their npairs * q_stride layout.
+ *
+ * orbm_update_normal_and_depth / orbm_update_normal_and_depth_batch_async: MapPoint::UpdateNormalAndDepth (MapPoint.cc:578-652).  Bad
+ * KeyFrames are NOT skipped here (the reference does not test them).  Numerics are the facade's lines against facade/cvcompat.h: per
+ * entry, in list order, d = pw - Ow in float (Ow from ow_l, or ow_r with bit 0), s = (float)(1.0 / sqrt(double sum of d^2)), normal =
+ * normal + d * s as a float multiply then a float add without contraction, n++; the sum is sequential per MapPoint, float addition order
+ * is part of the result.  Then dist = (float)sqrt(double sum of (pw - ow_l[ref_row])^2), level = kps_kf[ref_row][ref_slot].octave (the
+ * caller picks ref_slot by the rules of :627-638), max_dist = dist * scale[level], min_dist = max_dist / scale[nlevels - 1], normal_out =
+ * normal * (float)(1.0 / n).  pw [nmp][3], ref_row / ref_slot [nmp]; scale_factors(_host) [nlevels] on the host.  Outputs normal
+ * [nmp][3], min_dist, max_dist, updated [nmp].  updated = 0, with that MapPoint's three rows left untouched, when the MapPoint is not
+ * valid, n == 0, ref_row or ref_slot is out of range, or the octave lies outside [0, nlevels).  A point exactly at a camera centre gives
+ * inf or NaN by IEEE; the bits of a NaN are not pinned.  The rows go straight into orbm_is_in_frustum(ORBM_DEVICE) and the min_dist /
+ * max_dist / normal inputs of the batched projections.
+ *
+ * Host forms: host pointers, synchronous; mp_desc / normal / min_dist / max_dist are in/out (rows that are not written keep the caller's
+ * values); return the number of MapPoints that got a descriptor / were updated.  Device forms: enqueue-only, all pointers device pointers
+ * except scale_factors_host; no work buffer, every output is recomputed per launch and nothing accumulates across graph replays, so the
+ * calls can be captured (orbx_capture_begin) at once.  ORBM_E_INVALID, with nothing enqueued: a NULL required array (valid, ow_r and
+ * best_median may be NULL); nmp, nkf_rows, cap or nlevels < 1; nobs < 0.  ORBM_E_CAPACITY: nlevels > 12, nmp > ORBM_MP_MAX_BATCH,
+ * nkf_rows * cap > 2^31 - 1. */
+enum { ORBM_MP_MAX_OBS = 65535, ORBM_MP_MAX_BATCH = 1 << 20 };
+int orbm_distinctive_descriptors(orbm_t*, int nmp, int nkf_rows, int cap, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                 int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                 const uint8_t* obs_flags, const uint8_t* valid,
+                                 uint8_t* mp_desc, int32_t* best_obs, int32_t* best_median);
+int orbm_distinctive_descriptors_batch_async(orbm_t*, int nmp, int nkf_rows, int cap, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                             int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                             const uint8_t* obs_flags, const uint8_t* valid,
+                                             uint8_t* mp_desc, int32_t* best_obs, int32_t* best_median);
+int orbm_update_normal_and_depth(orbm_t*, int nmp, int nkf_rows, int cap, const orbm_kp_t* kps_kf, const int32_t* counts_kf,
+                                 const float* ow_l, const float* ow_r,
+                                 int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                 const uint8_t* obs_flags, const uint8_t* valid,
+                                 const float* pw, const int32_t* ref_row, const int32_t* ref_slot, const float* scale_factors, int nlevels,
+                                 float* normal, float* min_dist, float* max_dist, uint8_t* updated);
+int orbm_update_normal_and_depth_batch_async(orbm_t*, int nmp, int nkf_rows, int cap, const orbm_kp_t* kps_kf, const int32_t* counts_kf,
+                                             const float* ow_l, const float* ow_r,
+                                             int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                             const uint8_t* obs_flags, const uint8_t* valid,
+                                             const float* pw, const int32_t* ref_row, const int32_t* ref_slot, const float* scale_factors_host, int nlevels,
+                                             float* normal, float* min_dist, float* max_dist, uint8_t* updated);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -891,6 +891,15 @@ def _install_search():
                                                     vp, ci, ci, ci, ci, cf, cf, vp, vp, vp]    # image table, type, w, h, stride, factor, mbf, outputs
     L.orbm_unproject_stereo.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.orbm_unproject_stereo_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    for name in ("orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, ci, ci, vp, vp,                       # nmp, nkf_rows, cap, desc_kf, counts_kf
+                                     ci, vp, vp, vp, vp, vp,                       # nobs, obs_off, obs_row, obs_slot, obs_flags, valid
+                                     vp, vp, vp]                                   # mp_desc, best_obs, best_median
+    for name in ("orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, ci, ci, vp, vp, vp, vp,               # nmp, nkf_rows, cap, kps_kf, counts_kf, ow_l, ow_r
+                                     ci, vp, vp, vp, vp, vp,                       # nobs, obs_off, obs_row, obs_slot, obs_flags, valid
+                                     vp, vp, vp, vp, ci,                           # pw, ref_row, ref_slot, scale factors (host), nlevels
+                                     vp, vp, vp, vp]                               # normal, min_dist, max_dist, updated
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -934,6 +943,67 @@ def _install_search():
         return _chk(self.L.orbm_unproject_stereo_batch_async(self.h, nrows, first, cap, kps_un, counts, depth, twc, _p(K), x3dw, has_depth),
                     "orbm_unproject_stereo_batch_async")
 
+    def _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, valid, nmp):
+        off = np.ascontiguousarray(obs_off, np.int32); row = np.ascontiguousarray(obs_row, np.int32); slot = np.ascontiguousarray(obs_slot, np.int32)
+        fl = np.ascontiguousarray(obs_flags, np.uint8)
+        if len(off) != nmp + 1 or not (len(row) == len(slot) == len(fl)):
+            raise OrbError("obs_off must hold nmp + 1 offsets and obs_row / obs_slot / obs_flags one entry each")
+        pad = lambda a: a if len(a) else np.zeros(1, a.dtype)               # nobs == 0: the arrays are still required
+        v = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+        return off, pad(row), pad(slot), pad(fl), v, len(row)
+
+    def distinctive_descriptors(self, desc_kf, counts_kf, obs_off, obs_row, obs_slot, obs_flags, valid=None, mp_desc=None):
+        """MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:450-538) for nmp = len(obs_off) - 1 MapPoints over a KeyFrame pool desc_kf
+        [nkf_rows][cap][32] -> (number with a descriptor, mp_desc [nmp][32], best_obs, best_median).  mp_desc (optional) holds the rows that
+        MapPoints without a winner keep."""
+        d = np.ascontiguousarray(desc_kf, np.uint8); nrows, cap = d.shape[0], d.shape[1]
+        cnt = np.ascontiguousarray(counts_kf, np.int32); nmp = len(obs_off) - 1
+        off, row, slot, fl, v, nobs = _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, valid, nmp)
+        out = np.zeros((max(nmp, 1), 32), np.uint8) if mp_desc is None else np.array(mp_desc, np.uint8).reshape(-1, 32)
+        bo = np.zeros(max(nmp, 1), np.int32); bm = np.zeros(max(nmp, 1), np.int32)
+        rc = _chk(self.L.orbm_distinctive_descriptors(self.h, nmp, nrows, cap, _p(d), _p(cnt), nobs, _p(off), _p(row), _p(slot), _p(fl),
+                                                      None if v is None else _p(v), _p(out), _p(bo), _p(bm)), "orbm_distinctive_descriptors")
+        return rc, out[:nmp], bo[:nmp], bm[:nmp]
+
+    def distinctive_descriptors_batch_async(self, nmp, nkf_rows, cap, desc_kf, counts_kf, nobs, obs_off, obs_row, obs_slot, obs_flags, valid,
+                                            mp_desc, best_obs, best_median=None):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_distinctive_descriptors_batch_async)."""
+        return _chk(self.L.orbm_distinctive_descriptors_batch_async(self.h, nmp, nkf_rows, cap, desc_kf, counts_kf, nobs, obs_off, obs_row, obs_slot,
+                                                                    obs_flags, valid, mp_desc, best_obs, best_median),
+                    "orbm_distinctive_descriptors_batch_async")
+
+    def update_normal_and_depth(self, kps_kf, counts_kf, ow_l, ow_r, obs_off, obs_row, obs_slot, obs_flags, valid, pw, ref_row, ref_slot, scale_factors,
+                                normal=None, min_dist=None, max_dist=None):
+        """MapPoint::UpdateNormalAndDepth (MapPoint.cc:578-652) for nmp MapPoints over a KeyFrame pool kps_kf [nkf_rows][cap] ->
+        (number updated, normal [nmp][3], min_dist, max_dist, updated).  normal / min_dist / max_dist (optional) hold the rows that
+        MapPoints which are not updated keep."""
+        k = np.ascontiguousarray(kps_kf, KP_DTYPE); nrows, cap = k.shape[0], k.shape[1]
+        cnt = np.ascontiguousarray(counts_kf, np.int32); nmp = len(obs_off) - 1
+        ol = np.ascontiguousarray(ow_l, np.float32).reshape(-1, 3); orr = None if ow_r is None else np.ascontiguousarray(ow_r, np.float32).reshape(-1, 3)
+        off, row, slot, fl, v, nobs = _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, valid, nmp)
+        P = np.ascontiguousarray(pw, np.float32).reshape(-1, 3); rr = np.ascontiguousarray(ref_row, np.int32); rs = np.ascontiguousarray(ref_slot, np.int32)
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        if len(ol) != nrows or (orr is not None and len(orr) != nrows) or not (len(P) == len(rr) == len(rs) == nmp):
+            raise OrbError("ow_l / ow_r hold one centre per pool row; pw, ref_row and ref_slot one entry per MapPoint")
+        keep = lambda a, shape: np.zeros(shape, np.float32) if a is None else np.array(a, np.float32).reshape(shape)
+        nm = keep(normal, (max(nmp, 1), 3)); mn = keep(min_dist, max(nmp, 1)); mx = keep(max_dist, max(nmp, 1)); up = np.zeros(max(nmp, 1), np.uint8)
+        rc = _chk(self.L.orbm_update_normal_and_depth(self.h, nmp, nrows, cap, _p(k), _p(cnt), _p(ol), None if orr is None else _p(orr), nobs, _p(off),
+                                                      _p(row), _p(slot), _p(fl), None if v is None else _p(v), _p(P), _p(rr), _p(rs), _p(sf), len(sf),
+                                                      _p(nm), _p(mn), _p(mx), _p(up)), "orbm_update_normal_and_depth")
+        return rc, nm[:nmp], mn[:nmp], mx[:nmp], up[:nmp]
+
+    def update_normal_and_depth_batch_async(self, nmp, nkf_rows, cap, kps_kf, counts_kf, ow_l, ow_r, nobs, obs_off, obs_row, obs_slot, obs_flags, valid,
+                                            pw, ref_row, ref_slot, scale_factors, normal, min_dist, max_dist, updated):
+        """Device form, enqueue only: device pointers except scale_factors (include/orbm.h: orbm_update_normal_and_depth_batch_async)."""
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        return _chk(self.L.orbm_update_normal_and_depth_batch_async(self.h, nmp, nkf_rows, cap, kps_kf, counts_kf, ow_l, ow_r, nobs, obs_off, obs_row,
+                                                                    obs_slot, obs_flags, valid, pw, ref_row, ref_slot, _p(sf), len(sf),
+                                                                    normal, min_dist, max_dist, updated), "orbm_update_normal_and_depth_batch_async")
+
+    ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
+    ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
+    ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
+    ORBmatcher.UpdateNormalAndDepthBatchAsync = update_normal_and_depth_batch_async
     ORBmatcher.window_candidates = window_candidates
     ORBmatcher.ComputeStereoMatches = stereo_matches
     ORBmatcher.ComputeStereoFromRGBD = stereo_from_rgbd
@@ -1014,6 +1084,8 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_stereo_from_rgbd", "orbm_stereo_from_rgbd_batch_async", "orbm_unproject_stereo", "orbm_unproject_stereo_batch_async",
+            "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async",
+            "orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

@@ -2607,4 +2607,136 @@ int orbm_unproject_stereo(orbm_t* m, int n, const orbm_kp_t* kps_un, const float
     return cnt;
 }
 
+// ---- MapPoint refresh: MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth -------------------------
+// the argument tests the four entry points share; fills the observation block of the kernels
+static int mp_obs_args(const char* who, int nmp, int nkf_rows, int cap, int nobs, const int32_t* obs_off, const int32_t* obs_row,
+                       const int32_t* obs_slot, const uint8_t* obs_flags, const uint8_t* valid, MpObs& O) {
+    if (!obs_off || !obs_row || !obs_slot || !obs_flags) { set_merr("%s: an observation array is NULL", who); return ORBM_E_INVALID; }
+    if (nmp < 1 || nkf_rows < 1 || cap < 1 || nobs < 0) { set_merr("%s: nmp, nkf_rows and cap must be >= 1 and nobs >= 0", who); return ORBM_E_INVALID; }
+    if (nmp > ORBM_MP_MAX_BATCH) { set_merr("%s: %d MapPoints in one call (at most %d)", who, nmp, (int)ORBM_MP_MAX_BATCH); return ORBM_E_CAPACITY; }
+    if ((long long)nkf_rows * cap > INT_MAX) { set_merr("%s: %d rows of %d slots (the pool holds at most 2^31 - 1 slots)", who, nkf_rows, cap); return ORBM_E_CAPACITY; }
+    O = MpObs{obs_off, obs_row, obs_slot, obs_flags, valid, nobs, nmp, nkf_rows, cap};
+    return ORBM_OK;
+}
+
+int orbm_distinctive_descriptors_batch_async(orbm_t* m, int nmp, int nkf_rows, int cap, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                             int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                             const uint8_t* obs_flags, const uint8_t* valid,
+                                             uint8_t* mp_desc, int32_t* best_obs, int32_t* best_median) {
+    if (!m || !desc_kf || !counts_kf || !mp_desc || !best_obs) { set_merr("ComputeDistinctiveDescriptors batch: a required array is NULL"); return ORBM_E_INVALID; }
+    MpObs O;
+    const int rc = mp_obs_args("ComputeDistinctiveDescriptors batch", nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, valid, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+#ifdef ORBX_AB
+#define MP_PACKED(G) do { hipLaunchKernelGGL(k_mp_distinctive_packed<G>, dim3((unsigned)(((long long)nmp * G + 255) / 256)), dim3(256), 0, m->stream, desc_kf, counts_kf, O, mp_desc, best_obs, best_median); \
+                          hipLaunchKernelGGL(k_mp_distinctive_long<G>, dim3((nmp + 3) / 4), dim3(256), 0, m->stream, desc_kf, counts_kf, O, mp_desc, best_obs, best_median); } while (0)
+    const char* packed = ab_env("ORBM_MP_PACKED");                          // A/B: several MapPoints per wave in groups of 8, 16 or 32 lanes
+    const int g = packed ? atoi(packed) : 0;
+    if (g == 8) MP_PACKED(8);
+    else if (g == 16) MP_PACKED(16);
+    else if (g == 32) MP_PACKED(32);
+    else
+#endif
+    hipLaunchKernelGGL(k_mp_distinctive, dim3((nmp + 3) / 4), dim3(256), 0, m->stream, desc_kf, counts_kf, O, mp_desc, best_obs, best_median);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_distinctive_descriptors(orbm_t* m, int nmp, int nkf_rows, int cap, const uint8_t* desc_kf, const int32_t* counts_kf,
+                                 int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                 const uint8_t* obs_flags, const uint8_t* valid,
+                                 uint8_t* mp_desc, int32_t* best_obs, int32_t* best_median) {
+    if (!m || !desc_kf || !counts_kf || !mp_desc || !best_obs) { set_merr("ComputeDistinctiveDescriptors: a required array is NULL"); return ORBM_E_INVALID; }
+    MpObs O;
+    int rc = mp_obs_args("ComputeDistinctiveDescriptors", nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, valid, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t ne = (size_t)std::max(nobs, 1);
+    DevBuf dd, dc, doff, drow, dslot, dfl, dv, dmp, dbo, dbm;
+    arena_reset(m);
+    UP(dd, desc_kf, (size_t)nkf_rows * cap * 32); UP(dc, counts_kf, sizeof(int) * nkf_rows); UP(doff, obs_off, sizeof(int) * ((size_t)nmp + 1));
+    UP(drow, obs_row, sizeof(int) * ne * (nobs > 0)); UP(dslot, obs_slot, sizeof(int) * ne * (nobs > 0)); UP(dfl, obs_flags, ne * (nobs > 0));
+    if (valid) UP(dv, valid, nmp);
+    UPIO(dmp, mp_desc, (size_t)nmp * 32);                                    // in/out: a MapPoint without a winner keeps the caller's bytes
+    AL(dbo, sizeof(int) * nmp); AL(dbm, sizeof(int) * nmp);
+    ARENA_FLUSH(m);
+    rc = orbm_distinctive_descriptors_batch_async(m, nmp, nkf_rows, cap, dd.as<uint8_t>(), dc.as<int32_t>(), nobs, doff.as<int32_t>(), drow.as<int32_t>(),
+                                                  dslot.as<int32_t>(), dfl.as<uint8_t>(), valid ? dv.as<uint8_t>() : nullptr,
+                                                  dmp.as<uint8_t>(), dbo.as<int32_t>(), dbm.as<int32_t>());
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(mp_desc, dmp.host(), (size_t)nmp * 32); memcpy(best_obs, dbo.host(), sizeof(int) * nmp);
+    if (best_median) memcpy(best_median, dbm.host(), sizeof(int) * nmp);
+    int cnt = 0;
+    for (int i = 0; i < nmp; ++i) cnt += best_obs[i] >= 0 ? 1 : 0;
+    return cnt;
+}
+
+int orbm_update_normal_and_depth_batch_async(orbm_t* m, int nmp, int nkf_rows, int cap, const orbm_kp_t* kps_kf, const int32_t* counts_kf,
+                                             const float* ow_l, const float* ow_r,
+                                             int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                             const uint8_t* obs_flags, const uint8_t* valid,
+                                             const float* pw, const int32_t* ref_row, const int32_t* ref_slot, const float* scale_factors_host, int nlevels,
+                                             float* normal, float* min_dist, float* max_dist, uint8_t* updated) {
+    if (!m || !kps_kf || !counts_kf || !ow_l || !pw || !ref_row || !ref_slot || !scale_factors_host || !normal || !min_dist || !max_dist || !updated) {
+        set_merr("UpdateNormalAndDepth batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nlevels < 1) { set_merr("UpdateNormalAndDepth batch: nlevels must be >= 1"); return ORBM_E_INVALID; }
+    if (nlevels > 12) { set_merr("UpdateNormalAndDepth batch: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
+    MpObs O;
+    const int rc = mp_obs_args("UpdateNormalAndDepth batch", nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, valid, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const MpNdParams P{nlevels, scale_tab(scale_factors_host, nlevels)};
+    hipLaunchKernelGGL(k_mp_normal_depth, dim3((nmp + 255) / 256), dim3(256), 0, m->stream, (const KpIn*)kps_kf, counts_kf, ow_l, ow_r, O, pw, ref_row, ref_slot, P,
+                       normal, min_dist, max_dist, updated);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_update_normal_and_depth(orbm_t* m, int nmp, int nkf_rows, int cap, const orbm_kp_t* kps_kf, const int32_t* counts_kf,
+                                 const float* ow_l, const float* ow_r,
+                                 int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                 const uint8_t* obs_flags, const uint8_t* valid,
+                                 const float* pw, const int32_t* ref_row, const int32_t* ref_slot, const float* scale_factors, int nlevels,
+                                 float* normal, float* min_dist, float* max_dist, uint8_t* updated) {
+    if (!m || !kps_kf || !counts_kf || !ow_l || !pw || !ref_row || !ref_slot || !scale_factors || !normal || !min_dist || !max_dist || !updated) {
+        set_merr("UpdateNormalAndDepth: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nlevels < 1) { set_merr("UpdateNormalAndDepth: nlevels must be >= 1"); return ORBM_E_INVALID; }
+    if (nlevels > 12) { set_merr("UpdateNormalAndDepth: %d scale levels (the scale table holds 12)", nlevels); return ORBM_E_CAPACITY; }
+    MpObs O;
+    int rc = mp_obs_args("UpdateNormalAndDepth", nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, valid, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t ne = (size_t)std::max(nobs, 1), nslots = (size_t)nkf_rows * cap;
+    DevBuf dk, dc, dol, dor, doff, drow, dslot, dfl, dv, dpw, drr, drs, dn, dmin, dmax, dup;
+    arena_reset(m);
+    UP(dk, kps_kf, sizeof(KpIn) * nslots); UP(dc, counts_kf, sizeof(int) * nkf_rows); UP(dol, ow_l, sizeof(float) * 3 * nkf_rows);
+    if (ow_r) UP(dor, ow_r, sizeof(float) * 3 * nkf_rows);
+    UP(doff, obs_off, sizeof(int) * ((size_t)nmp + 1));
+    UP(drow, obs_row, sizeof(int) * ne * (nobs > 0)); UP(dslot, obs_slot, sizeof(int) * ne * (nobs > 0)); UP(dfl, obs_flags, ne * (nobs > 0));
+    if (valid) UP(dv, valid, nmp);
+    UP(dpw, pw, sizeof(float) * 3 * nmp); UP(drr, ref_row, sizeof(int) * nmp); UP(drs, ref_slot, sizeof(int) * nmp);
+    UPIO(dn, normal, sizeof(float) * 3 * nmp); UPIO(dmin, min_dist, sizeof(float) * nmp); UPIO(dmax, max_dist, sizeof(float) * nmp);   // rows not updated keep the caller's values
+    AL(dup, nmp);
+    ARENA_FLUSH(m);
+    rc = orbm_update_normal_and_depth_batch_async(m, nmp, nkf_rows, cap, (const orbm_kp_t*)dk.as<KpIn>(), dc.as<int32_t>(), dol.as<float>(),
+                                                  ow_r ? dor.as<float>() : nullptr, nobs, doff.as<int32_t>(), drow.as<int32_t>(), dslot.as<int32_t>(),
+                                                  dfl.as<uint8_t>(), valid ? dv.as<uint8_t>() : nullptr, dpw.as<float>(), drr.as<int32_t>(), drs.as<int32_t>(),
+                                                  scale_factors, nlevels, dn.as<float>(), dmin.as<float>(), dmax.as<float>(), dup.as<uint8_t>());
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(normal, dn.host(), sizeof(float) * 3 * nmp); memcpy(min_dist, dmin.host(), sizeof(float) * nmp); memcpy(max_dist, dmax.host(), sizeof(float) * nmp);
+    memcpy(updated, dup.host(), nmp);
+    int cnt = 0;
+    for (int i = 0; i < nmp; ++i) cnt += updated[i] ? 1 : 0;
+    return cnt;
+}
+
 }  // extern "C"

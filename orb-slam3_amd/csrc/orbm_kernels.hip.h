@@ -4103,6 +4103,295 @@ __global__ __launch_bounds__(256) void k_unproject_stereo(const KpIn* __restrict
     has_depth[o] = ok;
 }
 
+// ------------------------------------------------------------------------------------------------
+// MapPoint refresh: the producer of the qdesc / normal / min_dist / max_dist rows the batched searches read.
+// k_mp_distinctive: MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:450-538); k_mp_normal_depth: MapPoint::UpdateNormalAndDepth
+// (MapPoint.cc:578-652).  Both walk a CSR of observation entries (KeyFrame pool row, slot, flags) over the MapPoints of the call.
+// An entry is skipped when its row lies outside [0, nkf_rows) or its slot outside [0, min(counts_kf[row], cap)); a list is empty when
+// its offset pair does not increase, leaves [0, nobs] or is longer than MP_MAX_OBS entries: nothing is read out of bounds.
+// ------------------------------------------------------------------------------------------------
+#define MP_MAX_OBS 65535                                                    // the winner key holds the entry's position in 16 bits
+struct MpObs { const int* off; const int* row; const int* slot; const uint8_t* flags; const uint8_t* valid; int nobs, nmp, nkf_rows, cap; };
+
+// the entry list of MapPoint mp: [o0, o0 + return value)
+__device__ __forceinline__ int mp_obs_range(const MpObs& O, int mp, int& o0) {
+    o0 = 0;
+    if (O.valid && !O.valid[mp]) return 0;
+    const int a = O.off[mp], b = O.off[mp + 1];
+    if (a < 0 || b > O.nobs || b <= a || b - a > MP_MAX_OBS) return 0;
+    o0 = a;
+    return b - a;
+}
+// the pool slot (row * cap + slot) entry e of the arrays names, or -1 when the entry is skipped
+__device__ __forceinline__ long long mp_obs_slot(const MpObs& O, const int* __restrict__ counts_kf, int e) {
+    const int r = O.row[e], s = O.slot[e];
+    if ((unsigned)r >= (unsigned)O.nkf_rows) return -1;
+    if (s < 0 || s >= min(counts_kf[r], O.cap)) return -1;
+    return (long long)r * O.cap + s;
+}
+
+// k_mp_distinctive: ONE wave per MapPoint, four MapPoints per workgroup; a list of more than 64 entries is shared by the workgroup's
+// four waves.  Lane i holds the descriptor of entry i in eight registers;
+// entries of a bad KeyFrame (flag bit 1, :477) and skipped entries are masked out of the rows and out of the columns, so that N is the
+// number of live entries and the position reported is the entry's position in the MapPoint's own list.  Column j reaches every lane by
+// v_readlane (no memory traffic inside the N x N table).  The median of row i -- element (int)(0.5 * (N - 1)) = (N - 1) >> 1 of the
+// sorted row, the 0 to itself included (:518-521) -- is the least v with count(d <= v) >= k + 1:
+//   E <= 64   the row's distances go to LDS once (16 bits: 256 is a legal distance) and nine bisection steps over 0..256 count them;
+//   E  > 64   the waves walk the rows in chunks of 64 (wave w: chunks w, w + 4, ...) and the columns in chunks of 64; per row chunk two sweeps recompute the
+//             distances into a per-lane histogram in LDS: 17 bins of d >> 4 find the bin of the k-th, 16 bins of d & 15 inside it
+//             find the value (counts fit 16 bits: N <= 65535).
+// The winner is one wave_min_u32 over median << 16 | position (and, for a shared list, one LDS atomic minimum per wave): the FIRST row of least median (strict <, :524).  N == 0 (an empty list,
+// every entry skipped, a MapPoint that is not valid) writes best_obs = best_median = -1 and leaves mp_desc alone.
+__device__ __forceinline__ bool mpd_load(const MpObs& O, const int* __restrict__ counts_kf, const uint8_t* __restrict__ desc_kf, int o0, int E, int e,
+                                         unsigned (&a)[8]) {
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a[t] = 0;
+    if (e >= E || (O.flags[o0 + e] & 2)) return false;
+    const long long p = mp_obs_slot(O, counts_kf, o0 + e);
+    if (p < 0) return false;
+    const uint4* q = (const uint4*)(desc_kf + p * 32);
+    const uint4 x = q[0], y = q[1];
+    a[0] = x.x; a[1] = x.y; a[2] = x.z; a[3] = x.w; a[4] = y.x; a[5] = y.y; a[6] = y.z; a[7] = y.w;
+    return true;
+}
+// distance of the lane's descriptor a to lane j's descriptor b (j wave-uniform)
+__device__ __forceinline__ unsigned mpd_dist(const unsigned (&a)[8], const unsigned (&b)[8], int j) {
+    unsigned d = 0;
+#pragma unroll
+    for (int t = 0; t < 8; ++t) d = bcnt_acc(a[t] ^ (unsigned)__builtin_amdgcn_readlane((int)b[t], j), d);
+    return d;
+}
+
+// the outputs of one MapPoint from the reduced key median << 16 | position (all ones: no live entry)
+__device__ __forceinline__ void mpd_write(const MpObs& O, const int* __restrict__ counts_kf, const uint8_t* __restrict__ desc_kf, int mp, int o0,
+                                          unsigned best, int lane, uint8_t* __restrict__ mp_desc, int* __restrict__ best_obs,
+                                          int* __restrict__ best_median) {
+    if (best == 0xFFFFFFFFu) {
+        if (lane == 0) { best_obs[mp] = -1; if (best_median) best_median[mp] = -1; }
+        return;
+    }
+    const int win = (int)(best & 0xFFFFu);
+    if (lane < 8) {                                                         // the winner's 32 bytes, one dword per lane
+        const long long p = mp_obs_slot(O, counts_kf, o0 + win);
+        ((unsigned*)(mp_desc + (size_t)mp * 32))[lane] = ((const unsigned*)(desc_kf + p * 32))[lane];
+    }
+    if (lane == 0) { best_obs[mp] = win; if (best_median) best_median[mp] = (int)(best >> 16); }
+}
+
+// the workgroup's work: phase 1, every wave takes its own MapPoint when the list has at most 64 entries (no barrier); phase 2, the four
+// waves share the row chunks of each longer list of the workgroup (wave w takes rows 64 w, 64 w + 256, ...) and meet in one LDS word.
+// The tests around the barriers read the same global words in every thread, so they are uniform over the workgroup.
+// SKIP_UPTO > 0 (A/B build only) leaves lists of at most that many entries to the packed kernel.
+template <int SKIP_UPTO>
+__device__ __forceinline__ void mp_distinctive_block(const uint8_t* __restrict__ desc_kf, const int* __restrict__ counts_kf, const MpObs& O,
+                                                     uint8_t* __restrict__ mp_desc, int* __restrict__ best_obs, int* __restrict__ best_median,
+                                                     unsigned short (&sD)[4][64][64], unsigned& sBest) {
+    const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int mp0 = blockIdx.x * 4;
+    unsigned a[8], b[8];
+    if (mp0 + wv < O.nmp) {                                                 // phase 1
+        const int mp = mp0 + wv;
+        int o0;
+        const int E = mp_obs_range(O, mp, o0);
+        if (E <= 64 && !(SKIP_UPTO > 0 && E <= SKIP_UPTO)) {
+            unsigned best = 0xFFFFFFFFu;
+            const bool ok = mpd_load(O, counts_kf, desc_kf, o0, E, lane, a);
+            const u64 mask = __ballot(ok);
+            if (mask) {
+                const int k = (__popcll(mask) - 1) >> 1;
+                for (u64 m = mask; m; m &= m - 1) {
+                    const int j = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+                    sD[wv][j][lane] = (unsigned short)mpd_dist(a, a, j);
+                }
+                int lo = 0, hi = 256;                                       // the answer stays in [lo, hi]: count(d <= 256) = N > k
+                for (int it = 0; it < 9; ++it) {
+                    const int mid = (lo + hi) >> 1;
+                    int cnt = 0;
+                    for (u64 m = mask; m; m &= m - 1) cnt += sD[wv][__builtin_amdgcn_readfirstlane(__builtin_ctzll(m))][lane] <= mid;
+                    if (cnt > k) hi = mid; else lo = mid + 1;
+                }
+                best = wave_min_u32(ok ? ((unsigned)lo << 16 | (unsigned)lane) : 0xFFFFFFFFu);
+            }
+            mpd_write(O, counts_kf, desc_kf, mp, o0, best, lane, mp_desc, best_obs, best_median);
+        }
+    }
+    for (int q = 0; q < 4; ++q) {                                           // phase 2
+        const int mp = mp0 + q;
+        if (mp >= O.nmp) break;
+        int o0;
+        const int E = mp_obs_range(O, mp, o0);
+        if (E <= 64) continue;
+        if (threadIdx.x == 0) sBest = 0xFFFFFFFFu;
+        __syncthreads();
+        int N = 0;
+        for (int jb = 0; jb < E; jb += 64) {
+            const int e = jb + lane;
+            N += __popcll(__ballot(e < E && !(O.flags[o0 + e] & 2) && mp_obs_slot(O, counts_kf, o0 + e) >= 0));
+        }
+        const int k = (N - 1) >> 1;
+        unsigned best = 0xFFFFFFFFu;
+        for (int ib = wv * 64; ib < E && N > 0; ib += 256) {
+            const bool okA = mpd_load(O, counts_kf, desc_kf, o0, E, ib + lane, a);
+            if (!__ballot(okA)) continue;
+            for (int c = 0; c < 33; ++c) sD[wv][c][lane] = 0;
+            for (int jb = 0; jb < E; jb += 64) {                            // sweep 1: bins of d >> 4 (0..16)
+                const u64 mB = __ballot(mpd_load(O, counts_kf, desc_kf, o0, E, jb + lane, b));
+                for (u64 m = mB; m; m &= m - 1) {
+                    const unsigned d = mpd_dist(a, b, __builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
+                    sD[wv][d >> 4][lane] += 1;
+                }
+            }
+            int cum = 0, bin = 16, kk = k;
+            bool found = false;
+            for (int c = 0; c < 17; ++c) {                                  // the lowest bin whose running count passes k
+                const int h = sD[wv][c][lane];
+                if (!found && cum + h > k) { bin = c; kk = k - cum; found = true; }
+                cum += h;
+            }
+            for (int jb = 0; jb < E; jb += 64) {                            // sweep 2: bins of d & 15 inside that bin
+                const u64 mB = __ballot(mpd_load(O, counts_kf, desc_kf, o0, E, jb + lane, b));
+                for (u64 m = mB; m; m &= m - 1) {
+                    const unsigned d = mpd_dist(a, b, __builtin_amdgcn_readfirstlane(__builtin_ctzll(m)));
+                    if ((int)(d >> 4) == bin) sD[wv][17 + (d & 15)][lane] += 1;
+                }
+            }
+            int fine = 15;
+            cum = 0; found = false;
+            for (int t = 0; t < 16; ++t) {
+                const int h = sD[wv][17 + t][lane];
+                if (!found && cum + h > kk) { fine = t; found = true; }
+                cum += h;
+            }
+            const unsigned med = (unsigned)(bin * 16 + fine);
+            best = min(best, wave_min_u32(okA ? (med << 16 | (unsigned)(ib + lane)) : 0xFFFFFFFFu));
+        }
+        if (lane == 0 && best != 0xFFFFFFFFu) atomicMin(&sBest, best);
+        __syncthreads();
+        if (wv == 0) mpd_write(O, counts_kf, desc_kf, mp, o0, sBest, lane, mp_desc, best_obs, best_median);
+        __syncthreads();                                                    // the word is free for the next long list
+    }
+}
+
+__global__ __launch_bounds__(256) void k_mp_distinctive(const uint8_t* __restrict__ desc_kf, const int* __restrict__ counts_kf, MpObs O,
+                                                        uint8_t* __restrict__ mp_desc, int* __restrict__ best_obs, int* __restrict__ best_median) {
+    __shared__ __attribute__((aligned(16))) unsigned short sD[4][64][64];   // [wave][column j | histogram bin][lane]: a lane reads what it wrote
+    // the meeting word of phase 2 lives in wave 0's last column: thread 0 writes it after its own phase 1, and phase 2 uses bins 0..32 only
+    mp_distinctive_block<0>(desc_kf, counts_kf, O, mp_desc, best_obs, best_median, sD, reinterpret_cast<unsigned&>(sD[0][63][0]));
+}
+
+#ifdef ORBX_AB   /* A/B: several MapPoints per wave in groups of G lanes (ORBM_MP_PACKED = 8 | 16 | 32), not in the product library */
+// k_mp_distinctive_packed<G>: a group of G lanes takes one MapPoint whose list has at most G entries; lane l holds entry l, column j
+// reaches the group by ds_bpermute, the G distances of a row stay in registers (0xFFFF for a masked column), nine bisection steps
+// count them, and log2(G) xor-shuffles reduce median << 16 | position inside the group.  Lists of more than G entries are left
+// alone: k_mp_distinctive_long<G>, the product wave with the short lists skipped, takes them in a second launch.
+template <int G>
+__global__ __launch_bounds__(256) void k_mp_distinctive_packed(const uint8_t* __restrict__ desc_kf, const int* __restrict__ counts_kf, MpObs O,
+                                                               uint8_t* __restrict__ mp_desc, int* __restrict__ best_obs, int* __restrict__ best_median) {
+    const int lane = threadIdx.x & 63, l = lane & (G - 1), gbase = lane & ~(G - 1);
+    const int mp = (int)((blockIdx.x * 256u + threadIdx.x) / G);
+    int o0 = 0, E = 0;
+    bool mine = false;
+    if (mp < O.nmp) { E = mp_obs_range(O, mp, o0); mine = E <= G; }
+    unsigned a[8];
+#pragma unroll
+    for (int t = 0; t < 8; ++t) a[t] = 0;
+    bool ok = false;
+    if (mine) ok = mpd_load(O, counts_kf, desc_kf, o0, E, l, a);
+    const u64 bal = __ballot(ok);
+    const unsigned gmask = (unsigned)((bal >> gbase) & (G == 32 ? 0xFFFFFFFFull : ((1ull << G) - 1)));
+    const int k = (__popc(gmask) - 1) >> 1;
+    unsigned d[G];
+#pragma unroll
+    for (int j = 0; j < G; ++j) {
+        unsigned dd = 0;
+#pragma unroll
+        for (int t = 0; t < 8; ++t) dd = bcnt_acc(a[t] ^ (unsigned)__shfl((int)a[t], gbase + j), dd);
+        d[j] = ((gmask >> j) & 1u) ? dd : 0xFFFFu;
+    }
+    int lo = 0, hi = 256;
+    for (int it = 0; it < 9; ++it) {
+        const int mid = (lo + hi) >> 1;
+        int cnt = 0;
+#pragma unroll
+        for (int j = 0; j < G; ++j) cnt += d[j] <= (unsigned)mid;
+        if (cnt > k) hi = mid; else lo = mid + 1;
+    }
+    unsigned key = ok ? ((unsigned)lo << 16 | (unsigned)l) : 0xFFFFFFFFu;
+#pragma unroll
+    for (int sft = G / 2; sft > 0; sft >>= 1) key = min(key, (unsigned)__shfl_xor((int)key, sft));
+    if (!mine) return;                                                      // every shuffle is behind us
+    if (key == 0xFFFFFFFFu) {
+        if (l == 0) { best_obs[mp] = -1; if (best_median) best_median[mp] = -1; }
+        return;
+    }
+    const int win = (int)(key & 0xFFFFu);
+    if (l < 8) {
+        const long long p = mp_obs_slot(O, counts_kf, o0 + win);
+        ((unsigned*)(mp_desc + (size_t)mp * 32))[l] = ((const unsigned*)(desc_kf + p * 32))[l];
+    }
+    if (l == 0) { best_obs[mp] = win; if (best_median) best_median[mp] = (int)(key >> 16); }
+}
+
+template <int G>
+__global__ __launch_bounds__(256) void k_mp_distinctive_long(const uint8_t* __restrict__ desc_kf, const int* __restrict__ counts_kf, MpObs O,
+                                                             uint8_t* __restrict__ mp_desc, int* __restrict__ best_obs, int* __restrict__ best_median) {
+    __shared__ __attribute__((aligned(16))) unsigned short sD[4][64][64];
+    mp_distinctive_block<G>(desc_kf, counts_kf, O, mp_desc, best_obs, best_median, sD, reinterpret_cast<unsigned&>(sD[0][63][0]));
+}
+#endif  /* ORBX_AB */
+
+// k_mp_normal_depth: one thread per MapPoint, a sequential loop over its entries in the order given (float addition order is part of
+// the result).  Entries of bad KeyFrames count here: the reference does not test them.  Per entry d = pw - Ow in float (Ow from ow_l or,
+// flag bit 0, ow_r), s = (float)(1.0 / sqrt(double sum of d^2)) -- cv::norm and Mat / s of facade/cvcompat.h --, normal += d * s as a
+// float multiply and a float add.  An entry that names the right camera while ow_r is NULL is skipped like an out-of-range one.
+struct MpNdParams { int nlevels; ScaleTab sf; };
+
+__device__ __forceinline__ double mp_norm3(float x, float y, float z) { return sqrt((double)x * (double)x + (double)y * (double)y + (double)z * (double)z); }
+
+__global__ __launch_bounds__(256) void k_mp_normal_depth(const KpIn* __restrict__ kps_kf, const int* __restrict__ counts_kf, const float* __restrict__ ow_l,
+                                                         const float* __restrict__ ow_r, MpObs O, const float* __restrict__ pw,
+                                                         const int* __restrict__ ref_row, const int* __restrict__ ref_slot, MpNdParams P,
+                                                         float* __restrict__ normal, float* __restrict__ min_dist, float* __restrict__ max_dist,
+                                                         uint8_t* __restrict__ updated) {
+    const int mp = blockIdx.x * 256 + threadIdx.x;
+    if (mp >= O.nmp) return;
+    int o0;
+    const int E = mp_obs_range(O, mp, o0);
+    if (E == 0) { updated[mp] = 0; return; }                                // not valid or an empty list: nothing else is read
+    const float px = pw[(size_t)mp * 3], py = pw[(size_t)mp * 3 + 1], pz = pw[(size_t)mp * 3 + 2];
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    int n = 0;
+    for (int e = o0; e < o0 + E; ++e) {
+        const int r = O.row[e], s = O.slot[e];
+        if ((unsigned)r >= (unsigned)O.nkf_rows || s < 0 || s >= min(counts_kf[r], O.cap)) continue;
+        const bool right = O.flags[e] & 1;
+        if (right && !ow_r) continue;
+        const float* ow = (right ? ow_r : ow_l) + (size_t)r * 3;
+        const float dx = px - ow[0], dy = py - ow[1], dz = pz - ow[2];
+        const float sc = (float)(1.0 / mp_norm3(dx, dy, dz));
+        nx = nx + dx * sc; ny = ny + dy * sc; nz = nz + dz * sc;
+        ++n;
+    }
+    uint8_t ok = 0;
+    if (n > 0) {
+        const int rr = ref_row[mp], rs = ref_slot[mp];
+        if ((unsigned)rr < (unsigned)O.nkf_rows && rs >= 0 && rs < min(counts_kf[rr], O.cap)) {
+            const int level = kps_kf[(size_t)rr * O.cap + rs].octave;
+            if (level >= 0 && level < P.nlevels) {
+                const float* ow = ow_l + (size_t)rr * 3;
+                const float dist = (float)mp_norm3(px - ow[0], py - ow[1], pz - ow[2]);
+                const float mx = dist * P.sf.sf[level];
+                const float inv = (float)(1.0 / (double)n);
+                max_dist[mp] = mx;
+                min_dist[mp] = mx / P.sf.sf[P.nlevels - 1];
+                normal[(size_t)mp * 3] = nx * inv; normal[(size_t)mp * 3 + 1] = ny * inv; normal[(size_t)mp * 3 + 2] = nz * inv;
+                ok = 1;
+            }
+        }
+    }
+    updated[mp] = ok;
+}
+
 // k_gather_rows: packs the used prefix of every row of the two [nq][cap] candidate arrays into [nq][maxc] (one contiguous
 // device-to-host copy instead of nq*cap entries or a strided copy).
 __global__ __launch_bounds__(256) void k_gather_rows(const int* __restrict__ idx, const int* __restrict__ dist, int nq, int cap, int maxc,
