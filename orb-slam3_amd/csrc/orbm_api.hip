@@ -1136,6 +1136,43 @@ static int lp_capacity(const char* call, int cap, int q_stride, int nlevels, int
     return ORBM_OK;
 }
 
+// the searched pool of a batched search as its entry point names it (counts NULL where the search reads none)
+static Pool pool_view(const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap, const int32_t* grid_start, const int32_t* grid_idx,
+                      float min_x, float min_y, float inv_w, float inv_h) {
+    return Pool{(const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
+}
+
+// The handle's scratch carved for a batched search over `rows` query rows:
+//   [win: a float4 per row] | ncam x [cnt | keys | r] | [acc: nacc words] | [tail bytes]
+// win and r only with SC_WIN / SC_R (M4 and M5 used to keep acc in front of r; nothing depends on the order).  cnt is padded to 256 bytes, keys / r / acc with their SC_PAD_ flag: the byte counts the entry points
+// have always asked for (a captured graph relies on an earlier eager call having grown the block to its size).
+enum { SC_WIN = 1, SC_R = 2, SC_PAD_KEYS = 4, SC_PAD_R = 8, SC_PAD_ACC = 16 };
+struct SearchScratch { float4* win; TopList cam[2]; unsigned* acc; uint8_t* tail; };
+static int search_scratch(orbm* m, const char* call, size_t rows, int ncam, unsigned flags, size_t nacc, size_t tail, SearchScratch& S) {
+    const auto sized = [&](size_t b, unsigned pad) { return flags & pad ? (b + 255) & ~(size_t)255 : b; };
+    const size_t bWin = flags & SC_WIN ? rows * sizeof(float4) : 0, bCnt = (rows * sizeof(int) + 255) & ~(size_t)255,
+                 bKeys = sized(rows * TK_K * sizeof(unsigned), SC_PAD_KEYS), bR = flags & SC_R ? sized(rows * sizeof(float), SC_PAD_R) : 0,
+                 bCam = bCnt + bKeys + bR, bAcc = sized(nacc * sizeof(unsigned), SC_PAD_ACC), bytes = bWin + ncam * bCam + bAcc + tail;
+    uint8_t* scr = batch_scratch(m, bytes);
+    if (!scr) { set_merr("%s scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", call, bytes); return ORBM_E_HIP; }
+    S.win = (float4*)scr;
+    for (int c = 0; c < ncam; ++c) {
+        uint8_t* b = scr + bWin + c * bCam;
+        S.cam[c] = TopList{(int*)b, (unsigned*)(b + bCnt), flags & SC_R ? (float*)(b + bCnt + bKeys) : nullptr};
+    }
+    S.acc = (unsigned*)(scr + bWin + ncam * bCam);
+    S.tail = scr + bWin + ncam * bCam + bAcc;
+    return ORBM_OK;
+}
+
+// the common ending of a batched search: the closing time stamp of orbm_last_timing (the opening one is rec_time(m, m->e0) before the launches)
+static int timed_end(orbm* m) {
+    MHIPCHK(rec_time(m, m->e1));
+    MHIPCHK(hipGetLastError());
+    m->timed = true;
+    return ORBM_OK;
+}
+
 int orbm_track_window_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
                                   const int32_t* grid_start, const int32_t* grid_idx,
                                   float min_x, float min_y, float inv_w, float inv_h,
@@ -1144,14 +1181,12 @@ int orbm_track_window_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t
     if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !best_idx || !best_dist || !second_dist || npairs < 1 ||
         nlevels < 1 || nlevels > 12 || !sf) return ORBM_E_INVALID;
     MHIPCHK(hipSetDevice(m->device));
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
+    const TrackArgs A{q_first, t_first, th, dx, dy, 0.f};
     const ScaleTab st = scale_tab(sf, nlevels);
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_track_window, dim3((cap + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
-                       grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, best_idx, best_dist, second_dist);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    hipLaunchKernelGGL(k_track_window, dim3((cap + 3) / 4, npairs), dim3(256), 0, m->stream, pool, A, st, best_idx, best_dist, second_dist);
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
@@ -1163,50 +1198,43 @@ int orbm_search_by_projection_batch_async(orbm_t* m, const orbm_kp_t* kps, const
     if (!m || !kps || !desc || !counts || !grid_start || !grid_idx || !match || !nmatches || npairs < 1 || cap < 1 || cap > 65535 ||
         nlevels < 1 || nlevels > 12 || !sf || q_first < 0 || t_first < 0) return ORBM_E_INVALID;
     MHIPCHK(hipSetDevice(m->device));
-    const ScaleTab st = scale_tab(sf, nlevels);
     const size_t lds = (size_t)(2 * ((cap + 31) >> 5) + 32 + cap) * sizeof(unsigned);   // blocked bits, rotation histogram, observed bits, proposal tags
     if (lds > 64 * 1024) { set_merr("SearchByProjection batch: %d keypoint slots per frame need %zu B of LDS (limit 64 KB, ~16 000 slots)", cap, lds); return ORBM_E_INVALID; }
-    // scratch of the handle: per query the window population and its TK_K best candidates, per pair the (slot, bin) list of the assignments
+    // scratch of the handle: per query the window population and its TK_K best candidates, per pair the (slot, bin) list of the assignments,
+    // and the searched frames' grid entries, packed (k_track_pack)
     const size_t rows = (size_t)npairs * cap;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = (rows * TK_K * sizeof(unsigned) + 255) & ~(size_t)255,
-                 bAcc = (rows * sizeof(unsigned) + 255) & ~(size_t)255, bEnt = rows * sizeof(uint4);
-    uint8_t* scr = batch_scratch(m, bCnt + bKeys + bAcc + bEnt);
-    if (!scr) { set_merr("SearchByProjection batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bAcc + bEnt); return ORBM_E_HIP; }
-    int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); unsigned* acc = (unsigned*)(scr + bCnt + bKeys);
-    uint4* ent = (uint4*)(scr + bCnt + bKeys + bAcc);                      // the searched frames' grid entries, packed (k_track_pack)
-    const float factor = ORBM_HISTO_LENGTH / 360.0f;                        // ORBmatcher.cc:2478
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection batch", rows, 1, SC_PAD_KEYS | SC_PAD_ACC, rows, rows * sizeof(uint4), S)) return rc;
+    const TopList L = S.cam[0];
+    uint4* ent = (uint4*)S.tail;
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
+    const TrackArgs A{q_first, t_first, th, dx, dy, ORBM_HISTO_LENGTH / 360.0f};   // factor: ORBmatcher.cc:2478
+    const ScaleTab st = scale_tab(sf, nlevels);
     MHIPCHK(rec_time(m, m->e0));
 #ifdef ORBX_AB
     if (ab_env("ORBM_TOPK_WAVE"))                                           // A/B: a wave per query
-        hipLaunchKernelGGL(k_track_topk, dim3((cap + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
-                           grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys);
+        hipLaunchKernelGGL(k_track_topk, dim3((cap + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h,
+                           q_first, t_first, th, st, dx, dy, A.factor, L.cnt, L.keys);
     else
 #endif
     {
-        hipLaunchKernelGGL(k_track_pack, dim3((cap + 255) / 256, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, cap, grid_start, grid_idx, t_first, ent);
+        hipLaunchKernelGGL(k_track_pack, dim3((cap + 255) / 256, npairs), dim3(256), 0, m->stream, pool, t_first, ent);
 #ifdef ORBX_AB
         if (ab_env("ORBM_TOPK16_V1"))                                       // A/B: descriptors and distances for every grid entry
-            hipLaunchKernelGGL(k_track_topk16_v1, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
-                               grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys);
+            hipLaunchKernelGGL(k_track_topk16_v1, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, ent, min_x, min_y, inv_w, inv_h,
+                               q_first, t_first, th, st, dx, dy, A.factor, L.cnt, L.keys);
         else
 #endif
-        hipLaunchKernelGGL(k_track_topk16, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap,
-                           grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys);
+        hipLaunchKernelGGL(k_track_topk16, dim3((cap + 15) / 16, npairs), dim3(256), 0, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, ent, min_x, min_y, inv_w, inv_h,
+                           q_first, t_first, th, st, dx, dy, A.factor, L.cnt, L.keys);
     }
 #ifdef ORBX_AB
     if (ab_env("ORBM_CLAIM_V1"))                                            // A/B: eight queries per step
-        hipLaunchKernelGGL(k_track_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap,
-                           grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys,
-                           t_blocked, q_obs, check_orientation, acc, match, nmatches);
+        hipLaunchKernelGGL(k_track_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, A.factor, L.cnt, L.keys, t_blocked, q_obs, check_orientation, S.acc, match, nmatches);
     else
 #endif
-    hipLaunchKernelGGL(k_track_claim64, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap,
-                       grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, topCnt, topKeys,
-                       t_blocked, q_obs, check_orientation, acc, match, nmatches);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    hipLaunchKernelGGL(k_track_claim64, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, A.factor, L.cnt, L.keys, t_blocked, q_obs, check_orientation, S.acc, match, nmatches);
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
@@ -1232,11 +1260,9 @@ int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps
     const ScaleTab st = scale_tab(scale_factors_host, nlevels);
     const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // k_claim's layout: blocked bits, histogram (unused here), the current 64 queries' lists
     // scratch of the handle: per query the window population, its TK_K best candidates and its radius
-    const size_t rows = (size_t)nframes * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = rows * sizeof(float);
-    uint8_t* scr = batch_scratch(m, bCnt + bKeys + bR);
-    if (!scr) { set_merr("SearchByProjection points batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bR); return ORBM_E_HIP; }
-    int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); float* topR = (float*)(scr + bCnt + bKeys);
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection points batch", (size_t)nframes * q_stride, 1, SC_R, 0, 0, S)) return rc;
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     LpRows R;
     R.nq = nq; R.q_stride = q_stride;
     R.in_view = in_view; R.px = proj_x; R.py = proj_y; R.pxr = proj_xr; R.view_cos = view_cos; R.level = level;
@@ -1244,14 +1270,9 @@ int orbm_search_by_projection_points_batch_async(orbm_t* m, const orbm_kp_t* kps
     R.qdesc = qdesc; R.mp_obs = mp_obs; R.q_shared = q_shared != 0;
     R.th = th; R.nlevels = nlevels;
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_lp_topk, dim3((q_stride + 3) / 4, nframes), dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, t_first, uright, R, st, topCnt, topKeys, topR);
-    hipLaunchKernelGGL(k_lp_claim, dim3(nframes), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, t_first, uright, t_blocked, R, nnratio, topCnt, topKeys, topR, match, nmatches);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    hipLaunchKernelGGL(k_lp_topk, dim3((q_stride + 3) / 4, nframes), dim3(256), 0, m->stream, pool, t_first, uright, R, st, S.cam[0]);
+    hipLaunchKernelGGL(k_lp_claim, dim3(nframes), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, t_first, uright, t_blocked, R, nnratio, S.cam[0], match, nmatches);
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
@@ -1277,12 +1298,9 @@ int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps,
     const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // blocked bits, histogram, the current 64 queries' lists
     // scratch of the handle: per query the window population, its TK_K best candidates and a slot of the accepted-assignment list
     const size_t rows = (size_t)npairs * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bAcc = rows * sizeof(unsigned),
-                 bR = rows * sizeof(float);
-    uint8_t* scr = batch_scratch(m, bCnt + bKeys + bAcc + bR);
-    if (!scr) { set_merr("SearchByProjection frame batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bCnt + bKeys + bAcc + bR); return ORBM_E_HIP; }
-    int* topCnt = (int*)scr; unsigned* topKeys = (unsigned*)(scr + bCnt); unsigned* acc = (unsigned*)(scr + bCnt + bKeys);
-    float* topR = (float*)(scr + bCnt + bKeys + bAcc);
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection frame batch", rows, 1, SC_R, rows, 0, S)) return rc;
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     MmRows R;
     R.nq = nq; R.q_stride = q_stride;
     R.valid = valid; R.u = u; R.v = v; R.invzc = invzc; R.octave = octave; R.angle = angle;
@@ -1291,21 +1309,14 @@ int orbm_search_by_projection_frame_batch_async(orbm_t* m, const orbm_kp_t* kps,
     R.nlevels = nlevels; R.retry_below = retry_below; R.check_ori = check_orientation != 0;
     const dim3 gTop((q_stride + 3) / 4, npairs);
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, t_first, uright, R, st, th, nmatches, topCnt, topKeys, topR);
-    hipLaunchKernelGGL(k_mm_claim<false>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, t_first, uright, t_blocked, R, topCnt, topKeys, topR, acc, match, nmatches, retried);
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, pool, t_first, uright, R, st, th, nmatches, S.cam[0]);
+    hipLaunchKernelGGL(k_mm_claim<false>, dim3(npairs), dim3(64), lds, m->stream, pool, t_first, uright, t_blocked, R, S.cam[0], S.acc, match, nmatches, retried);
     if (retry_below > 0) {                                                  // Tracking.cc:3213-3221, decided per pair on the device
         const float th2 = 2 * th;
-        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, t_first, uright, R, st, th2, nmatches, topCnt, topKeys, topR);
-        hipLaunchKernelGGL(k_mm_claim<true>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, t_first, uright, nullptr, R, topCnt, topKeys, topR, acc, match, nmatches, retried);
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, pool, t_first, uright, R, st, th2, nmatches, S.cam[0]);
+        hipLaunchKernelGGL(k_mm_claim<true>, dim3(npairs), dim3(64), lds, m->stream, pool, t_first, uright, nullptr, R, S.cam[0], S.acc, match, nmatches, retried);
     }
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
@@ -1333,15 +1344,9 @@ int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t* m, const orbm_kp
     // scratch of the handle: per query and camera the window population, its TK_K best candidates and its radius; per query two slots of
     // the accepted-assignment list
     const size_t rows = (size_t)npairs * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = (rows * sizeof(float) + 255) & ~(size_t)255,
-                 bCam = bCnt + bKeys + bR, bAcc = 2 * rows * sizeof(unsigned);
-    uint8_t* scr = batch_scratch(m, 2 * bCam + bAcc);
-    if (!scr) { set_merr("SearchByProjection frame fisheye batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", 2 * bCam + bAcc); return ORBM_E_HIP; }
-    int* topCnt[2]; unsigned* topKeys[2]; float* topR[2];
-    for (int c = 0; c < 2; ++c) {
-        topCnt[c] = (int*)(scr + c * bCam); topKeys[c] = (unsigned*)(scr + c * bCam + bCnt); topR[c] = (float*)(scr + c * bCam + bCnt + bKeys);
-    }
-    unsigned* acc = (unsigned*)(scr + 2 * bCam);
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection frame fisheye batch", rows, 2, SC_R | SC_PAD_R, 2 * rows, 0, S)) return rc;
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     MmRows R;
     R.nq = nq; R.q_stride = q_stride;
     R.valid = valid; R.u = u; R.v = v; R.invzc = nullptr; R.octave = octave; R.angle = angle;   // no stereo gate when Nleft != -1 (ORBmatcher.cc:2569)
@@ -1350,29 +1355,20 @@ int orbm_search_by_projection_frame_fisheye_batch_async(orbm_t* m, const orbm_kp
     R.nlevels = nlevels; R.retry_below = retry_below; R.check_ori = check_orientation != 0;
     MmRows Rr = R;                                                          // the right camera's candidate pass: the same rows at (ur, vr), :2616-2633
     Rr.u = ur; Rr.v = vr;
-    const MmfLists T{topCnt[0], topKeys[0], topR[0], topCnt[1], topKeys[1], topR[1]};
     const dim3 gTop((q_stride + 3) / 4, npairs);
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, th, nmatches, topCnt[0], topKeys[0], topR[0]);
-    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, th, nmatches, topCnt[1], topKeys[1], topR[1]);
-    hipLaunchKernelGGL(k_mmf_claim<false>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, R, ur, vr, T, acc, match_l, match_r, nmatches, retried);
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, pool, first_l, nullptr, R, st, th, nmatches, S.cam[0]);
+    hipLaunchKernelGGL(k_mm_topk<false>, gTop, dim3(256), 0, m->stream, pool, first_r, nullptr, Rr, st, th, nmatches, S.cam[1]);
+    hipLaunchKernelGGL(k_mmf_claim<false>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, R, ur, vr,
+                       S.cam[0], S.cam[1], S.acc, match_l, match_r, nmatches, retried);
     if (retry_below > 0) {                                                  // Tracking.cc:3213-3221, decided per pair on the device
         const float th2 = 2 * th;
-        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, th2, nmatches, topCnt[0], topKeys[0], topR[0]);
-        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, th2, nmatches, topCnt[1], topKeys[1], topR[1]);
-        hipLaunchKernelGGL(k_mmf_claim<true>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, first_l, first_r, (const uint8_t*)nullptr, (const uint8_t*)nullptr, R, ur, vr, T, acc,
-                           match_l, match_r, nmatches, retried);
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, pool, first_l, nullptr, R, st, th2, nmatches, S.cam[0]);
+        hipLaunchKernelGGL(k_mm_topk<true>, gTop, dim3(256), 0, m->stream, pool, first_r, nullptr, Rr, st, th2, nmatches, S.cam[1]);
+        hipLaunchKernelGGL(k_mmf_claim<true>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, first_l, first_r, nullptr, nullptr, R, ur, vr,
+                           S.cam[0], S.cam[1], S.acc, match_l, match_r, nmatches, retried);
     }
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_points_fisheye_batch_async(orbm_t* m, const orbm_kp_t* kps, const uint8_t* desc, const int32_t* counts, int cap,
@@ -1401,15 +1397,9 @@ int orbm_search_by_projection_points_fisheye_batch_async(orbm_t* m, const orbm_k
     const ScaleTab st = scale_tab(scale_factors_host, nlevels);
     const size_t lds = (size_t)(2 * ((cap + 31) >> 5) + 2 * 64 * TK_K) * sizeof(unsigned);   // two blocked bit arrays, both cameras' lists of the current 64 queries
     // scratch of the handle: per query and camera the window population, its TK_K best candidates and its radius
-    const size_t rows = (size_t)npairs * q_stride;
-    const size_t bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned), bR = (rows * sizeof(float) + 255) & ~(size_t)255,
-                 bCam = bCnt + bKeys + bR;
-    uint8_t* scr = batch_scratch(m, 2 * bCam);
-    if (!scr) { set_merr("SearchByProjection points fisheye batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", 2 * bCam); return ORBM_E_HIP; }
-    int* topCnt[2]; unsigned* topKeys[2]; float* topR[2];
-    for (int c = 0; c < 2; ++c) {
-        topCnt[c] = (int*)(scr + c * bCam); topKeys[c] = (unsigned*)(scr + c * bCam + bCnt); topR[c] = (float*)(scr + c * bCam + bCnt + bKeys);
-    }
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection points fisheye batch", (size_t)npairs * q_stride, 2, SC_R | SC_PAD_R, 0, 0, S)) return rc;
+    const Pool pool = pool_view(kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     LpRows R;
     R.nq = nq; R.q_stride = q_stride;
     R.in_view = in_view; R.px = proj_x; R.py = proj_y; R.pxr = nullptr; R.view_cos = view_cos; R.level = level;   // no stereo gate when Nleft != -1 (ORBmatcher.cc:107)
@@ -1419,19 +1409,13 @@ int orbm_search_by_projection_points_fisheye_batch_async(orbm_t* m, const orbm_k
     LpRows Rr = R;                                                          // the right camera's candidate pass: the mbTrackInViewR fields, no th factor (:173-176)
     Rr.in_view = in_view_r; Rr.px = proj_xr; Rr.py = proj_yr; Rr.view_cos = view_cos_r; Rr.level = level_r;
     Rr.th = 1.0f;
-    const MmfLists T{topCnt[0], topKeys[0], topR[0], topCnt[1], topKeys[1], topR[1]};
     const dim3 gTop((q_stride + 3) / 4, npairs);
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_l, (const float*)nullptr, R, st, topCnt[0], topKeys[0], topR[0]);
-    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, (const KpIn*)kps, desc, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_r, (const float*)nullptr, Rr, st, topCnt[1], topKeys[1], topR[1]);
-    hipLaunchKernelGGL(k_lpf_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, l2r, r2l, R, Rr, nnratio, T, match_l, match_r, nmatches);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, pool, first_l, nullptr, R, st, S.cam[0]);
+    hipLaunchKernelGGL(k_lp_topk, gTop, dim3(256), 0, m->stream, pool, first_r, nullptr, Rr, st, S.cam[1]);
+    hipLaunchKernelGGL(k_lpf_claim, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, first_l, first_r, blocked_l, blocked_r, l2r, r2l, R, Rr, nnratio,
+                       S.cam[0], S.cam[1], match_l, match_r, nmatches);
+    return timed_end(m);
 }
 
 int orbm_project_last_frame_batch_async(orbm_t* m, int npairs, const float* tcw_cur, const float* tcw_last, const int32_t* nq, int q_stride,
@@ -1486,14 +1470,11 @@ int orbm_fuse_batch_async(orbm_t* m, int npairs,
         P.sf[i] = st.sf[i];
         P.isg[i] = chi2_gate ? inv_sigma2_host[std::min(i, nlevels - 1)] : 0.f;
     }
+    const Pool pool = pool_view(kps_kf, desc_kf, nullptr, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_fuse_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, uright_kf,
-                       grid_start, grid_idx, min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, best_idx, level_out);
+    hipLaunchKernelGGL(k_fuse_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, pool, uright_kf, kf_row, tcw, ow, R, P, best_idx, level_out);
     hipLaunchKernelGGL(k_fuse_count, dim3(npairs), dim3(256), 0, m->stream, best_idx, q_stride, nfused);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_kf_batch_async(orbm_t* m, int npairs,
@@ -1520,15 +1501,9 @@ int orbm_search_by_projection_kf_batch_async(orbm_t* m, int npairs,
     // scratch of the handle: per query the window population, its TK_K best candidates, a slot of the accepted-assignment list, the
     // radius and the window centre / level (the last two read back only by a rescan)
     const size_t rows = (size_t)npairs * q_stride;
-    const size_t bWin = rows * sizeof(float4), bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned),
-                 bAcc = rows * sizeof(unsigned), bR = rows * sizeof(float);
-    uint8_t* scr = batch_scratch(m, bWin + bCnt + bKeys + bAcc + bR);
-    if (!scr) {
-        set_merr("SearchByProjection KF batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bWin + bCnt + bKeys + bAcc + bR);
-        return ORBM_E_HIP;
-    }
-    float4* topWin = (float4*)scr; int* topCnt = (int*)(scr + bWin); unsigned* topKeys = (unsigned*)(scr + bWin + bCnt);
-    unsigned* acc = (unsigned*)(scr + bWin + bCnt + bKeys); float* topR = (float*)(scr + bWin + bCnt + bKeys + bAcc);
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection KF batch", rows, 1, SC_WIN | SC_R, rows, 0, S)) return rc;
+    const Pool pool = pool_view(kps_f, desc_f, counts_f, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     RlRows R;
     R.nq = nq; R.valid = valid; R.pw = pw; R.min_dist = min_dist; R.max_dist = max_dist; R.angle = angle; R.qdesc = qdesc;
     RlParams P;
@@ -1538,14 +1513,9 @@ int orbm_search_by_projection_kf_batch_async(orbm_t* m, int npairs,
     const ScaleTab st = scale_tab(scale_factors_host, nlevels);
     for (int i = 0; i < 12; ++i) P.sf[i] = st.sf[i];
     MHIPCHK(rec_time(m, m->e0));
-    hipLaunchKernelGGL(k_rl_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, (const KpIn*)kps_f, desc_f, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, f_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
-    hipLaunchKernelGGL(k_claim<RlPol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_f, desc_f, counts_f, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, f_row, f_blocked, R, P, topCnt, topKeys, topR, topWin, acc, match, nmatches);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    hipLaunchKernelGGL(k_rl_topk, dim3((q_stride + 3) / 4, npairs), dim3(256), 0, m->stream, pool, f_row, tcw, ow, R, P, S.cam[0], S.win);
+    hipLaunchKernelGGL(k_claim<RlPol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_f, desc_f, counts_f, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, f_row, f_blocked, R, P, S.cam[0].cnt, S.cam[0].keys, S.cam[0].r, S.win, S.acc, match, nmatches);
+    return timed_end(m);
 }
 
 int orbm_search_by_projection_sim3_batch_async(orbm_t* m, int npairs,
@@ -1573,16 +1543,9 @@ int orbm_search_by_projection_sim3_batch_async(orbm_t* m, int npairs,
     MHIPCHK(hipSetDevice(m->device));
     const size_t lds = (size_t)(((cap + 31) >> 5) + 32 + 64 * TK_K) * sizeof(unsigned);   // k_claim's layout: blocked bits, histogram (unused here), the current 64 queries' lists
     // scratch of the handle, as M5's: per query the window population, its TK_K best candidates, the radius and the window centre / level
-    const size_t rows = (size_t)npairs * q_stride;
-    const size_t bWin = rows * sizeof(float4), bCnt = (rows * sizeof(int) + 255) & ~(size_t)255, bKeys = rows * TK_K * sizeof(unsigned),
-                 bR = rows * sizeof(float);
-    uint8_t* scr = batch_scratch(m, bWin + bCnt + bKeys + bR);
-    if (!scr) {
-        set_merr("SearchByProjection Sim3 batch scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bWin + bCnt + bKeys + bR);
-        return ORBM_E_HIP;
-    }
-    float4* topWin = (float4*)scr; int* topCnt = (int*)(scr + bWin); unsigned* topKeys = (unsigned*)(scr + bWin + bCnt);
-    float* topR = (float*)(scr + bWin + bCnt + bKeys);
+    SearchScratch S;
+    if (const int rc = search_scratch(m, "SearchByProjection Sim3 batch", (size_t)npairs * q_stride, 1, SC_WIN | SC_R, 0, 0, S)) return rc;
+    const Pool pool = pool_view(kps_kf, desc_kf, counts_kf, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h);
     FuseRows R;
     R.nq = nq; R.valid = valid; R.pw = pw; R.normal = normal; R.min_dist = min_dist; R.max_dist = max_dist; R.qdesc = qdesc;
     FuseParams P;
@@ -1594,18 +1557,11 @@ int orbm_search_by_projection_sim3_batch_async(orbm_t* m, int npairs,
     const S3Claim Cp{q_stride, nkf_rows, maxDist};
     MHIPCHK(rec_time(m, m->e0));
     const dim3 tg((q_stride + 3) / 4, npairs);
-    if (proj_form)
-        hipLaunchKernelGGL(k_s3_topk<1>, tg, dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
-    else
-        hipLaunchKernelGGL(k_s3_topk<0>, tg, dim3(256), 0, m->stream, (const KpIn*)kps_kf, desc_kf, cap, grid_start, grid_idx,
-                           min_x, min_y, inv_w, inv_h, kf_row, tcw, ow, R, P, topCnt, topKeys, topR, topWin);
-    hipLaunchKernelGGL(k_claim<S3Pol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_kf, desc_kf, counts_kf, cap, grid_start, grid_idx,
-                       min_x, min_y, inv_w, inv_h, kf_row, matched_in, S3Rows{nq, qdesc}, Cp, topCnt, topKeys, topR, topWin, (unsigned*)nullptr, match, nmatches);
-    MHIPCHK(rec_time(m, m->e1));
-    MHIPCHK(hipGetLastError());
-    m->timed = true;
-    return ORBM_OK;
+    if (proj_form) hipLaunchKernelGGL(k_s3_topk<1>, tg, dim3(256), 0, m->stream, pool, kf_row, tcw, ow, R, P, S.cam[0], S.win);
+    else hipLaunchKernelGGL(k_s3_topk<0>, tg, dim3(256), 0, m->stream, pool, kf_row, tcw, ow, R, P, S.cam[0], S.win);
+    hipLaunchKernelGGL(k_claim<S3Pol>, dim3(npairs), dim3(64), lds, m->stream, (const KpIn*)kps_kf, desc_kf, counts_kf, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h, kf_row, matched_in, S3Rows{nq, qdesc}, Cp, S.cam[0].cnt, S.cam[0].keys, S.cam[0].r, S.win,
+                       (unsigned*)nullptr, match, nmatches);
+    return timed_end(m);
 }
 
 // ---- DBoW2 vocabulary ----

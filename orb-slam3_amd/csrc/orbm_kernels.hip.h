@@ -1014,49 +1014,67 @@ __global__ __launch_bounds__(256) void k_grid_build_batch(const KpIn* __restrict
 
 struct ScaleTab { float sf[12]; };
 
-__global__ __launch_bounds__(256) void k_track_window(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                                      const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
-                                                      const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
-                                                      int q_first, int t_first, float th, ScaleTab st, float dx, float dy,
-                                                      int* __restrict__ best_idx, int* __restrict__ best_dist,
+// What every batched search is handed.  Pool: the searched rows of cap keypoint slots each (counts NULL where a search reads none) with
+// their 64 x 48 grids in CSR form over the cell geometry (min_x, min_y, inv_w, inv_h).  PoolRow: one row of it (row()).  TopList: the
+// candidate lists a *_topk kernel leaves for its claim replay, per query row the window population, its TK_K best candidates as
+// words and the radius a rescan reads back (r NULL for the track kernels, whose replay derives it).
+// The candidate kernels take Pool and TopList by value.  The one-wave claim replays (k_mm_claim apart) and k_track_topk16 keep loose __restrict__
+// parameters and build the Pool in their first line: a by-value struct carries no noalias to the compiler, and these kernels'
+// time follows their register allocation and code placement (profiles/NOTES.md).
+struct PoolRow {
+    const KpIn* kt; const uint8_t* dt; const int* gs; const int* gi;
+    float min_x, min_y, inv_w, inv_h;
+};
+struct Pool {
+    const KpIn* kps; const uint8_t* desc; const int* counts; int cap;
+    const int* grid_start; const int* grid_idx;
+    float min_x, min_y, inv_w, inv_h;
+    __device__ __forceinline__ PoolRow row(size_t r) const {
+        return PoolRow{kps + r * cap, desc + r * cap * 32, grid_start + r * (GRID_CELLS + 1), grid_idx + r * cap, min_x, min_y, inv_w, inv_h};
+    }
+};
+struct TopList { int* cnt; unsigned int* keys; float* r; };
+// the track kernels' pairing and window: query row q_first + pair against row t_first + pair, th * scale[octave] around (x + dx, y + dy);
+// factor: the rotation histogram's bins per degree
+struct TrackArgs { int q_first, t_first; float th, dx, dy, factor; };
+
+__global__ __launch_bounds__(256) void k_track_window(Pool pool, TrackArgs A, ScaleTab st, int* __restrict__ best_idx, int* __restrict__ best_dist,
                                                       int* __restrict__ second_dist) {
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.y;
-    const int qf = q_first + pair, tf = t_first + pair;
+    const int qf = A.q_first + pair, tf = A.t_first + pair;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= min(counts[qf], cap)) return;
-    const KpIn kq = kps[(size_t)qf * cap + q];
-    const KpIn* kt = kps + (size_t)tf * cap;
-    const uint8_t* dt = desc + (size_t)tf * cap * 32;
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const int* gi = grid_idx + (size_t)tf * cap;
-    const float x = kq.x + dx, y = kq.y + dy, r = th * st.sf[kq.octave];
+    const int cap = pool.cap;
+    if (q >= min(pool.counts[qf], cap)) return;
+    const KpIn kq = pool.kps[(size_t)qf * cap + q];
+    const PoolRow T = pool.row(tf);
+    const float x = kq.x + A.dx, y = kq.y + A.dy, r = A.th * st.sf[kq.octave];
     const int minLevel = kq.octave - 1, maxLevel = kq.octave + 1;
     unsigned int best = 0xFFFFFFFFu;                                        // (dist << 16 | order): first minimum in candidate order
     int second = 256, bestk = -1;
-    const int nMinCellX = max(0, (int)floorf((x - min_x - r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((x - min_x + r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - min_y - r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((y - min_y + r) * inv_h));
+    const int nMinCellX = max(0, (int)floorf((x - T.min_x - r) * T.inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((x - T.min_x + r) * T.inv_w));
+    const int nMinCellY = max(0, (int)floorf((y - T.min_y - r) * T.inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((y - T.min_y + r) * T.inv_h));
     int ord0 = 0;
     int bd = 256, bk = -1, sd = 256;                                        // per-lane partials
     unsigned int bo = 0xFFFFFFFFu;
     if (nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0) {
-        const uint4* qp = (const uint4*)(desc + ((size_t)qf * cap + q) * 32);
+        const uint4* qp = (const uint4*)(pool.desc + ((size_t)qf * cap + q) * 32);
         const uint4 qlo = qp[0], qhi = qp[1];
         const u64 a[4] = {(u64)qlo.x | ((u64)qlo.y << 32), (u64)qlo.z | ((u64)qlo.w << 32),
                           (u64)qhi.x | ((u64)qhi.y << 32), (u64)qhi.z | ((u64)qhi.w << 32)};
         for (int ix = nMinCellX; ix <= nMaxCellX; ++ix) {
-            const int j0 = gs[ix * 48 + nMinCellY], j1 = gs[ix * 48 + nMaxCellY + 1];
+            const int j0 = T.gs[ix * 48 + nMinCellY], j1 = T.gs[ix * 48 + nMaxCellY + 1];
             for (int jb = j0; jb < j1; jb += 64) {
                 const int j = jb + lane;
                 if (j < j1) {
-                    const int k = gi[j];
-                    const KpIn kp = kt[k];
+                    const int k = T.gi[j];
+                    const KpIn kp = T.kt[k];
                     bool ok = !(kp.octave < minLevel) && !(kp.octave > maxLevel);   // bCheckLevels is true here (maxLevel >= 0)
                     if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) ok = false;
                     if (ok) {
-                        const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                        const uint4* tp = (const uint4*)(T.dt + (size_t)k * 32);
                         const uint4 lo = tp[0], hi = tp[1];
                         const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
                                              (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
@@ -1172,18 +1190,16 @@ struct NoGate {
     __device__ bool operator()(const KpIn&, int) const { return true; }
 };
 template <bool TOPK, class Pay, class Gate = NoGate>
-__device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const KpIn* __restrict__ kt, const uint8_t* __restrict__ dt,
-                                          const float* __restrict__ urt, const int* __restrict__ gs, const int* __restrict__ gi,
-                                          float min_x, float min_y, float inv_w, float inv_h, const u64 (&a)[4], const unsigned int* blk,
-                                          int lane, int& cnt, u64 (&top)[TK_K], const Gate& gate = Gate{}) {
+__device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const PoolRow& T, const float* __restrict__ urt, const u64 (&a)[4],
+                                          const unsigned int* blk, int lane, int& cnt, u64 (&top)[TK_K], const Gate& gate = Gate{}) {
     const u64 INV = ~0ull;
 #pragma unroll
     for (int i = 0; i < TK_K; ++i) top[i] = INV;
     cnt = 0;
-    const int nMinCellX = max(0, (int)floorf((w.x - min_x - w.r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((w.x - min_x + w.r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((w.y - min_y - w.r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((w.y - min_y + w.r) * inv_h));
+    const int nMinCellX = max(0, (int)floorf((w.x - T.min_x - w.r) * T.inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((w.x - T.min_x + w.r) * T.inv_w));
+    const int nMinCellY = max(0, (int)floorf((w.y - T.min_y - w.r) * T.inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((w.y - T.min_y + w.r) * T.inv_h));
     if (!(w.r >= 0 && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0 && nMinCellX <= nMaxCellX && nMinCellY <= nMaxCellY)) return;
     const bool bCheckLevels = (w.minLevel > 0) || (w.maxLevel >= 0);
     const int loLevel = bCheckLevels ? w.minLevel : INT_MIN, hiLevel = bCheckLevels && w.maxLevel >= 0 ? w.maxLevel : INT_MAX;
@@ -1191,8 +1207,8 @@ __device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const Kp
     int cj0 = 0, clen = 0;
     if (lane < ncols) {
         const int ix = nMinCellX + lane;
-        cj0 = gs[ix * 48 + nMinCellY];
-        clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+        cj0 = T.gs[ix * 48 + nMinCellY];
+        clen = T.gs[ix * 48 + nMaxCellY + 1] - cj0;
     }
     int total;
     const int excl = wave_excl_scan(clen, &total);
@@ -1208,8 +1224,8 @@ __device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const Kp
         u64 key = INV;
         if (t < total) {
             const int j = c0 + (t - cs);
-            const int k = gi[j];
-            const KpIn kp = kt[k];
+            const int k = T.gi[j];
+            const KpIn kp = T.kt[k];
             ok = (kp.octave >= loLevel) & (kp.octave <= hiLevel) & (fabsf(kp.x - w.x) < w.r) & (fabsf(kp.y - w.y) < w.r);   // (no short cut: one x, y load)
             if (ok && urt) {
                 const float urk = urt[k];
@@ -1218,7 +1234,7 @@ __device__ __forceinline__ void win_sweep(const Win& w, const Pay& pay, const Kp
             if (Gate::on && ok && !gate(kp, k)) ok = false;
             if (!TOPK && ok && ((blk[k >> 5] >> (k & 31)) & 1u)) ok = false;
             if (ok) {
-                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                const uint4* tp = (const uint4*)(T.dt + (size_t)k * 32);
                 const uint4 lo = tp[0], hi = tp[1];
                 const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
                                      (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
@@ -1298,11 +1314,11 @@ __device__ __forceinline__ int rot_cull(const unsigned int* hist, const unsigned
     return pruned;
 }
 
-// per query row o: the window population, the radius a rescan reads back and the TK_K best candidates as words
-__device__ __forceinline__ void put_topk(int* out_cnt, float* out_r, unsigned int* out_keys, size_t o, int cnt, float r, const u64 (&top)[TK_K]) {
-    out_cnt[o] = cnt;
-    out_r[o] = r;
-    uint4* ok = (uint4*)(out_keys + o * TK_K);
+// row o of a TopList
+__device__ __forceinline__ void put_topk(const TopList& out, size_t o, int cnt, float r, const u64 (&top)[TK_K]) {
+    out.cnt[o] = cnt;
+    out.r[o] = r;
+    uint4* ok = (uint4*)(out.keys + o * TK_K);
     ok[0] = make_uint4(cand_word(top[0]), cand_word(top[1]), cand_word(top[2]), cand_word(top[3]));
     ok[1] = make_uint4(cand_word(top[4]), cand_word(top[5]), cand_word(top[6]), cand_word(top[7]));
 }
@@ -1317,29 +1333,29 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
                                                     const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
                                                     int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
                                                     int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys) {
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
+    const TrackArgs A{q_first, t_first, th, dx, dy, factor};
+    const TopList out{out_cnt, out_keys, nullptr};
     const int lane = threadIdx.x & 63;
     const int pair = blockIdx.y;
-    const int qf = q_first + pair, tf = t_first + pair;
+    const int qf = A.q_first + pair, tf = A.t_first + pair;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= min(counts[qf], cap)) return;
-    const KpIn kq = kps[(size_t)qf * cap + q];
-    const KpIn* kt = kps + (size_t)tf * cap;
-    const uint8_t* dt = desc + (size_t)tf * cap * 32;
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const int* gi = grid_idx + (size_t)tf * cap;
-    const float x = kq.x + dx, y = kq.y + dy, r = th * st.sf[kq.octave];
+    if (q >= min(pool.counts[qf], cap)) return;
+    const KpIn kq = pool.kps[(size_t)qf * cap + q];
+    const PoolRow T = pool.row(tf);
+    const float x = kq.x + A.dx, y = kq.y + A.dy, r = A.th * st.sf[kq.octave];
     const int minLevel = kq.octave - 1, maxLevel = kq.octave + 1;
     const unsigned INV = 0xFFFFFFFFu;
     unsigned topKey[TK_K], topPay[TK_K];                                   // (distance << 16 | position) ascending; payload = bin << 16 | keypoint
 #pragma unroll
     for (int i = 0; i < TK_K; ++i) { topKey[i] = INV; topPay[i] = INV; }
     int cnt = 0;
-    const int nMinCellX = max(0, (int)floorf((x - min_x - r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((x - min_x + r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - min_y - r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((y - min_y + r) * inv_h));
+    const int nMinCellX = max(0, (int)floorf((x - T.min_x - r) * T.inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((x - T.min_x + r) * T.inv_w));
+    const int nMinCellY = max(0, (int)floorf((y - T.min_y - r) * T.inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((y - T.min_y + r) * T.inv_h));
     if (nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0) {
-        const uint4* qp = (const uint4*)(desc + ((size_t)qf * cap + q) * 32);
+        const uint4* qp = (const uint4*)(pool.desc + ((size_t)qf * cap + q) * 32);
         const uint4 qlo = qp[0], qhi = qp[1];
         const u64 a[4] = {(u64)qlo.x | ((u64)qlo.y << 32), (u64)qlo.z | ((u64)qlo.w << 32),
                           (u64)qhi.x | ((u64)qhi.y << 32), (u64)qhi.z | ((u64)qhi.w << 32)};
@@ -1348,8 +1364,8 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
         int cj0 = 0, clen = 0;
         if (lane < ncols) {
             const int ix = nMinCellX + lane;
-            cj0 = gs[ix * 48 + nMinCellY];
-            clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+            cj0 = T.gs[ix * 48 + nMinCellY];
+            clen = T.gs[ix * 48 + nMaxCellY + 1] - cj0;
         }
         int total;
         const int coff = wave_excl_scan(clen, &total);
@@ -1366,8 +1382,8 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
             int k = 0;
             float ang = 0.f;
             if (t < total) {
-                k = gi[myj0 + (t - myoff)];
-                const KpIn kp = kt[k];
+                k = T.gi[myj0 + (t - myoff)];
+                const KpIn kp = T.kt[k];
                 ok = !(kp.octave < minLevel) && !(kp.octave > maxLevel);   // bCheckLevels is true here (maxLevel >= 0)
                 if (!(fabsf(kp.x - x) < r && fabsf(kp.y - y) < r)) ok = false;
                 ang = kp.angle;
@@ -1377,13 +1393,13 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
             unsigned key = INV, pay = INV;
             if (ok) {
                 const int pos = cnt + __popcll(bal & lt);
-                const uint4* tp = (const uint4*)(dt + (size_t)k * 32);
+                const uint4* tp = (const uint4*)(T.dt + (size_t)k * 32);
                 const uint4 lo = tp[0], hi = tp[1];
                 const int d = ham256(a, (u64)lo.x | ((u64)lo.y << 32), (u64)lo.z | ((u64)lo.w << 32),
                                      (u64)hi.x | ((u64)hi.y << 32), (u64)hi.z | ((u64)hi.w << 32));
                 float rot = kq.angle - ang;
                 if (rot < 0.0f) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
+                int bin = (int)roundf(rot * A.factor);
                 if (bin == 30) bin = 0;
                 if (bin < 0 || bin >= 30) bin = TK_NOBIN;
                 key = ((unsigned)d << 16) | (unsigned)pos;                   // positions < 65536 (cap)
@@ -1421,10 +1437,10 @@ __global__ __launch_bounds__(256) void k_track_topk(const KpIn* __restrict__ kps
     }
     if (lane == 0) {
         const size_t o = (size_t)pair * cap + q;
-        out_cnt[o] = cnt;
+        out.cnt[o] = cnt;
 #pragma unroll
         for (int i = 0; i < TK_K; ++i)
-            out_keys[o * TK_K + i] = topKey[i] == INV ? 0xFFFFFFFFu : ((topKey[i] >> 16) << 21) | (topPay[i] & 0x1FFFFFu);
+            out.keys[o * TK_K + i] = topKey[i] == INV ? 0xFFFFFFFFu : ((topKey[i] >> 16) << 21) | (topPay[i] & 0x1FFFFFu);
     }
 }
 
@@ -1692,47 +1708,43 @@ struct Tk16FetchAll {
 #endif  /* ORBX_AB */
 
 // k_track_pack: the searched frames' grid entries as 16-byte records in grid order (see tk16_pass)
-__global__ __launch_bounds__(256) void k_track_pack(const KpIn* __restrict__ kps, int cap, const int* __restrict__ grid_start,
-                                                    const int* __restrict__ grid_idx, int t_first, uint4* __restrict__ ent) {
-    const int pair = blockIdx.y, tf = t_first + pair;
+__global__ __launch_bounds__(256) void k_track_pack(Pool pool, int t_first, uint4* __restrict__ ent) {
+    const int pair = blockIdx.y;
+    const PoolRow T = pool.row(t_first + pair);
     const int pos = blockIdx.x * 256 + threadIdx.x;
-    const int n = min(grid_start[(size_t)tf * (64 * 48 + 1) + 64 * 48], cap);
+    const int n = min(T.gs[GRID_CELLS], pool.cap);
     if (pos >= n) return;
-    const int k = grid_idx[(size_t)tf * cap + pos];
-    const KpIn kp = kps[(size_t)tf * cap + k];
-    ent[(size_t)pair * cap + pos] = make_uint4(__float_as_uint(kp.x), __float_as_uint(kp.y), __float_as_uint(kp.angle), ((unsigned)kp.octave << 16) | (unsigned)k);
+    const int k = T.gi[pos];
+    const KpIn kp = T.kt[k];
+    ent[(size_t)pair * pool.cap + pos] = make_uint4(__float_as_uint(kp.x), __float_as_uint(kp.y), __float_as_uint(kp.angle), ((unsigned)kp.octave << 16) | (unsigned)k);
 }
 
 // the kernel's body; Pass: how a pass of up to 64 entries per query turns into candidates (Tk16Filter; the A/B build also has Tk16FetchAll)
 template <class Pass>
-__device__ __forceinline__ void tk16_body(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                          const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
-                                          const uint4* __restrict__ ent, float min_x, float min_y, float inv_w, float inv_h,
-                                          int q_first, int t_first, float th, const ScaleTab& st, float dx, float dy, float factor,
-                                          int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys) {
+__device__ __forceinline__ void tk16_body(const Pool& pool, const uint4* __restrict__ ent, const TrackArgs& A, const ScaleTab& st, const TopList& out) {
     __shared__ int2 sCol[16][64];                                           // per query: (offset in the flattened list, first grid entry) of each window column
     __shared__ uint2 sTop[16][TK_K];                                        // per query: (distance << 16 | position, output word), ascending
     __shared__ int sAdj[16][64];                                            // per query: grid position - list position of the first 64 window entries
     __shared__ uint2 sK[16][16];                                            // per query: the candidates that passed, one per lane
     const int lane = threadIdx.x & 63, l16 = threadIdx.x & 15, wr = lane >> 4, qr = threadIdx.x >> 4;
     const int pair = blockIdx.y;
-    const int qf = q_first + pair, tf = t_first + pair;
-    const int nq = min(counts[qf], cap);
+    const int qf = A.q_first + pair, cap = pool.cap;
+    const int nq = min(pool.counts[qf], cap);
     if ((int)blockIdx.x * 16 >= nq) return;
     const int q = blockIdx.x * 16 + qr;
     const bool live = q < nq;
-    const KpIn kq = kps[(size_t)qf * cap + (live ? q : 0)];
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const float x = kq.x + dx, y = kq.y + dy, r = th * st.sf[kq.octave];
+    const KpIn kq = pool.kps[(size_t)qf * cap + (live ? q : 0)];
+    const PoolRow T = pool.row(A.t_first + pair);
+    const float x = kq.x + A.dx, y = kq.y + A.dy, r = A.th * st.sf[kq.octave];
     const unsigned INV = 0xFFFFFFFFu;
-    const int nMinCellX = max(0, (int)floorf((x - min_x - r) * inv_w));
-    const int nMaxCellX = min(63, (int)ceilf((x - min_x + r) * inv_w));
-    const int nMinCellY = max(0, (int)floorf((y - min_y - r) * inv_h));
-    const int nMaxCellY = min(47, (int)ceilf((y - min_y + r) * inv_h));
+    const int nMinCellX = max(0, (int)floorf((x - T.min_x - r) * T.inv_w));
+    const int nMaxCellX = min(63, (int)ceilf((x - T.min_x + r) * T.inv_w));
+    const int nMinCellY = max(0, (int)floorf((y - T.min_y - r) * T.inv_h));
+    const int nMaxCellY = min(47, (int)ceilf((y - T.min_y + r) * T.inv_h));
     const bool hit = live && nMinCellX < 64 && nMaxCellX >= 0 && nMinCellY < 48 && nMaxCellY >= 0;
     const int ncols = hit ? nMaxCellX - nMinCellX + 1 : 0;                  // <= 64
     u64 a[4];
-    load_desc(desc + ((size_t)qf * cap + (live ? q : 0)) * 32, a);
+    load_desc(pool.desc + ((size_t)qf * cap + (live ? q : 0)) * 32, a);
     if (l16 < TK_K) sTop[qr][l16] = make_uint2(INV, INV);
     int total = 0;
     for (int cb = 0; __any(cb < ncols); cb += 16) {
@@ -1740,8 +1752,8 @@ __device__ __forceinline__ void tk16_body(const KpIn* __restrict__ kps, const ui
         int cj0 = 0, clen = 0;
         if (c < ncols) {
             const int ix = nMinCellX + c;
-            cj0 = gs[ix * 48 + nMinCellY];
-            clen = gs[ix * 48 + nMaxCellY + 1] - cj0;
+            cj0 = T.gs[ix * 48 + nMinCellY];
+            clen = T.gs[ix * 48 + nMaxCellY + 1] - cj0;
         }
         int sc = clen;                                                      // inclusive prefix sum inside the 16-lane row
         sc += __builtin_amdgcn_update_dpp(0, sc, 0x111, 0xf, 0xf, true);
@@ -1759,8 +1771,8 @@ __device__ __forceinline__ void tk16_body(const KpIn* __restrict__ kps, const ui
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");                  // a row lives inside one wave: LDS traffic of the same wave is ordered
     __builtin_amdgcn_wave_barrier();
     Tk16 c;
-    c.ent = ent + (size_t)pair * cap; c.dt = desc + (size_t)tf * cap * 32; c.cap = cap;
-    c.x = x; c.y = y; c.r = r; c.qangle = kq.angle; c.factor = factor; c.minLevel = kq.octave - 1; c.maxLevel = kq.octave + 1;
+    c.ent = ent + (size_t)pair * cap; c.dt = T.dt; c.cap = cap;
+    c.x = x; c.y = y; c.r = r; c.qangle = kq.angle; c.factor = A.factor; c.minLevel = kq.octave - 1; c.maxLevel = kq.octave + 1;
     c.total = total; c.ncols = ncols; c.qr = qr; c.l16 = l16; c.wr = wr;
     const int maxTotal = max(max(__builtin_amdgcn_readlane(total, 0), __builtin_amdgcn_readlane(total, 16)),
                              max(__builtin_amdgcn_readlane(total, 32), __builtin_amdgcn_readlane(total, 48)));
@@ -1779,35 +1791,38 @@ __device__ __forceinline__ void tk16_body(const KpIn* __restrict__ kps, const ui
     }
     if (live) {
         const size_t o = (size_t)pair * cap + q;
-        if (l16 == 0) out_cnt[o] = cnt;
-        if (l16 < TK_K) { const uint2 e = sTop[qr][l16]; out_keys[o * TK_K + l16] = e.x == INV ? INV : e.y; }
+        if (l16 == 0) out.cnt[o] = cnt;
+        if (l16 < TK_K) { const uint2 e = sTop[qr][l16]; out.keys[o * TK_K + l16] = e.x == INV ? INV : e.y; }
     }
 }
 
+// (the kernels keep the loose parameters their generated code was tuned with; the body takes the views)
 #define TK16_PARAMS const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,                 \
                     const int* __restrict__ grid_start, const uint4* __restrict__ ent, float min_x, float min_y, float inv_w, float inv_h,    \
                     int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor, int* __restrict__ out_cnt,             \
                     unsigned int* __restrict__ out_keys
-#define TK16_ARGS kps, desc, counts, cap, grid_start, ent, min_x, min_y, inv_w, inv_h, q_first, t_first, th, st, dx, dy, factor, out_cnt, out_keys
-__global__ __launch_bounds__(256) void k_track_topk16(TK16_PARAMS) { tk16_body<Tk16Filter>(TK16_ARGS); }
+#define TK16_BODY(Pass) tk16_body<Pass>(Pool{kps, desc, counts, cap, grid_start, nullptr, min_x, min_y, inv_w, inv_h}, ent,                 \
+                                        TrackArgs{q_first, t_first, th, dx, dy, factor}, st, TopList{out_cnt, out_keys, nullptr})
+__global__ __launch_bounds__(256) void k_track_topk16(TK16_PARAMS) { TK16_BODY(Tk16Filter); }
 #ifdef ORBX_AB   /* A/B reference, not in the product library */
-__global__ __launch_bounds__(256) void k_track_topk16_v1(TK16_PARAMS) { tk16_body<Tk16FetchAll>(TK16_ARGS); }
+__global__ __launch_bounds__(256) void k_track_topk16_v1(TK16_PARAMS) { TK16_BODY(Tk16FetchAll); }
 #endif
 #undef TK16_PARAMS
-#undef TK16_ARGS
+#undef TK16_BODY
 
 #ifdef ORBX_AB   /* A/B reference (eight queries per step), not in the product library */
-__global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                                    const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
-                                                    const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
-                                                    int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
+__global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                    const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                    float min_x, float min_y, float inv_w, float inv_h, int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
                                                     const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys,
                                                     const uint8_t* __restrict__ t_blocked, const uint8_t* __restrict__ q_obs, int check_ori,
                                                     unsigned int* __restrict__ accepted, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ unsigned int tk_lds[];                                // blocked bit array [ceil(cap / 32)], hist[32], "query has observations" bits [ceil(cap / 32)]
     const int lane = threadIdx.x, pair = blockIdx.x;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
+    const TrackArgs A{q_first, t_first, th, dx, dy, factor};
     const int qf = q_first + pair, tf = t_first + pair;
-    const int nq = min(counts[qf], cap), nt = min(counts[tf], cap);
+    const int nq = min(pool.counts[qf], cap), nt = min(pool.counts[tf], cap);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blk = tk_lds;
     unsigned int* hist = tk_lds + nwords;
@@ -1899,13 +1914,12 @@ __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps
             else {
                 const int c = __builtin_amdgcn_readlane(cnt, 8 * s);
                 if (c > TK_K) {                                             // the list ran dry, the window holds more: rescan it, blocked set applied
-                    const KpIn kq = kps[(size_t)qf * cap + qi];                     // the window k_track_topk16 swept
-                    const Win w = {kq.x + dx, kq.y + dy, th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
+                    const KpIn kq = pool.kps[(size_t)qf * cap + qi];                // the window k_track_topk16 swept
+                    const Win w = {kq.x + A.dx, kq.y + A.dy, A.th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
                     u64 a[4], top[TK_K];
-                    load_desc(desc + ((size_t)qf * cap + qi) * 32, a);
+                    load_desc(pool.desc + ((size_t)qf * cap + qi) * 32, a);
                     int c2;
-                    win_sweep<false>(w, RotBinPay{kq.angle, factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, nullptr,
-                                     grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                    win_sweep<false>(w, RotBinPay{kq.angle, A.factor}, pool.row(tf), nullptr, a, blk, lane, c2, top);
                     best = cand_word(top[0]);
                 }
             }
@@ -1934,17 +1948,18 @@ __global__ __launch_bounds__(64) void k_track_claim(const KpIn* __restrict__ kps
 
 #endif  /* ORBX_AB */
 
-__global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc,
-                                                    const int* __restrict__ counts, int cap, const int* __restrict__ grid_start,
-                                                    const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
-                                                    int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
+__global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
+                                                    const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                    float min_x, float min_y, float inv_w, float inv_h, int q_first, int t_first, float th, ScaleTab st, float dx, float dy, float factor,
                                                     const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys,
                                                     const uint8_t* __restrict__ t_blocked, const uint8_t* __restrict__ q_obs, int check_ori,
                                                     unsigned int* __restrict__ accepted, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ unsigned int tk_lds[];                                // blocked bit array [ceil(cap / 32)], hist[32], "query has observations" bits [ceil(cap / 32)]
     const int lane = threadIdx.x, pair = blockIdx.x;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
+    const TrackArgs A{q_first, t_first, th, dx, dy, factor};
     const int qf = q_first + pair, tf = t_first + pair;
-    const int nq = min(counts[qf], cap), nt = min(counts[tf], cap);
+    const int nq = min(pool.counts[qf], cap), nt = min(pool.counts[tf], cap);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blk = tk_lds;
     unsigned int* hist = tk_lds + nwords;
@@ -2038,13 +2053,12 @@ __global__ __launch_bounds__(64) void k_track_claim64(const KpIn* __restrict__ k
                     best = fr ? ki : best;
                 }
                 if (best == 0xFFFFFFFFu && __builtin_amdgcn_readlane(cnt, f) > TK_K) {   // the list ran dry, the window holds more: rescan it, blocked set applied
-                    const KpIn kq = kps[(size_t)qf * cap + qi];                     // the window k_track_topk16 swept
-                    const Win w = {kq.x + dx, kq.y + dy, th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
+                    const KpIn kq = pool.kps[(size_t)qf * cap + qi];                // the window k_track_topk16 swept
+                    const Win w = {kq.x + A.dx, kq.y + A.dy, A.th * st.sf[kq.octave], 0.f, kq.octave - 1, kq.octave + 1};
                     u64 a[4], top[TK_K];
-                    load_desc(desc + ((size_t)qf * cap + qi) * 32, a);
+                    load_desc(pool.desc + ((size_t)qf * cap + qi) * 32, a);
                     int c2;
-                    win_sweep<false>(w, RotBinPay{kq.angle, factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, nullptr,
-                                     grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                    win_sweep<false>(w, RotBinPay{kq.angle, A.factor}, pool.row(tf), nullptr, a, blk, lane, c2, top);
                     best = cand_word(top[0]);
                 }
                 if (best != 0xFFFFFFFFu && (best >> 21) <= 100u) {
@@ -2108,11 +2122,7 @@ __device__ __forceinline__ bool lp_query(const LpRows& R, const float* sf, bool 
     return true;
 }
 
-__global__ __launch_bounds__(256) void k_lp_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
-                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
-                                                 LpRows R, ScaleTab st, int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys,
-                                                 float* __restrict__ out_r) {
+__global__ __launch_bounds__(256) void k_lp_topk(Pool pool, int t_first, const float* __restrict__ uright, LpRows R, ScaleTab st, TopList out) {
     const int lane = threadIdx.x & 63;
     const int f = blockIdx.y, tf = t_first + f;
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -2125,25 +2135,23 @@ __global__ __launch_bounds__(256) void k_lp_topk(const KpIn* __restrict__ kps, c
     if (lp_query(R, st.sf, uright != nullptr, o, w)) {
         u64 a[4];
         load_desc(R.qdesc + (R.q_shared ? (size_t)q : o) * 32, a);
-        win_sweep<true>(w, OctavePay{}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)f * cap : nullptr,
-                        grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
+        win_sweep<true>(w, OctavePay{}, pool.row(tf), uright ? uright + (size_t)f * pool.cap : nullptr, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
         for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
-    if (lane == 0) put_topk(out_cnt, out_r, out_keys, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
+    if (lane == 0) put_topk(out, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
 }
 
 __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
-                                                 const uint8_t* __restrict__ t_blocked, LpRows R, float nnratio,
-                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
-                                                 int* __restrict__ match, int* __restrict__ nmatches) {
+                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright, const uint8_t* __restrict__ t_blocked,
+                                                 LpRows R, float nnratio, TopList L, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ unsigned int lp_lds[];                                 // blocked bit array [ceil(cap / 32)], the current 64 queries' lists [64][TK_K]
     const unsigned INV = 0xFFFFFFFFu;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
     const int lane = threadIdx.x, f = blockIdx.x, tf = t_first + f;
-    const int nt = min(max(counts[tf], 0), cap);
+    const int nt = min(max(pool.counts[tf], 0), cap);
     const int nq = min(max(R.nq[f], 0), R.q_stride);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blk = lp_lds;
@@ -2152,11 +2160,8 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
     for (int wd = lane; wd < nwords; wd += 64) blk[wd] = bits_word(t_blocked ? t_blocked + (size_t)f * cap : nullptr, nt, wd, 0u);
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
     __syncthreads();
-    const KpIn* kt = kps + (size_t)tf * cap;
-    const uint8_t* dt = desc + (size_t)tf * cap * 32;
+    const PoolRow T = pool.row(tf);
     const float* urt = uright ? uright + (size_t)f * cap : nullptr;
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const int* gi = grid_idx + (size_t)tf * cap;
     const size_t rowBase = (size_t)f * R.q_stride;
     int nm = 0;
     // the next 64 queries' lists, counts and observation flags are in flight while the current ones are replayed (clamped, unconditional loads)
@@ -2166,9 +2171,9 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
     auto fetch = [&](int W0) {
         const int last = nq * TK_K - 1;
 #pragma unroll
-        for (int r = 0; r < TK_K; ++r) pk[r] = topKeys[rowBase * TK_K + min(W0 * TK_K + r * 64 + lane, last)];
+        for (int r = 0; r < TK_K; ++r) pk[r] = L.keys[rowBase * TK_K + min(W0 * TK_K + r * 64 + lane, last)];
         const int qc = min(W0 + lane, nq - 1);
-        pc = topCnt[rowBase + qc];
+        pc = L.cnt[rowBase + qc];
         pob = R.mp_obs[R.q_shared ? (size_t)qc : rowBase + qc];
     };
     if (nq > 0) fetch(0);
@@ -2201,11 +2206,11 @@ __global__ __launch_bounds__(64) void k_lp_claim(const KpIn* __restrict__ kps, c
             if (w2 == INV && __builtin_amdgcn_readlane(cnt, i) > TK_K) {
                 // best AND second must come from the unblocked candidates: the listed ones ran dry, the window holds more
                 const size_t o = rowBase + W0 + i;
-                const Win w = {R.px[o], R.py[o], topR[o], uright ? R.pxr[o] : 0.f, R.level[o] - 1, R.level[o]};   // the window k_lp_topk swept
+                const Win w = {R.px[o], R.py[o], L.r[o], uright ? R.pxr[o] : 0.f, R.level[o] - 1, R.level[o]};   // the window k_lp_topk swept
                 u64 a[4], top[TK_K];                                         // (its radius from there: no scale table here)
                 load_desc(R.qdesc + (R.q_shared ? (size_t)(W0 + i) : o) * 32, a);
                 int c2;
-                win_sweep<false>(w, OctavePay{}, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                win_sweep<false>(w, OctavePay{}, T, urt, a, blk, lane, c2, top);
                 w1 = cand_word(top[0]); w2 = cand_word(top[1]);
             }
             if (w1 == INV) continue;
@@ -2283,11 +2288,8 @@ __device__ __forceinline__ bool mm_query(const MmRows& R, const float* sf, float
 }
 
 template <bool RETRY>
-__global__ __launch_bounds__(256) void k_mm_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
-                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
-                                                 MmRows R, ScaleTab st, float th, const int* __restrict__ nmatches,
-                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r) {
+__global__ __launch_bounds__(256) void k_mm_topk(Pool pool, int t_first, const float* __restrict__ uright, MmRows R, ScaleTab st, float th,
+                                                 const int* __restrict__ nmatches, TopList out) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y, tf = t_first + p;
     if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // the first search of this pair stands
@@ -2302,28 +2304,23 @@ __global__ __launch_bounds__(256) void k_mm_topk(const KpIn* __restrict__ kps, c
     if (mm_query(R, st.sf, th, uright != nullptr, p, o, w)) {
         u64 a[4];
         load_desc(R.qdesc + o * 32, a);
-        win_sweep<true>(w, RotBinPay{R.angle[o], R.factor}, kps + (size_t)tf * cap, desc + (size_t)tf * cap * 32, uright ? uright + (size_t)p * cap : nullptr,
-                        grid_start + (size_t)tf * (64 * 48 + 1), grid_idx + (size_t)tf * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top);
+        win_sweep<true>(w, RotBinPay{R.angle[o], R.factor}, pool.row(tf), uright ? uright + (size_t)p * pool.cap : nullptr, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
         for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
-    if (lane == 0) put_topk(out_cnt, out_r, out_keys, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
+    if (lane == 0) put_topk(out, o, cnt, w.r, top);    // (the radius is read back only by a rescan: count > TK_K)
 }
 
 template <bool RETRY>
-__global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
-                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, int t_first, const float* __restrict__ uright,
-                                                 const uint8_t* __restrict__ t_blocked, MmRows R,
-                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
-                                                 unsigned int* __restrict__ accepted,
+__global__ __launch_bounds__(64) void k_mm_claim(Pool pool, int t_first, const float* __restrict__ uright, const uint8_t* __restrict__ t_blocked,
+                                                 MmRows R, TopList L, unsigned int* __restrict__ accepted,
                                                  int* __restrict__ match, int* __restrict__ nmatches, uint8_t* __restrict__ retried) {
     extern __shared__ unsigned int mm_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][TK_K]
     const unsigned INV = 0xFFFFFFFFu;
-    const int lane = threadIdx.x, p = blockIdx.x, tf = t_first + p;
+    const int lane = threadIdx.x, p = blockIdx.x, tf = t_first + p, cap = pool.cap;
     if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // (wave-uniform) the first search of this pair stands
-    const int nt = min(max(counts[tf], 0), cap);
+    const int nt = min(max(pool.counts[tf], 0), cap);
     const int nq = min(max(R.nq[p], 0), R.q_stride);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blk = mm_lds;
@@ -2335,18 +2332,15 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
     if (lane < 32) hist[lane] = 0;
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
     __syncthreads();
-    const KpIn* kt = kps + (size_t)tf * cap;
-    const uint8_t* dt = desc + (size_t)tf * cap * 32;
+    const PoolRow T = pool.row(tf);
     const float* urt = uright ? uright + (size_t)p * cap : nullptr;
-    const int* gs = grid_start + (size_t)tf * (64 * 48 + 1);
-    const int* gi = grid_idx + (size_t)tf * cap;
     const size_t rowBase = (size_t)p * R.q_stride;
     unsigned int* acc = accepted + rowBase;                                  // (slot | bin << 16) of every assignment with a bin, in order
     int nm = 0, nacc = 0;
     // the next 64 queries' lists and counts are in flight while the current ones are replayed (clamped, unconditional loads);
     // mp_obs is read only for a query with candidates (a skipped row reads nothing else)
-    const unsigned int* keyRow = topKeys + rowBase * TK_K;
-    const int* cntRow = topCnt + rowBase;
+    const unsigned int* keyRow = L.keys + rowBase * TK_K;
+    const int* cntRow = L.cnt + rowBase;
     const uint8_t* obRow = R.mp_obs + rowBase;
     unsigned int pk[TK_K];
     int pc = 0;
@@ -2385,12 +2379,12 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
                 // every listed candidate is blocked and the window holds more: the window again, blocked set applied
                 const size_t o = rowBase + W0 + i;
                 Win w;                                                       // the window k_mm_topk swept (its radius from there: no scale table here)
-                w.r = topR[o];
+                w.r = L.r[o];
                 mm_levels(R, p, R.octave[o], o, urt != nullptr, w);
                 u64 a[4], top[TK_K];
                 load_desc(R.qdesc + o * 32, a);
                 int c2;
-                win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, kt, dt, urt, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, T, urt, a, blk, lane, c2, top);
                 best = cand_word(top[0]);
             }
             if (best == INV || (best >> 21) > 100u) continue;                // TH_HIGH (:2589)
@@ -2433,16 +2427,13 @@ __global__ __launch_bounds__(64) void k_mm_claim(const KpIn* __restrict__ kps, c
 //   the row the entry names and counts down once per entry.
 // RETRY: as k_mm_*: 2 * th, both blocked sets empty, only the pairs whose count is below retry_below (Tracking.cc:3213-3221).
 // ------------------------------------------------------------------------------------------------
-// one camera's rows of a pair and its projections
-struct MmfCam {
-    const KpIn* kt; const uint8_t* dt; const int* gs; const int* gi;
-    const float* px; const float* py;                                       // [npairs][q_stride]
-};
+// one camera's row of a pair and its projections
+struct MmfCam { PoolRow T; const float* px; const float* py; };             // px, py [npairs][q_stride]
 
 // query i of the current 64 (row o) in one camera: the first listed candidate that is not blocked, or, when every listed one is
 // blocked and the window holds more, the window again with the blocked set applied.  0xFFFFFFFF: nothing to claim.
 __device__ __forceinline__ unsigned int mmf_best(const unsigned int* sk, int i, const unsigned int* blk, int cnt, float r, const MmfCam& cam,
-                                                 const MmRows& R, int p, size_t o, float min_x, float min_y, float inv_w, float inv_h, int lane) {
+                                                 const MmRows& R, int p, size_t o, int lane) {
     const unsigned INV = 0xFFFFFFFFu;
     unsigned int key = INV;
     bool fr = false;
@@ -2461,7 +2452,7 @@ __device__ __forceinline__ unsigned int mmf_best(const unsigned int* sk, int i, 
         u64 a[4], top[TK_K];
         load_desc(R.qdesc + o * 32, a);
         int c2;
-        win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, cam.kt, cam.dt, nullptr, cam.gs, cam.gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+        win_sweep<false>(w, RotBinPay{R.angle[o], R.factor}, cam.T, nullptr, a, blk, lane, c2, top);
         best = cand_word(top[0]);
     }
     return best;
@@ -2482,25 +2473,21 @@ __device__ __forceinline__ int rot_cull_lr(const unsigned int* hist, const unsig
     return pruned;
 }
 
-struct MmfLists {                                          // what the two k_mm_topk launches left, [npairs][q_stride] each
-    const int* cnt_l; const unsigned int* keys_l; const float* r_l;
-    const int* cnt_r; const unsigned int* keys_r; const float* r_r;
-};
-
 template <bool RETRY>
 __global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
-                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                  float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
                                                   const uint8_t* __restrict__ blocked_l, const uint8_t* __restrict__ blocked_r, MmRows R,
-                                                  const float* __restrict__ ur, const float* __restrict__ vr, MmfLists T,
+                                                  const float* __restrict__ ur, const float* __restrict__ vr, TopList LL, TopList LR,
                                                   unsigned int* __restrict__ accepted,
                                                   int* __restrict__ match_l, int* __restrict__ match_r, int* __restrict__ nmatches,
                                                   uint8_t* __restrict__ retried) {
     extern __shared__ unsigned int mmf_lds[];                                // blocked bits left, right [ceil(cap / 32)] each, hist[32], the current 64 queries' lists [64][TK_K] per camera
     const unsigned INV = 0xFFFFFFFFu;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
     const int lane = threadIdx.x, p = blockIdx.x, fl = first_l + p, fr = first_r + p;
     if (RETRY && !(nmatches[p] < R.retry_below)) return;                    // (wave-uniform) the first search of this pair stands
-    const int ntl = min(max(counts[fl], 0), cap), ntr = min(max(counts[fr], 0), cap);
+    const int ntl = min(max(pool.counts[fl], 0), cap), ntr = min(max(pool.counts[fr], 0), cap);
     const int nq = min(max(R.nq[p], 0), R.q_stride);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blkL = mmf_lds;
@@ -2517,16 +2504,15 @@ __global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, 
     for (int k = lane; k < cap; k += 64) { mrowL[k] = -1; mrowR[k] = -1; }  // ORBM_NO_MATCH
     __syncthreads();
     const size_t rowBase = (size_t)p * R.q_stride;
-    const MmfCam camL{kps + (size_t)fl * cap, desc + (size_t)fl * cap * 32, grid_start + (size_t)fl * (64 * 48 + 1), grid_idx + (size_t)fl * cap, R.u, R.v};
-    const MmfCam camR{kps + (size_t)fr * cap, desc + (size_t)fr * cap * 32, grid_start + (size_t)fr * (64 * 48 + 1), grid_idx + (size_t)fr * cap, ur, vr};
+    const MmfCam camL{pool.row(fl), R.u, R.v}, camR{pool.row(fr), ur, vr};
     unsigned int* acc = accepted + rowBase * 2;                              // at most one entry per query and camera, in order
     int nm = 0, nacc = 0;
     // the next 64 queries' lists and counts of both cameras are in flight while the current ones are replayed (clamped, unconditional
     // loads); mp_obs is read only for a query with left candidates (any other row reads nothing else)
-    const unsigned int* keyRowL = T.keys_l + rowBase * TK_K;
-    const unsigned int* keyRowR = T.keys_r + rowBase * TK_K;
-    const int* cntRowL = T.cnt_l + rowBase;
-    const int* cntRowR = T.cnt_r + rowBase;
+    const unsigned int* keyRowL = LL.keys + rowBase * TK_K;
+    const unsigned int* keyRowR = LR.keys + rowBase * TK_K;
+    const int* cntRowL = LL.cnt + rowBase;
+    const int* cntRowR = LR.cnt + rowBase;
     const uint8_t* obRow = R.mp_obs + rowBase;
     unsigned int pkL[TK_K], pkR[TK_K];
     int pcL = 0, pcR = 0;
@@ -2563,8 +2549,7 @@ __global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, 
                 const int cn = __builtin_amdgcn_readlane(c ? cntR : cntL, i);
                 if (cn <= 0) continue;                                       // (right) an empty window claims nothing
                 unsigned int* blk = c ? blkR : blkL;
-                const unsigned int best = mmf_best(c ? skR : skL, i, blk, cn, cn > TK_K ? (c ? T.r_r : T.r_l)[o] : 0.f, c ? camR : camL, R, p, o,
-                                                   min_x, min_y, inv_w, inv_h, lane);
+                const unsigned int best = mmf_best(c ? skR : skL, i, blk, cn, cn > TK_K ? (c ? LR.r : LL.r)[o] : 0.f, c ? camR : camL, R, p, o, lane);
                 if (best == INV || (best >> 21) > 100u) continue;            // TH_HIGH (:2590, :2658)
                 const unsigned int k = best & 0xFFFFu, bin = (best >> 16) & 31u;
                 const bool withBin = R.check_ori && bin != TK_NOBIN;
@@ -2604,13 +2589,10 @@ __global__ __launch_bounds__(64) void k_mmf_claim(const KpIn* __restrict__ kps, 
 //   same query already sees.  The right block (:170-236) is the mirror over the right list: mvRightToLeftMatch[best] into match_l,
 //   then match_r[best].  Partner slots are read at claim time (wave-uniform) and honoured only inside the other row's count.
 // ------------------------------------------------------------------------------------------------
-struct LpfCam { const KpIn* kt; const uint8_t* dt; const int* gs; const int* gi; };
-
 // query i of the current 64 (row o, index q of its pair) in one camera: the first two listed candidates that are not blocked, or,
 // when the truncated list holds fewer than two, the window again with the blocked set applied.  0xFFFFFFFF: none.
-__device__ __forceinline__ void lpf_top2(const unsigned int* sk, int i, const unsigned int* blk, int cnt, const float* topR, const LpfCam& cam,
-                                         const LpRows& R, size_t o, int q, float min_x, float min_y, float inv_w, float inv_h, int lane,
-                                         unsigned int& w1, unsigned int& w2) {
+__device__ __forceinline__ void lpf_top2(const unsigned int* sk, int i, const unsigned int* blk, int cnt, const float* topR, const PoolRow& T,
+                                         const LpRows& R, size_t o, int q, int lane, unsigned int& w1, unsigned int& w2) {
     const unsigned INV = 0xFFFFFFFFu;
     unsigned int key = INV;
     bool fr = false;
@@ -2631,21 +2613,22 @@ __device__ __forceinline__ void lpf_top2(const unsigned int* sk, int i, const un
         u64 a[4], top[TK_K];
         load_desc(R.qdesc + (R.q_shared ? (size_t)q : o) * 32, a);
         int c2;
-        win_sweep<false>(w, OctavePay{}, cam.kt, cam.dt, nullptr, cam.gs, cam.gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+        win_sweep<false>(w, OctavePay{}, T, nullptr, a, blk, lane, c2, top);
         w1 = cand_word(top[0]); w2 = cand_word(top[1]);
     }
 }
 
 __global__ __launch_bounds__(64) void k_lpf_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
-                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                  float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
+                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
+                                                 float min_x, float min_y, float inv_w, float inv_h, int first_l, int first_r,
                                                   const uint8_t* __restrict__ blocked_l, const uint8_t* __restrict__ blocked_r,
                                                   const int* __restrict__ l2r, const int* __restrict__ r2l, LpRows RL, LpRows RR, float nnratio,
-                                                  MmfLists T, int* __restrict__ match_l, int* __restrict__ match_r, int* __restrict__ nmatches) {
+                                                  TopList LL, TopList LR, int* __restrict__ match_l, int* __restrict__ match_r, int* __restrict__ nmatches) {
     extern __shared__ unsigned int lpf_lds[];                                // blocked bits left, right [ceil(cap / 32)] each, the current 64 queries' lists [64][TK_K] per camera
     const unsigned INV = 0xFFFFFFFFu;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
     const int lane = threadIdx.x, p = blockIdx.x, fl = first_l + p, fr = first_r + p;
-    const int ntl = min(max(counts[fl], 0), cap), ntr = min(max(counts[fr], 0), cap);
+    const int ntl = min(max(pool.counts[fl], 0), cap), ntr = min(max(pool.counts[fr], 0), cap);
     const int nq = min(max(RL.nq[p], 0), RL.q_stride);
     const int nwords = (cap + 31) >> 5;
     unsigned int* blkL = lpf_lds;
@@ -2660,17 +2643,16 @@ __global__ __launch_bounds__(64) void k_lpf_claim(const KpIn* __restrict__ kps, 
     for (int k = lane; k < cap; k += 64) { mrowL[k] = -1; mrowR[k] = -1; }  // ORBM_NO_MATCH
     __syncthreads();
     const size_t rowBase = (size_t)p * RL.q_stride;
-    const LpfCam camL{kps + (size_t)fl * cap, desc + (size_t)fl * cap * 32, grid_start + (size_t)fl * (64 * 48 + 1), grid_idx + (size_t)fl * cap};
-    const LpfCam camR{kps + (size_t)fr * cap, desc + (size_t)fr * cap * 32, grid_start + (size_t)fr * (64 * 48 + 1), grid_idx + (size_t)fr * cap};
+    const PoolRow camL = pool.row(fl), camR = pool.row(fr);
     const int* l2rRow = l2r ? l2r + (size_t)p * cap : nullptr;               // mvLeftToRightMatch / mvRightToLeftMatch of the pair
     const int* r2lRow = r2l ? r2l + (size_t)p * cap : nullptr;
     int nm = 0;
     // the next 64 queries' lists and counts of both cameras are in flight while the current ones are replayed (clamped, unconditional
     // loads); mp_obs is read only for a query with candidates in either camera (any other row reads nothing else)
-    const unsigned int* keyRowL = T.keys_l + rowBase * TK_K;
-    const unsigned int* keyRowR = T.keys_r + rowBase * TK_K;
-    const int* cntRowL = T.cnt_l + rowBase;
-    const int* cntRowR = T.cnt_r + rowBase;
+    const unsigned int* keyRowL = LL.keys + rowBase * TK_K;
+    const unsigned int* keyRowR = LR.keys + rowBase * TK_K;
+    const int* cntRowL = LL.cnt + rowBase;
+    const int* cntRowR = LR.cnt + rowBase;
     const uint8_t* obRow = RL.mp_obs + (RL.q_shared ? (size_t)0 : rowBase);
     unsigned int pkL[TK_K], pkR[TK_K];
     int pcL = 0, pcR = 0;
@@ -2709,7 +2691,7 @@ __global__ __launch_bounds__(64) void k_lpf_claim(const KpIn* __restrict__ kps, 
                 unsigned int* blk = c ? blkR : blkL;
                 unsigned int* oblk = c ? blkL : blkR;
                 unsigned int w1, w2;
-                lpf_top2(c ? skR : skL, i, blk, cn, c ? T.r_r : T.r_l, c ? camR : camL, c ? RR : RL, o, W0 + i, min_x, min_y, inv_w, inv_h, lane, w1, w2);
+                lpf_top2(c ? skR : skL, i, blk, cn, c ? LR.r : LL.r, c ? camR : camL, c ? RR : RL, o, W0 + i, lane, w1, w2);
                 if (w1 == INV) continue;                                     // every candidate blocked: bestDist stays 256
                 const int bestDist = (int)(w1 >> 21), bestLevel = (int)((w1 >> 16) & 31u) - 1;
                 const int bestDist2 = w2 == INV ? 256 : (int)(w2 >> 21), bestLevel2 = w2 == INV ? -1 : (int)((w2 >> 16) & 31u) - 1;
@@ -2862,10 +2844,7 @@ __device__ __forceinline__ int fuse_project(const float* T, const float* O, cons
     return ns;
 }
 
-__global__ __launch_bounds__(256) void k_fuse_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
-                                                   const float* __restrict__ uright, const int* __restrict__ grid_start,
-                                                   const int* __restrict__ grid_idx, float min_x, float min_y, float inv_w, float inv_h,
-                                                   const int* __restrict__ kf_row, const float* __restrict__ tcw, const float* __restrict__ ow,
+__global__ __launch_bounds__(256) void k_fuse_topk(Pool pool, const float* __restrict__ uright, const int* __restrict__ kf_row, const float* __restrict__ tcw, const float* __restrict__ ow,
                                                    FuseRows R, FuseParams P, int* __restrict__ best_idx, int* __restrict__ level_out) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y;
@@ -2883,11 +2862,10 @@ __global__ __launch_bounds__(256) void k_fuse_topk(const KpIn* __restrict__ kps,
         u64 a[4];
         load_desc(R.qdesc + qo * 32, a);
         const Win w = {u, v, P.th * P.sf[lvl], 0.f, lvl - 1, lvl};               // radius = th * mvScaleFactors[nPredictedLevel]
-        const FuseGate g = {u, v, ur, uright ? uright + (size_t)row * cap : nullptr, P.isg, P.chi2 != 0};
+        const FuseGate g = {u, v, ur, uright ? uright + (size_t)row * pool.cap : nullptr, P.isg, P.chi2 != 0};
         int cnt;
         u64 top[TK_K];
-        win_sweep<true>(w, OctavePay{}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr, grid_start + (size_t)row * (64 * 48 + 1),
-                        grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr, lane, cnt, top, g);
+        win_sweep<true>(w, OctavePay{}, pool.row(row), nullptr, a, nullptr, lane, cnt, top, g);
         if (top[0] != ~0ull && (int)(top[0] >> 40) <= 50) best = (int)(top[0] & 0xFFFFu);   // bestDist <= TH_LOW
     }
     if (lane == 0) {
@@ -2954,12 +2932,8 @@ __device__ __forceinline__ int rl_project(const float* T, const float* O, const 
     return ns;
 }
 
-__global__ __launch_bounds__(256) void k_rl_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
-                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row,
-                                                 const float* __restrict__ tcw, const float* __restrict__ ow, RlRows R, RlParams P,
-                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r,
-                                                 float4* __restrict__ out_win) {
+__global__ __launch_bounds__(256) void k_rl_topk(Pool pool, const int* __restrict__ f_row, const float* __restrict__ tcw, const float* __restrict__ ow,
+                                                 RlRows R, RlParams P, TopList out, float4* __restrict__ out_win) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y;
     const int row = f_row ? f_row[p] : p;
@@ -2977,15 +2951,13 @@ __global__ __launch_bounds__(256) void k_rl_topk(const KpIn* __restrict__ kps, c
         load_desc(R.qdesc + o * 32, a);
         r = P.th * P.sf[lvl];                                                // radius = th * mvScaleFactors[nPredictedLevel], :2775
         const Win w = {u, v, r, 0.f, lvl - 1, lvl + 1};
-        win_sweep<true>(w, RotBinPay{R.angle[o], P.factor}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr,
-                        grid_start + (size_t)row * (64 * 48 + 1), grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr,
-                        lane, cnt, top);
+        win_sweep<true>(w, RotBinPay{R.angle[o], P.factor}, pool.row(row), nullptr, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
         for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
     if (lane == 0) {
-        put_topk(out_cnt, out_r, out_keys, o, cnt, r, top);
+        put_topk(out, o, cnt, r, top);
         out_win[o] = make_float4(u, v, 0.f, __int_as_float(lvl));            // read back only by a rescan (count > TK_K)
     }
 }
@@ -3004,17 +2976,18 @@ struct RlPol {
 template <class Pol>
 __global__ __launch_bounds__(64) void k_claim(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, const int* __restrict__ counts, int cap,
                                                  const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row,
-                                                 const uint8_t* __restrict__ f_blocked, typename Pol::Rows R, typename Pol::Params P,
-                                                 const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
-                                                 const float4* __restrict__ topWin, unsigned int* __restrict__ accepted,
-                                                 int* __restrict__ match, int* __restrict__ nmatches) {
+                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ f_row, const uint8_t* __restrict__ f_blocked,
+                                              typename Pol::Rows R, typename Pol::Params P,
+                                              const int* __restrict__ topCnt, const unsigned int* __restrict__ topKeys, const float* __restrict__ topR,
+                                              const float4* __restrict__ topWin,
+                                              unsigned int* __restrict__ accepted, int* __restrict__ match, int* __restrict__ nmatches) {
     extern __shared__ unsigned int rl_lds[];                                 // blocked bits [ceil(cap / 32)], hist[32], the current 64 queries' lists [64][TK_K]
     const unsigned INV = 0xFFFFFFFFu;
+    const Pool pool{kps, desc, counts, cap, grid_start, grid_idx, min_x, min_y, inv_w, inv_h};
     const int lane = threadIdx.x, p = blockIdx.x;
     const int row = f_row ? f_row[p] : p;
     const bool live = row >= 0 && row < P.nf_rows;                           // (wave-uniform) an out-of-range row: all NO_MATCH and 0
-    const int nt = live ? min(max(counts[row], 0), cap) : 0;
+    const int nt = live ? min(max(pool.counts[row], 0), cap) : 0;
     const int nq = live ? min(max(R.nq[p], 0), P.q_stride) : 0;
     const int nwords = (cap + 31) >> 5;
     unsigned int* blk = rl_lds;
@@ -3025,11 +2998,7 @@ __global__ __launch_bounds__(64) void k_claim(const KpIn* __restrict__ kps, cons
     if (lane < 32) hist[lane] = 0;
     for (int k = lane; k < cap; k += 64) mrow[k] = -1;                      // ORBM_NO_MATCH
     __syncthreads();
-    const size_t rowOff = live ? (size_t)row : 0;
-    const KpIn* kt = kps + rowOff * cap;
-    const uint8_t* dt = desc + rowOff * cap * 32;
-    const int* gs = grid_start + rowOff * (64 * 48 + 1);
-    const int* gi = grid_idx + rowOff * cap;
+    const PoolRow T = pool.row(live ? (size_t)row : 0);
     const size_t rowBase = (size_t)p * P.q_stride;
     unsigned int* acc = accepted + rowBase;                                  // (slot | bin << 16) of every assignment with a bin, in order
     int nm = 0, nacc = 0;
@@ -3074,7 +3043,7 @@ __global__ __launch_bounds__(64) void k_claim(const KpIn* __restrict__ kps, cons
                 u64 a[4], top[TK_K];
                 load_desc(R.qdesc + o * 32, a);
                 int c2;
-                win_sweep<false>(w, Pol::pay(R, o, P), kt, dt, nullptr, gs, gi, min_x, min_y, inv_w, inv_h, a, blk, lane, c2, top);
+                win_sweep<false>(w, Pol::pay(R, o, P), T, nullptr, a, blk, lane, c2, top);
                 best = cand_word(top[0]);
             }
             if (best == INV || !Pol::accept(best, P)) continue;
@@ -3112,12 +3081,8 @@ __global__ __launch_bounds__(64) void k_claim(const KpIn* __restrict__ kps, cons
 struct S3Claim { int q_stride, nf_rows; float max_dist; };
 
 template <int FORM>
-__global__ __launch_bounds__(256) void k_s3_topk(const KpIn* __restrict__ kps, const uint8_t* __restrict__ desc, int cap,
-                                                 const int* __restrict__ grid_start, const int* __restrict__ grid_idx,
-                                                 float min_x, float min_y, float inv_w, float inv_h, const int* __restrict__ kf_row,
-                                                 const float* __restrict__ tcw, const float* __restrict__ ow, FuseRows R, FuseParams P,
-                                                 int* __restrict__ out_cnt, unsigned int* __restrict__ out_keys, float* __restrict__ out_r,
-                                                 float4* __restrict__ out_win) {
+__global__ __launch_bounds__(256) void k_s3_topk(Pool pool, const int* __restrict__ kf_row, const float* __restrict__ tcw, const float* __restrict__ ow,
+                                                 FuseRows R, FuseParams P, TopList out, float4* __restrict__ out_win) {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.y;
     const int row = kf_row ? kf_row[p] : p;
@@ -3136,15 +3101,13 @@ __global__ __launch_bounds__(256) void k_s3_topk(const KpIn* __restrict__ kps, c
         load_desc(R.qdesc + o * 32, a);
         r = P.th * P.sf[lvl];                                                // radius = th * mvScaleFactors[nPredictedLevel], :622, :744
         const Win w = {u, v, r, 0.f, lvl - 1, lvl};
-        win_sweep<true>(w, OctavePay{}, kps + (size_t)row * cap, desc + (size_t)row * cap * 32, nullptr,
-                        grid_start + (size_t)row * (64 * 48 + 1), grid_idx + (size_t)row * cap, min_x, min_y, inv_w, inv_h, a, nullptr,
-                        lane, cnt, top);
+        win_sweep<true>(w, OctavePay{}, pool.row(row), nullptr, a, nullptr, lane, cnt, top);
     } else {
 #pragma unroll
         for (int i = 0; i < TK_K; ++i) top[i] = ~0ull;
     }
     if (lane == 0) {
-        put_topk(out_cnt, out_r, out_keys, o, cnt, r, top);
+        put_topk(out, o, cnt, r, top);
         out_win[o] = make_float4(u, v, 0.f, __int_as_float(lvl));            // read back only by a rescan (count > TK_K)
     }
 }
