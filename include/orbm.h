@@ -813,12 +813,74 @@ int orbm_stereo_from_rgbd_batch_async(orbm_t*, int nframes, int first, int cap,
  * beyond the count get 0 and (0, 0, 0) too.  With q_stride == cap they are valid x3dw / has_mp inputs of
  * orbm_project_last_frame_batch_async.  Which depth points become temporal MapPoints stays with the caller (UpdateLastFrame takes the
  * 100 closest and those under mThDepth): the caller ANDs its own selection into has_depth.  No scratch: capturable after one eager
- * call (orbx_capture_begin).  ORBM_E_INVALID: a NULL array, nrows or cap < 1, first < 0; ORBM_E_CAPACITY: nrows > 65535. */
+ * call (orbx_capture_begin).  ORBM_E_INVALID: a NULL array, nrows or cap < 1, first < 0; ORBM_E_CAPACITY: nrows > 65535.
+ * That selection is also available on the device: orbm_select_depth_points_batch_async and orbm_adopt_new_points_batch_async below. */
 int orbm_unproject_stereo(orbm_t*, int n, const orbm_kp_t* kps_un, const float* depth, const float* twc12,
                           const float* k, float* x3dw, uint8_t* has_depth);
 int orbm_unproject_stereo_batch_async(orbm_t*, int nrows, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
                                       const float* depth, const float* twc, const float* k_host,
                                       float* x3dw, uint8_t* has_depth);
+/* orbm_select_depth_points / orbm_select_depth_points_batch_async: which depth points of a stereo / RGB-D frame become MapPoints -- the
+ * sorted walk that Tracking::UpdateLastFrame (Tracking.cc:3094-3163, temporal points before TrackWithMotionModel) and
+ * Tracking::CreateNewKeyFrame (Tracking.cc:3694-3783, the new points of every stereo / RGB-D KeyFrame) both run -- and the close counts
+ * of Tracking::NeedNewKeyFrame (Tracking.cc:3524-3546) over the same mvDepth row and threshold.  For one frame with n slots:
+ *  - D = { i < n : mvDepth[i] > 0 }: NaN, 0 and negatives are out; +inf is in, as orbm_stereo_from_rgbd passes it; a positive denormal
+ *    is in (the test runs on the bit pattern, nothing is flushed).
+ *  - D is sorted as std::pair<float,int>: ascending depth, equal depths in ascending slot order (ties by slot).  Slots are unique, so
+ *    the order is total and the result deterministic.
+ *  - The walk visits the sorted points in order and stops after visiting the first position j with depth_j > th_depth && j + 1 >
+ *    max_points (nPoints is incremented in both branches, so it is j + 1).  With c = the number of points of D with !(depth >
+ *    th_depth): nvisit = min(|D|, max(c, max_points) + 1) -- one extra point beyond the bound is visited as well: 150 far points and
+ *    max_points = 100 give 101 visited slots, not 100.  A NaN th_depth never stops the walk (nvisit = |D|).  max_points is the
+ *    reference's 100 (maxPoint).
+ *  - A visited slot creates a new point when it holds no MapPoint or one with Observations() < 1: create_new = visited && !keeps_mp,
+ *    where keeps_mp is the caller's `pMP && pMP->Observations() >= 1` (NULL = no slot holds one).  Other visited slots only advance
+ *    the walk.
+ *  - Close counts: slots with depth > 0 && depth < th_depth, split by tracked = `mvpMapPoints[i] && !mvbOutlier[i]` (NULL = none) into
+ *    nclose_tracked and nclose_untracked.  Mind the strict < here against the > of the walk: a depth equal to th_depth is in neither
+ *    close count, yet it does not stop the walk.  With a NaN th_depth both counts are 0.
+ * Outputs: order[j] = the slot visited at position j < nvisit, -1 for the rest of the row; create_new per slot (0 where not visited);
+ * nvisit, ncreate = the number of create_new slots; nclose_tracked / nclose_untracked may be NULL.  The caller creates its MapPoints
+ * in `order`, which is the order the reference creates them in (and so the order of their ids).
+ * Host form: host pointers, one frame of n slots, synchronous; order [n], create_new [n]; ncreate, nclose_tracked and nclose_untracked
+ * point to one int each and may be NULL; returns nvisit.
+ * Device form: enqueue-only, all pointers device pointers.  Row r of the call uses counts[first + r] (an extractor result block's
+ * counts; n = min(max(count, 0), cap)) and row r of depth [nrows][cap] -- one row per row of the call, as
+ * orbm_unproject_stereo_batch_async reads it and orbm_stereo_from_rgbd_batch_async / orbm_stereo_batch_async write it -- of keeps_mp
+ * and tracked [nrows][cap], and writes row r of order, create_new [nrows][cap] and entry r of nvisit, ncreate, nclose_tracked,
+ * nclose_untracked [nrows].  Slots at or beyond the count are never visited, whatever their depth / keeps_mp hold; their create_new is
+ * written 0 and their order -1, so the rows are fully defined.  One workgroup per row sorts 64-bit keys (depth bits << 32 | slot) in
+ * LDS, sized from cap padded to a power of two; every count is written from the finished row with plain stores:
+ * nothing accumulates across graph replays and nothing needs a memset.  No scratch: capturable after one eager call
+ * (orbx_capture_begin).
+ * Limit: cap (host form: n) <= ORBM_DEPTH_SELECT_MAX_CAP = 16384 -- 128 KiB of keys out of the 160 KiB of LDS; stereo and RGB-D
+ * extractors never use the 5 x nFeatures initialiser.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL required array; nrows or cap < 1 (host form: n < 0); first < 0; max_points < 0.
+ * ORBM_E_CAPACITY, with nothing enqueued: cap above the limit or nrows > 65535.
+ *
+ * orbm_adopt_new_points_batch_async: `new MapPoint(x3D, pMap, &mLastFrame, i)` + `mLastFrame.mvpMapPoints[i] = pNewMP`
+ * (Tracking.cc:3139-3143) as far as M4 reads it, thread per slot, pinhole (Nleft == -1).  Row r of the call is block frame first + r of
+ * counts and desc (the block's descriptor rows [..][cap][32]); create_new [nrows][cap] as the select call wrote it; x3d_new
+ * [nrows][cap][3] the rows orbm_unproject_stereo_batch_async wrote; outlier [nrows][cap] = mvbOutlier (NULL = none).  In/out rows, one
+ * per row of the call: x3dw [nrows][cap][3], has_mp, mp_obs [nrows][cap], qdesc [nrows][cap][32].  Where create_new is set and the slot
+ * lies below the count: x3dw = x3d_new; has_mp = !outlier (M4 tests pMP && !mvbOutlier[i], ORBmatcher.cc:2505-2509); mp_obs = 0 (the
+ * constructor sets nObs(0), MapPoint.cc:92); qdesc = the frame's own descriptor row of that slot (MapPoint.cc:127).  Every other slot is
+ * untouched.  With q_stride == cap the four rows are then inputs of orbm_project_last_frame_batch_async and
+ * orbm_search_by_projection_frame_batch_async as they stand.  desc and qdesc are read / written as 32-bit words: 4-byte aligned.
+ * For CreateNewKeyFrame the map surgery (AddObservation, AddMapPoint, the Atlas), the UnprojectStereoFishEye branch and the
+ * mvLeftToRightMatch partner slot stay with the caller.  No scratch: capturable.  ORBM_E_INVALID: a NULL array other than outlier, nrows
+ * or cap < 1, first < 0; ORBM_E_CAPACITY: nrows > 65535. */
+enum { ORBM_DEPTH_SELECT_MAX_CAP = 16384 };
+int orbm_select_depth_points(orbm_t*, int n, const float* depth, const uint8_t* keeps_mp, const uint8_t* tracked,
+                             float th_depth, int max_points, int32_t* order, uint8_t* create_new,
+                             int32_t* ncreate, int32_t* nclose_tracked, int32_t* nclose_untracked);
+int orbm_select_depth_points_batch_async(orbm_t*, int nrows, int first, int cap, const int32_t* counts, const float* depth,
+                                         const uint8_t* keeps_mp, const uint8_t* tracked, float th_depth, int max_points,
+                                         int32_t* order, uint8_t* create_new, int32_t* nvisit, int32_t* ncreate,
+                                         int32_t* nclose_tracked, int32_t* nclose_untracked);
+int orbm_adopt_new_points_batch_async(orbm_t*, int nrows, int first, int cap, const int32_t* counts, const uint8_t* create_new,
+                                      const float* x3d_new, const uint8_t* desc, const uint8_t* outlier,
+                                      float* x3dw, uint8_t* has_mp, uint8_t* mp_obs, uint8_t* qdesc);
 
 /* ---- MapPoint refresh: the producer of the qdesc / normal / min_dist / max_dist rows that the batched searches read (M3, M4, M5, M6,
  * M13, orbm_is_in_frustum), for a batch of MapPoints over a resident pool of KeyFrame rows.

@@ -21,6 +21,7 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 
 HOST, DEVICE = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1                          # include/orbm.h: ORBM_DEPTH_*
+DEPTH_SELECT_MAX_CAP = 16384                         # include/orbm.h: ORBM_DEPTH_SELECT_MAX_CAP
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -891,6 +892,10 @@ def _install_search():
                                                     vp, ci, ci, ci, ci, cf, cf, vp, vp, vp]    # image table, type, w, h, stride, factor, mbf, outputs
     L.orbm_unproject_stereo.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.orbm_unproject_stereo_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_select_depth_points.argtypes = [vp, ci, vp, vp, vp, cf, ci, vp, vp, vp, vp, vp]     # n, depth, keeps_mp, tracked, th, max_points, outputs
+    L.orbm_select_depth_points_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, cf, ci,   # nrows, first, cap, counts, depth, keeps_mp, tracked, th, max
+                                                       vp, vp, vp, vp, vp, vp]                   # order, create_new, nvisit, ncreate, nclose_tracked / _untracked
+    L.orbm_adopt_new_points_batch_async.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     for name in ("orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async"):
         getattr(L, name).argtypes = [vp, ci, ci, ci, vp, vp,                       # nmp, nkf_rows, cap, desc_kf, counts_kf
                                      ci, vp, vp, vp, vp, vp,                       # nobs, obs_off, obs_row, obs_slot, obs_flags, valid
@@ -942,6 +947,32 @@ def _install_search():
         K = np.ascontiguousarray(K, np.float32)
         return _chk(self.L.orbm_unproject_stereo_batch_async(self.h, nrows, first, cap, kps_un, counts, depth, twc, _p(K), x3dw, has_depth),
                     "orbm_unproject_stereo_batch_async")
+
+    def select_depth_points(self, depth, keeps_mp=None, tracked=None, th_depth=float("inf"), max_points=100):
+        """The sorted walk of Tracking::UpdateLastFrame / CreateNewKeyFrame (Tracking.cc:3094-3163, :3694-3783) and NeedNewKeyFrame's close
+        counts (:3524-3546) over one frame's mvDepth -> (nvisit, order [n], create_new [n], ncreate, nclose_tracked, nclose_untracked).
+        keeps_mp = `pMP && pMP->Observations() >= 1`, tracked = `pMP && !mvbOutlier[i]` per slot (None = no slot)."""
+        d = np.ascontiguousarray(depth, np.float32); n = len(d)
+        k = None if keeps_mp is None else np.ascontiguousarray(keeps_mp, np.uint8); t = None if tracked is None else np.ascontiguousarray(tracked, np.uint8)
+        if (k is not None and len(k) != n) or (t is not None and len(t) != n):
+            raise OrbError("keeps_mp and tracked hold one flag per depth slot")
+        order = np.full(max(n, 1), -1, np.int32); cn = np.zeros(max(n, 1), np.uint8); cnt = np.zeros(3, np.int32)
+        rc = _chk(self.L.orbm_select_depth_points(self.h, n, _p(d), None if k is None else _p(k), None if t is None else _p(t), float(th_depth),
+                                                  int(max_points), _p(order), _p(cn), cnt.ctypes.data, cnt.ctypes.data + 4, cnt.ctypes.data + 8),
+                  "orbm_select_depth_points")
+        return rc, order[:n], cn[:n], int(cnt[0]), int(cnt[1]), int(cnt[2])
+
+    def select_depth_points_batch_async(self, nrows, first, cap, counts, depth, keeps_mp, tracked, th_depth, max_points, order, create_new, nvisit,
+                                        ncreate, nclose_tracked=None, nclose_untracked=None):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_select_depth_points_batch_async)."""
+        return _chk(self.L.orbm_select_depth_points_batch_async(self.h, nrows, first, cap, counts, depth, keeps_mp, tracked, float(th_depth),
+                                                                int(max_points), order, create_new, nvisit, ncreate, nclose_tracked, nclose_untracked),
+                    "orbm_select_depth_points_batch_async")
+
+    def adopt_new_points_batch_async(self, nrows, first, cap, counts, create_new, x3d_new, desc, outlier, x3dw, has_mp, mp_obs, qdesc):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_adopt_new_points_batch_async)."""
+        return _chk(self.L.orbm_adopt_new_points_batch_async(self.h, nrows, first, cap, counts, create_new, x3d_new, desc, outlier, x3dw, has_mp,
+                                                             mp_obs, qdesc), "orbm_adopt_new_points_batch_async")
 
     def _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, valid, nmp):
         off = np.ascontiguousarray(obs_off, np.int32); row = np.ascontiguousarray(obs_row, np.int32); slot = np.ascontiguousarray(obs_slot, np.int32)
@@ -1010,6 +1041,9 @@ def _install_search():
     ORBmatcher.ComputeStereoFromRGBDBatchAsync = stereo_from_rgbd_batch_async
     ORBmatcher.UnprojectStereo = unproject_stereo
     ORBmatcher.UnprojectStereoBatchAsync = unproject_stereo_batch_async
+    ORBmatcher.SelectDepthPoints = select_depth_points
+    ORBmatcher.SelectDepthPointsBatchAsync = select_depth_points_batch_async
+    ORBmatcher.AdoptNewPointsBatchAsync = adopt_new_points_batch_async
     _bind_frame_geometry(L, "orbm_")
     for name, fn in _frame_geometry_methods("orbm_").items():
         setattr(ORBmatcher, name, fn)
@@ -1084,6 +1118,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_search_for_triangulation_batch_async", "orbm_search_for_initialization_batch_async", "orbm_search_by_projection_frame_fisheye",
             "orbm_search_by_projection_points_fisheye", "orbm_search_by_bow_fisheye",
             "orbm_stereo_from_rgbd", "orbm_stereo_from_rgbd_batch_async", "orbm_unproject_stereo", "orbm_unproject_stereo_batch_async",
+            "orbm_select_depth_points", "orbm_select_depth_points_batch_async", "orbm_adopt_new_points_batch_async",
             "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async",
             "orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]

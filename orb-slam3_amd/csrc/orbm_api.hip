@@ -37,6 +37,7 @@ struct orbm {
     hipStream_t ownStream = nullptr;                           // the stream created with the handle (orbm_set_stream may point `stream` elsewhere)
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     bool timed = false, gridFirst = false;
+    bool dselLds = false;                                      // k_depth_select's dynamic LDS limit has been raised (orbm_select_depth_points*)
     bool initLds = false;                                      // k_init_search's dynamic LDS limit has been raised (orbm_search_for_initialization_batch_async)
     // Scratch arena of the single-frame entry points: ONE device block and a pinned host mirror of the same size.  Uploads are
     // staged in the mirror and sent with one asynchronous copy before the kernel, results come back with one copy after it
@@ -2561,6 +2562,114 @@ int orbm_unproject_stereo(orbm_t* m, int n, const orbm_kp_t* kps_un, const float
     int cnt = 0;
     for (int i = 0; i < n; ++i) cnt += has_depth[i] ? 1 : 0;
     return cnt;
+}
+
+// ---- Depth point selection: the sorted walk of Tracking::UpdateLastFrame / CreateNewKeyFrame and NeedNewKeyFrame's close counts ----
+// the tests the host and the device form share; fills the kernel's parameter block (the thresholds as bit patterns: DepthSelParams)
+static int depth_select_params(const char* who, int first, int cap, float th_depth, int max_points, DepthSelParams& P) {
+    if (cap < 1 || first < 0 || max_points < 0) { set_merr("%s: cap must be >= 1, first and max_points >= 0", who); return ORBM_E_INVALID; }
+    if (cap > ORBM_DEPTH_SELECT_MAX_CAP) {
+        set_merr("%s: cap %d above %d (the row's 64-bit keys are sorted in LDS)", who, cap, (int)ORBM_DEPTH_SELECT_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    int n2 = 1;
+    while (n2 < cap) n2 <<= 1;
+    unsigned int tb;
+    memcpy(&tb, &th_depth, sizeof(tb));
+    const bool nan = std::isnan(th_depth), neg = (tb >> 31) != 0;           // -0.0f counts as negative: every positive depth is > it and none is < it
+    P.first = first; P.cap = cap; P.n2 = n2; P.max_points = max_points;
+    P.far_above = nan ? 0xFFFFFFFFu : neg ? 0u : tb;                         // depth > th on the bits of a positive depth; never with a NaN th
+    P.close_below = (nan || neg) ? 0u : tb;                                  // depth < th likewise
+    return ORBM_OK;
+}
+
+static int depth_select_launch(orbm_t* m, const char* who, int nrows, const int32_t* counts, const float* depth, const uint8_t* keeps_mp,
+                               const uint8_t* tracked, const DepthSelParams& P, int32_t* order, uint8_t* create_new, int32_t* nvisit,
+                               int32_t* ncreate, int32_t* nclose_tracked, int32_t* nclose_untracked) {
+    if (!m->dselLds) {                                                       // once per handle, on its first (eager) call: the largest legal size
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(m->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+            set_merr("%s: inside a capture, run the call once eagerly first", who);
+            return ORBM_E_HIP;
+        }
+        MHIPCHK(hipFuncSetAttribute((const void*)k_depth_select, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(ORBM_DEPTH_SELECT_MAX_CAP * sizeof(unsigned long long))));
+        m->dselLds = true;
+    }
+    const int threads = std::min(1024, std::max(64, P.n2 / 2));              // one thread per pair of the bitonic network, whole waves
+    hipLaunchKernelGGL(k_depth_select, dim3(nrows), dim3(threads), (size_t)P.n2 * sizeof(unsigned long long), m->stream, counts, depth, keeps_mp, tracked,
+                       P, order, create_new, nvisit, ncreate, nclose_tracked, nclose_untracked);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_select_depth_points_batch_async(orbm_t* m, int nrows, int first, int cap, const int32_t* counts, const float* depth,
+                                         const uint8_t* keeps_mp, const uint8_t* tracked, float th_depth, int max_points,
+                                         int32_t* order, uint8_t* create_new, int32_t* nvisit, int32_t* ncreate,
+                                         int32_t* nclose_tracked, int32_t* nclose_untracked) {
+    if (!m || !counts || !depth || !order || !create_new || !nvisit || !ncreate) {
+        set_merr("SelectDepthPoints batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nrows < 1) { set_merr("SelectDepthPoints batch: nrows must be >= 1"); return ORBM_E_INVALID; }
+    DepthSelParams P;
+    const int rc = depth_select_params("SelectDepthPoints batch", first, cap, th_depth, max_points, P);
+    if (rc) return rc;
+    if (nrows > 65535) { set_merr("SelectDepthPoints batch: %d rows in one call (at most 65535)", nrows); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    return depth_select_launch(m, "SelectDepthPoints batch", nrows, counts, depth, keeps_mp, tracked, P, order, create_new, nvisit, ncreate,
+                               nclose_tracked, nclose_untracked);
+}
+
+int orbm_select_depth_points(orbm_t* m, int n, const float* depth, const uint8_t* keeps_mp, const uint8_t* tracked, float th_depth, int max_points,
+                             int32_t* order, uint8_t* create_new, int32_t* ncreate, int32_t* nclose_tracked, int32_t* nclose_untracked) {
+    if (!m || n < 0 || (n > 0 && (!depth || !order || !create_new))) {
+        set_merr("SelectDepthPoints: a required array is NULL or n < 0");
+        return ORBM_E_INVALID;
+    }
+    DepthSelParams P;
+    const int rc = depth_select_params("SelectDepthPoints", 0, std::max(n, 1), th_depth, max_points, P);
+    if (rc) return rc;
+    if (ncreate) *ncreate = 0;
+    if (nclose_tracked) *nclose_tracked = 0;
+    if (nclose_untracked) *nclose_untracked = 0;
+    if (n == 0) return 0;
+    MHIPCHK(hipSetDevice(m->device));
+    DevBuf dc, dd, dk, dt, dord, dcn, dcnt;
+    arena_reset(m);
+    UP(dc, &n, sizeof(int)); UP(dd, depth, sizeof(float) * n);
+    if (keeps_mp) UP(dk, keeps_mp, n);
+    if (tracked) UP(dt, tracked, n);
+    AL(dord, sizeof(int) * n); AL(dcn, n); AL(dcnt, sizeof(int) * 4);
+    ARENA_FLUSH(m);
+    int* cnt = dcnt.as<int>();
+    const int rl = depth_select_launch(m, "SelectDepthPoints", 1, dc.as<int>(), dd.as<float>(), keeps_mp ? dk.as<uint8_t>() : nullptr,
+                                       tracked ? dt.as<uint8_t>() : nullptr, P, dord.as<int>(), dcn.as<uint8_t>(), cnt, cnt + 1, cnt + 2, cnt + 3);
+    if (rl) return rl;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(order, dord.host(), sizeof(int) * n); memcpy(create_new, dcn.host(), n);
+    const int* hc = (const int*)dcnt.host();
+    if (ncreate) *ncreate = hc[1];
+    if (nclose_tracked) *nclose_tracked = hc[2];
+    if (nclose_untracked) *nclose_untracked = hc[3];
+    return hc[0];
+}
+
+int orbm_adopt_new_points_batch_async(orbm_t* m, int nrows, int first, int cap, const int32_t* counts, const uint8_t* create_new,
+                                      const float* x3d_new, const uint8_t* desc, const uint8_t* outlier,
+                                      float* x3dw, uint8_t* has_mp, uint8_t* mp_obs, uint8_t* qdesc) {
+    if (!m || !counts || !create_new || !x3d_new || !desc || !x3dw || !has_mp || !mp_obs || !qdesc) {
+        set_merr("AdoptNewPoints batch: a required array is NULL");
+        return ORBM_E_INVALID;
+    }
+    if (nrows < 1 || cap < 1 || first < 0) { set_merr("AdoptNewPoints batch: nrows and cap must be >= 1 and first >= 0"); return ORBM_E_INVALID; }
+    if (nrows > 65535) { set_merr("AdoptNewPoints batch: %d rows in one call (at most 65535)", nrows); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    hipLaunchKernelGGL(k_adopt_new_points, dim3((cap + 255) / 256, nrows), dim3(256), 0, m->stream, counts, first, cap, create_new, x3d_new, desc, outlier,
+                       x3dw, has_mp, mp_obs, qdesc);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
 }
 
 // ---- MapPoint refresh: MapPoint::ComputeDistinctiveDescriptors and MapPoint::UpdateNormalAndDepth -------------------------

@@ -4067,6 +4067,135 @@ __global__ __launch_bounds__(256) void k_unproject_stereo(const KpIn* __restrict
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_depth_select: the sorted walk over a frame's depth points that Tracking::UpdateLastFrame (Tracking.cc:3094-3163) and
+// Tracking::CreateNewKeyFrame (:3694-3783) run, and NeedNewKeyFrame's close counts (:3524-3546).  One workgroup per row of the call.
+//   keys    one 64-bit key per slot i < n with depth > 0: (depth bits) << 32 | i.  Positive IEEE floats, +inf included, order as their
+//           bit patterns, and the slot in the low word breaks ties, so an ascending sort of the keys IS std::sort of pair<float,int>.
+//           Depth tests run on the bits (zbits - 1 < 0x7F800000 is z > 0 without NaN; the thresholds arrive as bit patterns from
+//           the host, DepthSelParams): no compare that could flush a denormal.  The row is padded to n2 = a power of two with all-ones
+//           keys, which no point can equal (a NaN pattern in the high word).
+//   sort    bitonic network in LDS over n2 keys (n2 * 8 B of dynamic LDS: sized from the padded cap).  One thread per PAIR
+//           (i, i | j) with i = 2p - (p & (j - 1)), so every lane of every step works.  For j >= 32 the 32 lanes of a ds_read_b64
+//           group read 32 consecutive keys = 64 banks: conflict-free.  For j < 32 the group's pairs span 64 keys and both reads go
+//           2-way; those are the last five steps of each stage.  Steps with j > 64 end in a workgroup barrier; the steps with j <= 64
+//           stay inside the 128 keys one wave owns and run back to back under a wave barrier (56 of the 66 steps at 2048 keys).
+//   bound   c = points with !(depth > th) (ballot + popcount while the keys are built), nd = |D|;
+//           nvisit = min(nd, max(c, max_points) + 1): the walk stops AFTER visiting the first far point past max_points.
+//   output  order[j] = slot at position j < nvisit, -1 beyond.  A slot was visited iff its key <= the key at position nvisit - 1
+//           (keys are unique), so create_new and the counts are one pass over the slots, every value written once from the finished
+//           row with plain stores: nothing accumulates across graph replays.
+// ------------------------------------------------------------------------------------------------
+struct DepthSelParams { int first, cap, n2, max_points; unsigned int far_above, close_below; };
+
+__global__ __launch_bounds__(1024) void k_depth_select(const int* __restrict__ counts, const float* __restrict__ depth,
+                                                       const uint8_t* __restrict__ keeps_mp, const uint8_t* __restrict__ tracked,
+                                                       DepthSelParams P, int* __restrict__ order, uint8_t* __restrict__ create_new,
+                                                       int* __restrict__ nvisit, int* __restrict__ ncreate,
+                                                       int* __restrict__ nclose_tracked, int* __restrict__ nclose_untracked) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long dsel_keys[];
+    __shared__ int sA[16], sB[16], sC[16];
+    const int r = blockIdx.x, tid = threadIdx.x, T = blockDim.x, wave = tid >> 6, nwaves = T >> 6;
+    const size_t o0 = (size_t)r * P.cap;
+    const int n = min(max(counts[P.first + r], 0), P.cap);
+    const unsigned int* zb = (const unsigned int*)depth + o0;
+    int cntD = 0, cntC = 0;
+    for (int base = 0; base < P.n2; base += T) {                             // uniform trip count: every lane reaches the ballots
+        const int i = base + tid;
+        unsigned long long key = ~0ull;
+        bool has = false, nr = false;
+        if (i < n) {
+            const unsigned int z = zb[i];
+            has = z - 1u < 0x7F800000u;                                      // z > 0: not 0, not negative, not NaN; +inf and denormals pass
+            nr = has && !(z > P.far_above);
+            if (has) key = ((unsigned long long)z << 32) | (unsigned)i;
+        }
+        if (i < P.n2) dsel_keys[i] = key;
+        cntD += __popcll(__ballot(has)); cntC += __popcll(__ballot(nr));
+    }
+    if ((tid & 63) == 0) { sA[wave] = cntD; sB[wave] = cntC; }
+    __syncthreads();
+    const int half = P.n2 >> 1;
+    for (int k = 2; k <= P.n2; k <<= 1) {
+        int j = k >> 1;
+        for (; j > 64; j >>= 1) {                                            // steps that cross waves: a workgroup barrier each
+            for (int p = tid; p < half; p += T) {
+                const int i = 2 * p - (p & (j - 1)), q = i | j;
+                const unsigned long long a = dsel_keys[i], b = dsel_keys[q];
+                if ((a > b) == ((i & k) == 0)) { dsel_keys[i] = b; dsel_keys[q] = a; }
+            }
+            __syncthreads();
+        }
+        // j <= 64: the 64 pairs [64 w, 64 w + 64) of a wave are exactly the keys [128 w, 128 w + 128) at every remaining step, so the
+        // rest of the stage runs back to back on the wave's own keys (LDS accesses of one wave complete in order)
+        for (int p0 = tid & ~63; p0 < half; p0 += T) {                       // wave-uniform trip count
+            const int p = p0 + (tid & 63);
+            for (int jj = j; jj > 0; jj >>= 1) {
+                if (p < half) {
+                    const int i = 2 * p - (p & (jj - 1)), q = i | jj;
+                    const unsigned long long a = dsel_keys[i], b = dsel_keys[q];
+                    if ((a > b) == ((i & k) == 0)) { dsel_keys[i] = b; dsel_keys[q] = a; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+    }
+    int nd = 0, c = 0;
+    for (int w = 0; w < nwaves; ++w) { nd += sA[w]; c += sB[w]; }
+    const int nv = min(nd, max(c, min(P.max_points, nd)) + 1);
+    const unsigned long long kmax = nv > 0 ? dsel_keys[nv - 1] : 0ull;       // no key is 0: depth bits are >= 1
+    int* ord = order + o0;
+    for (int j = tid; j < P.cap; j += T) ord[j] = j < nv ? (int)(unsigned)dsel_keys[j] : -1;
+    int cntN = 0, cntT = 0, cntU = 0;
+    for (int base = 0; base < P.cap; base += T) {
+        const int i = base + tid;
+        bool cn = false, ct = false, cu = false;
+        if (i < n) {
+            const unsigned int z = zb[i];
+            const bool has = z - 1u < 0x7F800000u;
+            const unsigned long long key = ((unsigned long long)z << 32) | (unsigned)i;
+            cn = has && key <= kmax && !(keeps_mp && keeps_mp[o0 + i]);
+            const bool close = has && z < P.close_below;                    // depth > 0 && depth < th (Tracking.cc:3533)
+            const bool trk = tracked && tracked[o0 + i];
+            ct = close && trk; cu = close && !trk;
+        }
+        if (i < P.cap) create_new[o0 + i] = cn ? 1 : 0;
+        cntN += __popcll(__ballot(cn)); cntT += __popcll(__ballot(ct)); cntU += __popcll(__ballot(cu));
+    }
+    __syncthreads();                                                         // sA / sB have been read by every thread
+    if ((tid & 63) == 0) { sA[wave] = cntN; sB[wave] = cntT; sC[wave] = cntU; }
+    __syncthreads();
+    if (tid == 0) {
+        int a = 0, b = 0, u = 0;
+        for (int w = 0; w < nwaves; ++w) { a += sA[w]; b += sB[w]; u += sC[w]; }
+        nvisit[r] = nv; ncreate[r] = a;
+        if (nclose_tracked) nclose_tracked[r] = b;
+        if (nclose_untracked) nclose_untracked[r] = u;
+    }
+}
+
+// k_adopt_new_points: `new MapPoint(x3D, pMap, &mLastFrame, i)` (Tracking.cc:3139-3143) as far as M4 reads it, thread per slot.  Where
+// create_new is set: x3dw = x3d_new, has_mp = !outlier (M4 tests pMP && !mvbOutlier[i], ORBmatcher.cc:2505-2509), mp_obs = 0 (nObs(0),
+// MapPoint.cc:92), qdesc = the frame's descriptor row of that slot (MapPoint.cc:127).  Every other slot is untouched.
+__global__ __launch_bounds__(256) void k_adopt_new_points(const int* __restrict__ counts, int first, int cap, const uint8_t* __restrict__ create_new,
+                                                          const float* __restrict__ x3d_new, const uint8_t* __restrict__ desc,
+                                                          const uint8_t* __restrict__ outlier, float* __restrict__ x3dw,
+                                                          uint8_t* __restrict__ has_mp, uint8_t* __restrict__ mp_obs, uint8_t* __restrict__ qdesc) {
+    const int r = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= min(max(counts[first + r], 0), cap)) return;
+    const size_t o = (size_t)r * cap + i;
+    if (!create_new[o]) return;
+    x3dw[o * 3] = x3d_new[o * 3]; x3dw[o * 3 + 1] = x3d_new[o * 3 + 1]; x3dw[o * 3 + 2] = x3d_new[o * 3 + 2];
+    has_mp[o] = outlier ? (outlier[o] ? 0 : 1) : 1;
+    mp_obs[o] = 0;
+    const uint32_t* s = (const uint32_t*)(desc + ((size_t)(first + r) * cap + i) * 32);
+    uint32_t* d = (uint32_t*)(qdesc + o * 32);
+    for (int w = 0; w < 8; ++w) d[w] = s[w];
+}
+
+// ------------------------------------------------------------------------------------------------
 // MapPoint refresh: the producer of the qdesc / normal / min_dist / max_dist rows the batched searches read.
 // k_mp_distinctive: MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:450-538); k_mp_normal_depth: MapPoint::UpdateNormalAndDepth
 // (MapPoint.cc:578-652).  Both walk a CSR of observation entries (KeyFrame pool row, slot, flags) over the MapPoints of the call.

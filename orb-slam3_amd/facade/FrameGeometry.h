@@ -5,6 +5,7 @@
 //   cvtColor(..., COLOR_*2GRAY) (src/Tracking.cc:1264-1290) -> see orbx_gray_from_color in include/orbx.h
 //   Frame::ComputeStereoFromRGBD (src/Frame.cc:1279-1309) + the depth conversion of GrabImageRGBD (src/Tracking.cc:1353-1354) -> ComputeStereoFromRGBD()
 //   Frame::UnprojectStereo for every keypoint (src/Frame.cc:1312-1326) -> UnprojectStereoAll()
+//   the sorted walk over the depth points in Tracking::UpdateLastFrame / CreateNewKeyFrame (src/Tracking.cc:3094-3163, :3694-3783) -> SelectDepthPoints()
 // The bodies only flatten the reference's containers into plain arrays; all arithmetic runs in liborbslam3_amd.so.
 #pragma once
 #include <cstdint>
@@ -94,6 +95,32 @@ inline int UnprojectStereoAll(orbm_t* m, const std::vector<cv::KeyPoint>& keysUn
     const float twc[12] = {Rwc[0], Rwc[1], Rwc[2], Ow[0], Rwc[3], Rwc[4], Rwc[5], Ow[1], Rwc[6], Rwc[7], Rwc[8], Ow[2]};
     const int rc = orbm_unproject_stereo(m, (int)keysUn.size(), (const orbm_kp_t*)keysUn.data(), vDepth.data(), twc, K, x3Dw.data(), hasDepth.data());
     if (rc < 0) throw std::runtime_error(std::string("orbm_unproject_stereo: ") + orbm_last_error());
+    return rc;
+}
+
+// The walk `sort(vDepthIdx); for (j ...) { ...; if (vDepthIdx[j].first > mThDepth && nPoints > 100) break; }` of Tracking::UpdateLastFrame
+// (Tracking.cc:3094-3163) and Tracking::CreateNewKeyFrame (:3694-3783) in one call.  keepsMp[i] = `pMP && pMP->Observations() >= 1` for
+// mvpMapPoints[i] (empty = no slot holds one); maxPoints = the reference's 100.  order = the visited slots, closest first, equal depths by
+// slot; createNew[i] = 1 where the walk creates a MapPoint.  Returns the number of visited slots (order.size()).
+// Recipe, both functions:
+//     UnprojectStereoAll(m, mvKeysUn, mvDepth, Rwc, Ow, K, x3Dw, hasDepth);
+//     SelectDepthPoints(m, mvDepth, keepsMp, mThDepth, 100, order, createNew);
+//     for (int i : order) if (createNew[i]) { x3D = x3Dw[3 * i .. 3 * i + 2]; ... }
+//   UpdateLastFrame:   pNewMP = new MapPoint(x3D, pMap, &mLastFrame, i); mLastFrame.mvpMapPoints[i] = pNewMP; mlpTemporalPoints.push_back(pNewMP);
+//   CreateNewKeyFrame: pNewMP = new MapPoint(x3D, pKF, pMap) and the map surgery of :3750-3767 (AddObservation, AddMapPoint,
+//                      ComputeDistinctiveDescriptors, UpdateNormalAndDepth, the Atlas); a slot whose MapPoint has no observation is cleared
+//                      first (:3735).  With Nleft != -1 the UnprojectStereoFishEye point and the mvLeftToRightMatch partner stay with the caller.
+// Creating in `order` keeps the MapPoint ids in the reference's sequence.
+inline int SelectDepthPoints(orbm_t* m, const std::vector<float>& vDepth, const std::vector<uint8_t>& keepsMp, float thDepth, int maxPoints,
+                             std::vector<int>& order, std::vector<uint8_t>& createNew) {
+    if (!keepsMp.empty() && keepsMp.size() != vDepth.size()) throw std::runtime_error("SelectDepthPoints: mvDepth and keepsMp differ in size");
+    order.assign(vDepth.size(), -1); createNew.assign(vDepth.size(), 0);
+    if (vDepth.empty()) return 0;
+    static_assert(sizeof(int) == sizeof(int32_t), "int is 32 bits");
+    const int rc = orbm_select_depth_points(m, (int)vDepth.size(), vDepth.data(), keepsMp.empty() ? nullptr : keepsMp.data(), nullptr, thDepth, maxPoints,
+                                            (int32_t*)order.data(), createNew.data(), nullptr, nullptr, nullptr);
+    if (rc < 0) throw std::runtime_error(std::string("orbm_select_depth_points: ") + orbm_last_error());
+    order.resize(rc);
     return rc;
 }
 
