@@ -106,6 +106,9 @@ int orbx_last_timings(orbx_t*, float* ms8);
  * chain, beside FAST): ms8[7] then ends with the later of FAST and blur, and the pass's algorithmic traffic includes the
  * blur's read + write of every level (2 * sum of level pixels).  0 with ORBX_BLUR_V2 / ORBX_BLUR_LATE. */
 int orbx_blur_in_pass(const orbx_t*);
+/* workgroup size the quadtree of the most recent batch was enqueued with: 1024 or 256 (k_quadtree2 takes the wide form when some
+ * level wants >= 512 nodes or frames * levels <= 512), 0 for the first-generation kernel of the A/B library, -1 before any batch. */
+int orbx_quadtree_threads(const orbx_t*);
 /* stage-boundary events are optional: with `on` = 0 only the dependency events are recorded (a few microseconds less per
  * batch); orbx_last_timings / orbx_mean_timings then fill ms8[6] (total), ms8[7] (the pass: to the later of FAST and an in-pass blur)
  * and ms8[1] (first launch -> end of the last FAST launch, i.e. pyramid+FAST without the blur's tail) and zero the rest.

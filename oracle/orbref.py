@@ -74,6 +74,7 @@ class Extractor:
         self.h = self.L.orbref_create(nfeatures, scale_factor, nlevels, ini_th, min_th)
         assert self.h
         self.nfeatures, self.nlevels = nfeatures, nlevels
+        self._caps = {}
 
     def __del__(self):
         try:
@@ -88,10 +89,24 @@ class Extractor:
         self.L.orbref_tables(self.h, _p(sf), _p(isf), _p(s2), _p(is2), _p(nf), _p(um))
         return dict(sf=sf, inv_sf=isf, sig2=s2, inv_sig2=is2, nfeat=nf, umax=um)
 
+    def max_keypoints(self, w, h):
+        """Upper bound of what a w x h frame returns: DistributeOctTree ends with at most max(N + 3, 4 * nIni) nodes per level (the
+        first pass splits every root before it looks at N), nIni = round(width / height) of the level's inner area."""
+        if (w, h) in self._caps:
+            return self._caps[(w, h)]
+        t = self.tables()
+        cap = 0
+        for l in range(self.nlevels):
+            wl = int(np.rint(np.float32(w) * t["inv_sf"][l])) - 32; hl = int(np.rint(np.float32(h) * t["inv_sf"][l])) - 32
+            n_ini = wl // max(hl, 1) + 1                        # >= round(wl / hl)
+            cap += max(int(t["nfeat"][l]) + 3, 4 * n_ini)
+        self._caps[(w, h)] = cap
+        return cap
+
     def __call__(self, img, lap=(0, 0)):
         img = np.ascontiguousarray(img, np.uint8)
         h, w = img.shape
-        cap = self.nfeatures + 4 * self.nlevels + 64
+        cap = self.max_keypoints(w, h)
         kps = np.zeros(cap, KP_DTYPE); desc = np.zeros((cap, 32), np.uint8)
         mono = C.c_int32(0)
         n = self.L.orbref_extract(self.h, _p(img), w, h, w, int(lap[0]), int(lap[1]), _p(kps), _p(desc), cap, C.byref(mono))
@@ -160,8 +175,10 @@ def gauss7(src):
 
 def distribute(xyr, minX, maxX, minY, maxY, N):
     xyr = np.ascontiguousarray(xyr, np.int32); n = xyr.shape[0]
-    out = np.zeros(max(N + 16, 16), np.int32)
+    n_ini = (maxX - minX) // max(maxY - minY, 1) + 1            # >= round(width / height)
+    out = np.zeros(max(N + 3, 4 * n_ini, 1), np.int32)          # the first pass splits every root before it looks at N
     m = lib().orbref_distribute(_p(xyr), n, minX, maxX, minY, maxY, N, _p(out), out.shape[0])
+    assert m <= out.shape[0], (m, out.shape[0])
     return out[:m]
 
 

@@ -92,6 +92,7 @@ struct orbx {
     bool blurTiled = true;                                     // k_blur3 writes / k_orient_desc2 reads the blurred levels as 16 x 8-px tiles (ORBX_BLUR_ROWMAJOR: A/B)
     bool qtWide = false;                                       // 1024-thread quadtree workgroups (large frames / feature counts)
     int qtWideForce = -1;                                      // ORBX_QT_WIDE=0/1: A/B switch
+    int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
     // device
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;
@@ -410,12 +411,16 @@ static int build_geometry(orbx* o, int w, int h) {
     g.totalSlots = totalSlots;
     g.totalSel = totalSel;
     g.kpCap = totalSel;
+    // maxN = max over the levels of max(N, 4 * nIni) (above): the first pass of DistributeOctTree splits every root before it looks at
+    // N, so a level ends with up to 4 * nIni nodes whatever its budget.  k_quadtree (the A/B kernel) keeps the parents of a pass until
+    // its end: at most nIni + 4 * nIni nodes in the first pass and N + (N + 3) later, both within 2 * maxN + 64 for every nIni
     g.nodeCap = 2 * maxN + 64;
     int sc = 1; while (sc < maxN + 8) sc <<= 1;
     g.sortCap = sc;
     if (g.nodeCap > 65000) { set_err("nfeatures per level %d too large for 16-bit node ids", maxN); return ORBX_E_UNSUPPORTED; }
     o->qtLds = (size_t)g.sortCap * 8 + (size_t)g.nodeCap * 56 + 64;
-    {   // k_quadtree2: list capacity max(N+3, 4*nIni) (+slack), power-of-two sort buffer
+    {   // k_quadtree2: list capacity max(N+3, 4*nIni) (+slack), power-of-two sort buffer.  The 4 * nIni term is inside maxN, so a
+        // wide frame with a small budget (six roots, N = 11: 24 nodes after the first pass) fits: tests/test_gpu_extract_second_reading.py
         o->qt2Cap = maxN + 8;
         int sc2 = 1; while (sc2 < o->qt2Cap) sc2 <<= 1;
         o->qt2Sort = sc2;
@@ -983,6 +988,7 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
                            o->dTiles3 + first, (const uint4*)o->dB3Th, (const uint4*)o->dB3Tv);
     }
     HIPCHK(rec_ev(o, 9, s1, true));                              // blur ready
+    if (o->qtV1) o->qtThreadsLast = 0;
     if (o->qtV1)
         AB_LAUNCH(k_quadtree, dim3(nimg, g.nlevels), dim3(256), o->qtLds, st, g, o->dCells, o->dCandCnt, o->dCandEnt,
                   o->dKpNode, o->dSel, o->dSelCnt, o->dErr);
@@ -992,6 +998,7 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
         // a level's candidates four times faster than 256 (one frame: 0.276 -> 0.237 ms end to end); many workgroups: 256 threads
         // (shorter barriers, more workgroups per CU: 0.24 vs 0.56 ms per 512 frames)
         const bool wide = o->qtWideForce >= 0 ? o->qtWide : (o->qtWide || nimg * g.nlevels <= 512);
+        o->qtThreadsLast = wide ? 1024 : 256;
         if (wide)
             hipLaunchKernelGGL(k_quadtree2<1024>, dim3(nimg, g.nlevels), dim3(1024), o->qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
                                o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->maxCells, o->maxIni, o->qtFuseD);
@@ -1635,6 +1642,7 @@ int orbx_mean_timings(orbx_t* o, float* ms8, int* nsamples) {
 }
 
 int orbx_blur_in_pass(const orbx_t* o) { return o && o->blurEarly && !o->serial ? 1 : 0; }
+int orbx_quadtree_threads(const orbx_t* o) { return o ? o->qtThreadsLast : -1; }
 
 int orbx_set_stage_timing(orbx_t* o, int on) {
     if (!o) return ORBX_E_INVALID;

@@ -32,10 +32,28 @@ def test_ab_reference_kernels_stay_bit_exact(pkg, oracle, synth, monkeypatch):
             monkeypatch.setenv(e, "1")
         ex = pkg.ORBextractor(1000, max_size=(752, 480))
         mono, kps, desc = ex(img, (0, 1000))
+        assert ex.quadtree_threads() == (0 if "ORBX_QT_V1" in env else 1024)       # (one frame: the wide form also without ORBX_QT_WIDE)
         ex.close()
         for e in env:
             monkeypatch.delenv(e)
         assert mono == mono_ref and kps.tobytes() == kps_ref.tobytes() and np.array_equal(desc, desc_ref), env
+
+
+@pytest.mark.parametrize("env", [("ORBX_QT_V1", "1"), ("ORBX_QT_WIDE", "1"), ("ORBX_QT_WIDE", "0")], ids=lambda e: "%s=%s" % e)
+def test_quadtree_variants_equal_the_second_reading(pkg, monkeypatch, env):
+    """The first-generation quadtree (k_quadtree: lane 0 replays the list surgery on a linked list) and both workgroup widths of
+    k_quadtree2, forced, on the hand-laid frames of tests/extract_cases.py: held to the second reading, not to the oracle."""
+    from test_gpu_extract_second_reading import GROUPS, check_frame, make_extractor
+    for k, group in GROUPS.items():
+        monkeypatch.setenv(*env)
+        ex = make_extractor(pkg, k)
+        monkeypatch.delenv(env[0])
+        try:
+            for c in group:
+                check_frame(ex, c, ex(c["img"], c["lap"]))
+                assert ex.quadtree_threads() == {("ORBX_QT_V1", "1"): 0, ("ORBX_QT_WIDE", "1"): 1024, ("ORBX_QT_WIDE", "0"): 256}[env]      # the switch was read
+        finally:
+            ex.close()
 
 
 @pytest.mark.parametrize("qcap", [64, 128, 256])

@@ -79,6 +79,17 @@ def test_small_budgets(pkg, oracle, synth, nf):
     ex.close()
 
 
+@pytest.mark.parametrize("w,h,nf,nl,per_level0", [(1241, 376, 20, 8, 16), (1241, 376, 4, 1, 16), (2400, 420, 50, 8, 24), (2400, 420, 11, 1, 24)])
+def test_small_budgets_on_wide_frames(pkg, oracle, synth, w, h, nf, nl, per_level0):
+    """Four and six quadtree roots with a budget below 4 * nIni: every level returns 4 * nIni keypoints, 16 / 24 on level 0."""
+    n = _check(pkg, oracle, synth, w, h, nf, 30 + nf, (0, 0), "textured", nlevels=nl)
+    ex = pkg.ORBextractor(nf, nlevels=nl, max_size=(w, h), max_batch=1)
+    assert n <= ex.cap and (ex.features_per_level() < per_level0 - 3).all()
+    mono, kps, _ = ex(synth.gen_image(w, h, 30 + nf, "textured"), (0, 0))
+    assert np.count_nonzero(kps["octave"] == 0) == per_level0 and len(kps) >= nl * per_level0       # (the upper levels of 2400 x 420 have 7 and 8 roots)
+    ex.close()
+
+
 @pytest.mark.parametrize("w,h,sf,nl", [(239, 239, 1.2, 8), (337, 337, 1.5, 5)])
 def test_one_pixel_below_the_smallest_size(pkg, oracle, synth, w, h, sf, nl):
     """One pixel less in either direction: the oracle returns -3, the product raises OrbError (ORBX_E_TOO_SMALL)."""
