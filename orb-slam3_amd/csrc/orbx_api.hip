@@ -71,6 +71,7 @@ struct orbx {
     CellAux* dAux = nullptr; size_t capAux = 0;
     F4Item* dF4Items = nullptr; size_t capF4Items = 0;
     bool fastV3 = false;                                      // ORBX_FAST_V3: A/B, k_fast3 instead of k_fast4
+    bool fastV4p = false;                                     // ORBX_FAST_V4P: A/B, k_fast4p (register-staged tile, separate store pass) instead of k_fast4
     bool fastV1 = false;
     // k_fast3 launch groups: level 0 (needs no resize), the fine levels, the coarse levels.  Each group sizes its own LDS
     // (tile of its tallest cell row + survivor queues), because occupancy -- 20 vs 28 waves per CU -- is worth ~15 %.
@@ -519,7 +520,8 @@ static int build_geometry(orbx* o, int w, int h) {
             }
             // one compile-time tile pitch for the whole group when its strips allow it (35..40-px cells, 4 per strip: <= 208 bytes)
             G.pitch = o->f3NoFixedPitch ? 0 : maxLp <= 176 ? 176 : maxLp <= 208 ? 208 : 0;
-            if (G.pitch) G.tile = G.pitch * maxH;
+            // (>= 1 KiB: k_fast4 writes a fixed-pitch tile in wave-instructions of 64 x 16 bytes, a shorter strip as one of them)
+            if (G.pitch) G.tile = std::max(G.pitch * maxH, 1024);
             G.tile = align_up(G.tile, 16);
             G.lastLevel = o->strips[G.strip0 + G.nstrips - 1].level;
             G.qcap = qworst;
@@ -583,7 +585,7 @@ static int build_geometry(orbx* o, int w, int h) {
                 }
             }
         }
-        if (o->f4items.empty()) o->f4items.push_back(F4Item{0, 0});
+        if (o->f4items.size() < 64) o->f4items.resize(64, F4Item{0, 0});    // (k_fast4's waves without a cell read one iteration of table 0)
         if (ensure(&o->dAux, &o->capAux, o->aux.size())) return ORBX_E_HIP;
         if (ensure(&o->dF4Items, &o->capF4Items, o->f4items.size())) return ORBX_E_HIP;
         HIPCHK(hipMemcpy(o->dAux, o->aux.data(), o->aux.size() * sizeof(CellAux), hipMemcpyHostToDevice));
@@ -592,6 +594,9 @@ static int build_geometry(orbx* o, int w, int h) {
         HIPCHK(hipFuncSetAttribute((const void*)k_fast4<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
         HIPCHK(hipFuncSetAttribute((const void*)k_fast4<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
 #ifdef ORBX_AB
+        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
+        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
+        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
         HIPCHK(hipFuncSetAttribute((const void*)k_fast3<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
         HIPCHK(hipFuncSetAttribute((const void*)k_fast3<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
         HIPCHK(hipFuncSetAttribute((const void*)k_fast3<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
@@ -726,6 +731,7 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     if (const char* e = ab_env("ORBX_FAST_QCAP")) o->f3QcapForce = atoi(e);
     o->f3NoFixedPitch = ab_env("ORBX_FAST_PITCH0") != nullptr;
     o->fastV3 = ab_env("ORBX_FAST_V3") != nullptr;
+    o->fastV4p = ab_env("ORBX_FAST_V4P") != nullptr;
     if (const char* e = ab_env("ORBX_QT_WIDE")) o->qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
     o->blurTiled = !o->blurV2 && !o->odV1 && ab_env("ORBX_BLUR_ROWMAJOR") == nullptr;
@@ -947,6 +953,13 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
                 if (first) STAGE_EV(1, st);
                 first = false;
             }
+#ifdef ORBX_AB
+            if (G.v4 && o->fastV4p) {
+                auto kern = G.pitch == 176 ? k_fast4p<176> : G.pitch == 208 ? k_fast4p<208> : k_fast4p<0>;
+                hipLaunchKernelGGL(kern, dim3((unsigned)G.nstrips, nimg), dim3(F3_NT), G.lds, st, g, o->dL0Ptr, l0pitch, o->dPyr,
+                                   o->dAux, o->dF4Items, o->dStrips + G.strip0, o->dCandCnt, o->dCandEnt, o->dErr, G.tile, G.qcap, o->dOvf, o->dOvfList);
+            } else
+#endif
             if (G.v4) {
                 auto kern = G.pitch == 176 ? k_fast4<176> : G.pitch == 208 ? k_fast4<208> : k_fast4<0>;
                 hipLaunchKernelGGL(kern, dim3((unsigned)G.nstrips, nimg), dim3(F3_NT), G.lds, st, g, o->dL0Ptr, l0pitch, o->dPyr,

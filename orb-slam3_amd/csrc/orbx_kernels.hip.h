@@ -814,8 +814,9 @@ struct F4Ctx {                                              // wave-uniform cont
 };
 
 // quick reject at threshold t: survivors appended to the wave's queue in row-major order; returns their number, -1 if the queue overflowed
-template <int PITCH>
-__device__ __forceinline__ int f4_quick(const F4Ctx& cx, const CellAux& ax, const F4Item* __restrict__ items, const int t) {
+// PRE: the caller has already loaded the first item (`first`, landed); otherwise it is fetched here
+template <int PITCH, bool PRE = false>
+__device__ __forceinline__ int f4_quick(const F4Ctx& cx, const CellAux& ax, const F4Item* __restrict__ items, const int t, const uint2 first = uint2{0, 0}) {
     const int Pb = PITCH > 0 ? PITCH : cx.Pb, qcap = cx.qcap;
     const u32 qA = cx.qA;
     const u32 laneOff = (u32)cx.lane * 8u;
@@ -831,7 +832,8 @@ __device__ __forceinline__ int f4_quick(const F4Ctx& cx, const CellAux& ax, cons
     // iteration runs; the statement at the bottom waits and only then reads them (its inputs ARE the load's registers:
     // no tied operand, so no copy can be placed in front of the wait -- checked in the ISA).
     uint2 cur;                                                 // .x = mask, .y = offq of the current item
-    asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2\n\ts_waitcnt vmcnt(0)" : "=&v"(cur) : "v"(laneOff), "s"(tab) : "memory");
+    if constexpr (PRE) cur = first;
+    else asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2\n\ts_waitcnt vmcnt(0)" : "=&v"(cur) : "v"(laneOff), "s"(tab) : "memory");
     for (int it = 0; it < nit; ++it) {
         uint2 nxt;
         {
@@ -919,10 +921,10 @@ __device__ __forceinline__ int f4_quick(const F4Ctx& cx, const CellAux& ax, cons
     return n1;
 }
 
-// exact score of the n1 queued survivors at threshold t, then strict 3x3 maxima inside the cell window; both compact the queue in place.
-// Returns the number of keypoints left in the queue.
+// exact score of the n1 queued survivors at threshold t: scores >= t go to the score tile, their entries stay (compacted in place, in
+// order).  Returns their number.
 template <int PITCH>
-__device__ __forceinline__ int f4_score_nms(const F4Ctx& cx, const CellAux& ax, const int t, const int n1) {
+__device__ __forceinline__ int f4_score(const F4Ctx& cx, const int t, const int n1) {
     const int Pb = PITCH > 0 ? PITCH : cx.Pb, lane = cx.lane;
     const u32 qA = cx.qA, scD = cx.scD, cbase = cx.cbase;
 #if defined(F4_ABL_NOSCORE) || defined(F4_ABL_NOAPPEND)
@@ -950,6 +952,209 @@ __device__ __forceinline__ int f4_score_nms(const F4Ctx& cx, const CellAux& ax, 
         if (fB) lds_w16(qA + 2u * (u32)(n2 + nA + f4_below(balB)), eb);
         n2 += nA + __popcll(balB);
     }
+    return n2;
+}
+
+// strict 3x3 maxima inside the cell window among the n2 scored entries of the queue, stored as they are found: the queue is row-major
+// by construction (the quick reject appends iteration by iteration -- items in (row, column) order --, lanes in item order through the
+// wave prefix, pixels of a lane in ascending x; the score pass compacts it stably) and cv::FAST emits in the same order, so the k-th
+// maximum is candidate k of the cell.  The entry, its column, row and score are in registers here: no second pass over the queue.
+// Returns the number of keypoints.
+template <int PITCH>
+__device__ __forceinline__ int f4_nms_store(const F4Ctx& cx, const CellAux& ax, const int n2, const int slotCap, u32* __restrict__ out, int* err) {
+    const int Pb = PITCH > 0 ? PITCH : cx.Pb, lane = cx.lane;
+    const u32 qA = cx.qA, scD = cx.scD, cbase = cx.cbase;
+#ifdef F4_ABL_NONMS
+    if (n2 < 60000) return 0;
+#endif
+    int n3 = 0;
+    const u32 sbase = cbase + scD - (u32)(Pb + 1);               // (row 0, xs 0) -> its upper-left neighbour in the score tile
+    for (int e0 = 0; e0 < n2; e0 += 64) {
+        const int e = e0 + lane;
+        bool keep = false;
+        u32 kp = 0;
+        if (e < n2) {
+            const u32 pq = lds_r16(qA + 2u * (u32)e);
+            const u32 xs = __builtin_amdgcn_ubfe(pq, 2, 7), row = pq >> 9;
+            const u32 o = row * (u32)Pb + xs + sbase;
+            // branch-free: all eight neighbours are read (the tile has a halo; a neighbour column outside the cell's
+            // window may hold another cell's score, possibly mid-write -- it is masked to 0, never used)
+            const int s = (int)lds_r8(o + Pb + 1);
+            const int ml = max(max((int)lds_r8(o + Pb), (int)lds_r8(o)), (int)lds_r8(o + 2 * Pb));
+            const int mr = max(max((int)lds_r8(o + Pb + 2), (int)lds_r8(o + 2)), (int)lds_r8(o + 2 * Pb + 2));
+            const int mv = max((int)lds_r8(o + 1), (int)lds_r8(o + 2 * Pb + 1));
+            keep = s > max(mv, max(xs > (u32)ax.xlo ? ml : 0, xs < (u32)ax.xhi ? mr : 0));
+            kp = (u32)((int)ax.outx + (int)xs) | ((u32)((int)ax.outy + (int)row) << 12) | ((u32)s << 24);
+        }
+        const unsigned long long bal = __ballot(keep);
+        if (keep) {
+            const int k = n3 + f4_below(bal);
+            if (k < slotCap) out[k] = kp;
+            else atomicExch(err, 1);
+        }
+        n3 += __popcll(bal);
+    }
+    return n3;
+}
+
+// cv::FAST at iniTh and, only if that leaves the cell empty after non-max suppression, at minTh (ORBextractor.cc:1112-1125);
+// `n1` = result of the first quick pass (already run by the caller).  Nothing is stored before a pass finds a maximum, so the retry
+// (which runs only after a pass that found none) and an overflowing cell (handed to k_fast_fix) start from untouched slots.
+template <int PITCH>
+__device__ __forceinline__ void f4_finish(const int iniTh, const int minTh, const int totalCells, const int totalSlots, const F4Ctx& cx, const CellAux& ax,
+                                          const F4Item* __restrict__ items, int n1, const int slotCap,
+                                          const int frame, const int cellIdx, u32* candCnt, u32* candEnt, int* err, u32* ovf, u32* ovfList) {
+    u32* out = candEnt + (size_t)frame * totalSlots + ax.slot;
+    int n3 = 0;
+    if (n1 > 0) n3 = f4_nms_store<PITCH>(cx, ax, f4_score<PITCH>(cx, iniTh, n1), slotCap, out, err);
+#if !defined(F4_ABL_NOSCORE) && !defined(F4_ABL_NOAPPEND) && !defined(F4_ABL_NONMS)
+    if (n1 >= 0 && n3 == 0 && ax.nit > 0 && minTh < iniTh) {           // (a higher retry threshold cannot add corners)
+        n1 = f4_quick<PITCH>(cx, ax, items, minTh);
+        if (n1 > 0) n3 = f4_nms_store<PITCH>(cx, ax, f4_score<PITCH>(cx, minTh, n1), slotCap, out, err);
+    }
+#endif
+    if (n1 < 0) {
+        if (cx.lane == 0) ovfList[atomicAdd(&ovf[0], 1u)] = (u32)frame * (u32)totalCells + (u32)cellIdx;
+        return;
+    }
+    if (cx.lane == 0) candCnt[(size_t)frame * totalCells + ax.cnt] = (u32)n3;
+}
+
+// One strip by one workgroup: tile into LDS, then a wave per cell (a strip has at most F3_NT / 64 cells).
+//   * fixed-pitch groups (PITCH = 176 / 208) stage the tile with direct global -> LDS loads.  Such a load puts lane i's 16 bytes at
+//     (wave-uniform base) + 16 i, and a pitch that is a multiple of 16 makes the row-major tile a linear list of 16-byte chunks
+//     (chunk c = row c / cpr, column c % cpr, cpr = PITCH / 16): wave-instruction k fetches chunks 64 k .. 64 k + 63, each lane from
+//     its own clamped source address.  The LAST instruction of a tile starts at chunk (count - 64) instead: it re-fetches a few chunks
+//     of its predecessor (same bytes, so the double write is harmless) and ends exactly at the tile's end -- no lane is predicated and
+//     nothing lands outside the strip's rows.  The score tile is zeroed the same way, 1 KiB per wave-instruction from one zero vector.
+//     (A strip of fewer than 64 chunks is written as 64 from the tile's start: the host keeps a fixed-pitch tile >= 1 KiB.)
+//   * what the cell loop needs and the tile does not produce is asked for BEFORE the barrier, in three rounds of scalar loads with one
+//     wait each: the kernel arguments; the strip record and level 0's frame pointer; the level record and the wave's CellAux.  The
+//     cell's first F4Item follows the tile's loads and lands with them.  Left alone, the compiler sinks each of these loads to its
+//     first use (behind the barrier, or behind a branch on the level) and waits there; the empty asm statements below only name the
+//     values, so that they have to be in registers at that point.
+template <int PITCH>
+__global__ __launch_bounds__(F3_NT) void k_fast4(Geom g, const u8* const* l0, int l0pitch, const u8* pyr,
+                                                 const CellAux* __restrict__ aux, const F4Item* items,
+                                                 const StripInfo* __restrict__ strips,
+                                                 u32* candCnt, u32* candEnt, int* err, int tileBytes, int qcap,
+                                                 u32* ovf, u32* ovfList) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char f3smem[];
+    const u32 imgA = (u32)(uintptr_t)(lds_u8_t*)f3smem;                  // LDS address of the image tile (wave-uniform)
+    const u32 scD = (u32)tileBytes;                                       // score tile behind the image tile, same indexing
+    const int frame = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    int iniTh = g.iniTh, minTh = g.minTh, totalCells = g.totalCells, totalSlots = g.totalSlots;
+    size_t pyrFrameBytes = g.pyrFrameBytes;
+    // (pointers go through as integers and come back as GLOBAL pointers: a generic one would be dereferenced with flat instructions)
+    uintptr_t pyrI = (uintptr_t)pyr, cntI = (uintptr_t)candCnt, entI = (uintptr_t)candEnt, errI = (uintptr_t)err, ovfI = (uintptr_t)ovf,
+              ovlI = (uintptr_t)ovfList, itemsI = (uintptr_t)items, l0I = (uintptr_t)l0;
+    u32 nstrips = gridDim.x;
+    asm volatile("" : "+s"(iniTh), "+s"(minTh), "+s"(totalCells), "+s"(totalSlots), "+s"(pyrFrameBytes), "+s"(l0pitch), "+s"(qcap), "+s"(pyrI),
+                 "+s"(cntI), "+s"(entI), "+s"(errI), "+s"(ovfI), "+s"(ovlI), "+s"(itemsI), "+s"(l0I), "+s"(nstrips));
+#define F4_GPTR(T, v) ((T*)(__attribute__((address_space(1))) T*)(v))
+    pyr = F4_GPTR(const u8, pyrI); candCnt = F4_GPTR(u32, cntI); candEnt = F4_GPTR(u32, entI); err = F4_GPTR(int, errI);
+    ovf = F4_GPTR(u32, ovfI); ovfList = F4_GPTR(u32, ovlI); items = F4_GPTR(const F4Item, itemsI);
+    // the strip record as five aligned words (its 16-bit fields make the compiler fetch some of them through the vector cache)
+    const u32* sw = (const u32*)(strips + (nstrips - 1 - (F3_XCD ? xcd_task(blockIdx.x, nstrips) : blockIdx.x)));   // coarser (denser, slower) strips of the group first: a lighter tail
+    u32 sw0 = sw[0], sw1 = sw[1], sw2 = sw[2], sw3 = sw[3], sw4 = sw[4];
+    // level 0's frame pointer (used only there), read through the constant address space: the table is not written while FAST runs, and
+    // a pointer that has been through the asm statement is not known to be read-only any more, which a scalar load needs
+    uintptr_t l0f = ((const __attribute__((address_space(4))) uintptr_t*)l0I)[frame];
+    asm volatile("" : "+s"(sw0), "+s"(sw1), "+s"(sw2), "+s"(sw3), "+s"(sw4), "+s"(l0f));
+#undef F4_GPTR
+    StripInfo st;
+    st.level = (short)sw0; st.ncell = (short)(sw0 >> 16); st.y0 = (short)(sw1 >> 16); st.h = (short)(sw2 >> 16);
+    st.xal = (short)sw3; st.lp = (short)(sw3 >> 16); st.cell0 = (int)sw4;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);              // wave-uniform: per-cell metadata comes through the scalar cache
+    const u32 qA = imgA + 2u * (u32)tileBytes + (u32)(wv * qcap) * 2u;    // this wave's queue (u16 entries)
+    const int Pb = PITCH > 0 ? PITCH : (int)st.lp, H = st.h;              // tile pitch in bytes
+    const bool hasCell = wv < st.ncell;                                   // (ncell >= 1; an idle wave reads the last cell's record, not past the table)
+    const int cellIdx = st.cell0 + min(wv, st.ncell - 1);
+    CellAux ax = aux[cellIdx];
+    const LevelDesc& L = g.lv[st.level];
+    int Lw = L.w, Lpitch = L.pitch, Loff = L.off, slotCap = L.slotCap;
+    asm volatile("" : "+s"(Lw), "+s"(Lpitch), "+s"(Loff), "+s"(slotCap), "+s"(ax.tab), "+s"(ax.slot), "+s"(ax.cnt));
+    const int sp = st.level == 0 ? l0pitch : Lpitch;
+    const u8* src = st.level == 0 ? (const u8*)l0f : pyr + (size_t)frame * pyrFrameBytes + Loff;
+    // Rows and columns are CLAMPED into the level instead of predicated: a column at or right of the image's 16-byte-rounded width is
+    // only ever read by lanes whose pixels are masked out (valid pixels end 13 columns left of the image edge)
+    const int rowLimit = min((Lw + 15) & ~15, sp);
+    if constexpr (PITCH > 0) {
+        constexpr int cpr = PITCH / 16;
+        constexpr u32 RCP = (65536 + cpr - 1) / cpr;                     // c / cpr = c * RCP >> 16, exact for c < 6553 (cpr = 11, 13; a tile has <= 127 * 13 chunks)
+        static_assert(PITCH % 16 == 0 && (RCP * cpr - 65536) * 6553 < 65536, "chunk -> (row, column) by multiply-shift");
+        const int nchunk = H * cpr;
+        for (int k = wv * 64; k < nchunk; k += F3_NT) {
+            const int b = max(min(k, nchunk - 64), 0);                    // wave-uniform
+            const u32 c = (u32)(b + lane);
+            const u32 r = mad24(c, RCP, 0u) >> 16, col = c - r * (u32)cpr;
+            const int gx = min(st.xal + (int)col * 16, rowLimit - 16);
+            const u8* p = src + mad24((u32)(st.y0 + min((int)r, H - 1)), (u32)sp, (u32)gx);
+#ifndef F4_ABL_NOLOAD
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)p, (lds_u8_t*)(uintptr_t)(imgA + (u32)b * 16u), 16, 0, 0);
+#endif
+        }
+    }
+    // the cell's first item, behind the tile's loads and before the barrier.  f4_quick's rule for such a load: the statement that waits
+    // for it reads the load's own registers (no tied operand, no branch in between, so no copy can be placed in front of the wait); a
+    // wave without a cell or with an empty window reads table 0 (the host keeps >= 64 items) and ignores it
+    uint2 item0raw, item0;
+    asm volatile("s_nop 4\n\tglobal_load_dwordx2 %0, %1, %2" : "=&v"(item0raw) : "v"((u32)lane * 8u), "s"(items + (hasCell && ax.nit > 0 ? ax.tab : 0u)) : "memory");
+    if constexpr (PITCH > 0) {
+        const int nz = H * PITCH;
+        const uint4 zero = make_uint4(0, 0, 0, 0);
+        const u32 za = imgA + scD + (u32)lane * 16u;
+        for (int k = wv * 1024; k < nz; k += F3_NT * 16) lds_w128(za + (u32)max(min(k, nz - 1024), 0), zero);
+    } else {
+        // per-strip pitch: 32 lanes x 16 B per row, 8 rows per pass through registers; six passes in flight (one memory round trip)
+        const int cpr = Pb >> 4;
+        const int ck = tid & 31;
+        const int gx = min(st.xal + ck * 16, rowLimit - 16);
+        const bool colOk = ck < cpr;
+        const int RP = F3_NT / 32;
+        const int r0 = tid >> 5;
+        uint4 v[6];
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            const int r = min(r0 + p * RP, H - 1);
+            v[p] = gload128u(src, mad24((u32)(st.y0 + r), (u32)sp, (u32)gx));   // (written as __mul24 + add the compiler picks the 64-bit multiply-add)
+        }
+        const u32 lo = imgA + (u32)(r0 * Pb + ck * 16);
+#pragma unroll
+        for (int p = 0; p < 6; ++p) {
+            const int r = r0 + p * RP;
+            if (colOk && r < H) {
+                lds_w128(lo + (u32)(p * RP) * (u32)Pb, v[p]);
+                lds_w128(lo + scD + (u32)(p * RP) * (u32)Pb, make_uint4(0, 0, 0, 0));
+            }
+        }
+        for (int r = r0 + 6 * RP; r < H; r += RP) {                       // taller cells (coarse levels, tiny images)
+            if (colOk) {
+                const uint4 t = gload128u(src, (u32)(__mul24(st.y0 + r, sp) + gx));
+                lds_w128(imgA + (u32)(r * Pb + ck * 16), t);
+                lds_w128(imgA + scD + (u32)(r * Pb + ck * 16), make_uint4(0, 0, 0, 0));
+            }
+        }
+    }
+    __syncthreads();                                                      // (drains the direct loads: vmcnt(0) in front of the barrier)
+    asm volatile("s_waitcnt vmcnt(0)\n\tv_mov_b32 %0, %2\n\tv_mov_b32 %1, %3" : "=&v"(item0.x), "=&v"(item0.y) : "v"(item0raw.x), "v"(item0raw.y) : "memory");
+    if (hasCell) {
+        F4Ctx cx; cx.imgA = imgA; cx.scD = scD; cx.qA = qA; cx.cbase = imgA + ax.base; cx.Pb = Pb; cx.qcap = qcap; cx.lane = lane;
+#ifdef F4_ABL_NOQUICK
+        const int n1 = 0;
+#else
+        const int n1 = ax.nit > 0 ? f4_quick<PITCH, true>(cx, ax, items, iniTh, item0) : 0;
+#endif
+        f4_finish<PITCH>(iniTh, minTh, totalCells, totalSlots, cx, ax, items, n1, slotCap, frame, cellIdx, candCnt, candEnt, err, ovf, ovfList);
+    }
+}
+
+#ifdef ORBX_AB   /* k_fast4p: A/B reference (register-staged tile, separate store pass), not in the product library */
+template <int PITCH>
+__device__ __forceinline__ int f4p_score_nms(const F4Ctx& cx, const CellAux& ax, const int t, const int n1) {
+    const int Pb = PITCH > 0 ? PITCH : cx.Pb, lane = cx.lane;
+    const u32 qA = cx.qA, scD = cx.scD, cbase = cx.cbase;
+    const int n2 = f4_score<PITCH>(cx, t, n1);
 #ifdef F4_ABL_NONMS
     if (n2 < 60000) return 0;
 #endif
@@ -981,7 +1186,7 @@ __device__ __forceinline__ int f4_score_nms(const F4Ctx& cx, const CellAux& ax, 
 
 // packed store of the n3 keypoints in the queue + the cell's count
 template <int PITCH>
-__device__ __forceinline__ void f4_store(const Geom& g, const F4Ctx& cx, const CellAux& ax, const int n3, const int slotCap, const int frame,
+__device__ __forceinline__ void f4p_store(const Geom& g, const F4Ctx& cx, const CellAux& ax, const int n3, const int slotCap, const int frame,
                                          u32* candCnt, u32* candEnt, int* err) {
     const int Pb = PITCH > 0 ? PITCH : cx.Pb, lane = cx.lane;
     const u32 qA = cx.qA, scD = cx.scD, cbase = cx.cbase;
@@ -1006,25 +1211,25 @@ __device__ __forceinline__ void f4_store(const Geom& g, const F4Ctx& cx, const C
 // cv::FAST at iniTh and, only if that leaves the cell empty after non-max suppression, at minTh (ORBextractor.cc:1112-1125);
 // `n1` = result of the first quick pass (already run by the caller)
 template <int PITCH>
-__device__ __forceinline__ void f4_finish(const Geom& g, const F4Ctx& cx, const CellAux& ax, const F4Item* __restrict__ items, int n1, const int slotCap,
+__device__ __forceinline__ void f4p_finish(const Geom& g, const F4Ctx& cx, const CellAux& ax, const F4Item* __restrict__ items, int n1, const int slotCap,
                                           const int frame, const int cellIdx, u32* candCnt, u32* candEnt, int* err, u32* ovf, u32* ovfList) {
     int n3 = 0;
-    if (n1 > 0) n3 = f4_score_nms<PITCH>(cx, ax, g.iniTh, n1);
+    if (n1 > 0) n3 = f4p_score_nms<PITCH>(cx, ax, g.iniTh, n1);
 #if !defined(F4_ABL_NOSCORE) && !defined(F4_ABL_NOAPPEND) && !defined(F4_ABL_NONMS)
     if (n1 >= 0 && n3 == 0 && ax.nit > 0 && g.minTh < g.iniTh) {       // (a higher retry threshold cannot add corners)
         n1 = f4_quick<PITCH>(cx, ax, items, g.minTh);
-        if (n1 > 0) n3 = f4_score_nms<PITCH>(cx, ax, g.minTh, n1);
+        if (n1 > 0) n3 = f4p_score_nms<PITCH>(cx, ax, g.minTh, n1);
     }
 #endif
     if (n1 < 0) {
         if (cx.lane == 0) ovfList[atomicAdd(&ovf[0], 1u)] = (u32)frame * (u32)g.totalCells + (u32)cellIdx;
         return;
     }
-    f4_store<PITCH>(g, cx, ax, n3, slotCap, frame, candCnt, candEnt, err);
+    f4p_store<PITCH>(g, cx, ax, n3, slotCap, frame, candCnt, candEnt, err);
 }
 
 template <int PITCH>
-__global__ __launch_bounds__(F3_NT) void k_fast4(Geom g, const u8* const* l0, int l0pitch, const u8* pyr,
+__global__ __launch_bounds__(F3_NT) void k_fast4p(Geom g, const u8* const* l0, int l0pitch, const u8* pyr,
                                                  const CellAux* __restrict__ aux, const F4Item* __restrict__ items,
                                                  const StripInfo* __restrict__ strips,
                                                  u32* candCnt, u32* candEnt, int* err, int tileBytes, int qcap,
@@ -1087,9 +1292,10 @@ __global__ __launch_bounds__(F3_NT) void k_fast4(Geom g, const u8* const* l0, in
 #else
         const int n1 = ax.nit > 0 ? f4_quick<PITCH>(cx, ax, items, g.iniTh) : 0;
 #endif
-        f4_finish<PITCH>(g, cx, ax, items, n1, L.slotCap, frame, st.cell0 + c, candCnt, candEnt, err, ovf, ovfList);
+        f4p_finish<PITCH>(g, cx, ax, items, n1, L.slotCap, frame, st.cell0 + c, candCnt, candEnt, err, ovf, ovfList);
     }
 }
+#endif  /* ORBX_AB */
 
 // ------------------------------------------------------------------------------------------------
 // k_quadtree: ORBextractor::DistributeOctTree for one (level, frame) per workgroup.
