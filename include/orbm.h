@@ -961,10 +961,15 @@ int orbm_stereo_matches(orbm_t*, void* left_extractor, int frame_l, void* right_
 
 /* SURVEY 8(f).2  Frame::UndistortKeyPoints (Frame.cc:924-970): cv::undistortPoints(points, K, D, R = I, P = newK) on the
  * coordinates of n keypoints (other fields copied).  k / newk = (fx, fy, cx, cy); dist = (k1, k2, p1, p2[, k3 ...]),
- * ndist <= 14.  dist[0] == 0 copies the input (Frame.cc:928-932).  space = ORBM_HOST | ORBM_DEVICE for kps and out. */
+ * ndist <= 14 in OpenCV's order (k1, k2, p1, p2, k3, k4, k5, k6, s1, s2, s3, s4, tauX, tauY): the radial, tangential, rational
+ * and thin-prism terms are applied.  The tilted sensor model is NOT implemented: a call whose dist[12] or dist[13] is nonzero is
+ * refused with ORBM_E_INVALID (orbm_last_error says so) before anything is launched -- the reference never passes more than five
+ * coefficients (Frame.cc:924-970).  dist[0] == 0 copies the input (Frame.cc:928-932).  space = ORBM_HOST | ORBM_DEVICE for kps
+ * and out. */
 int orbm_undistort_keypoints(orbm_t*, int space, const orbm_kp_t* kps, int n, const float* k, const float* dist, int ndist,
                              const float* newk, orbm_kp_t* out);
-/* Frame::ComputeImageBounds (Frame.cc:977-1021): bounds[4] = (mnMinX, mnMaxX, mnMinY, mnMaxY) (host output). */
+/* Frame::ComputeImageBounds (Frame.cc:977-1021): bounds[4] = (mnMinX, mnMaxX, mnMinY, mnMaxY) (host output).  Nonzero tilt
+ * coefficients are refused as above. */
 int orbm_image_bounds(orbm_t*, int cols, int rows, const float* k, const float* dist, int ndist, const float* newk, float* bounds);
 
 /* SURVEY 8(f).3  Frame::isInFrustum (Nleft == -1; Frame.cc:603-671) + MapPoint::PredictScale (MapPoint.cc:725-740) +

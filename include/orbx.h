@@ -178,7 +178,11 @@ int orbx_gray_from_color(orbx_t*, const uint8_t* const* src, int src_space, int 
 /* SURVEY 8(f).4 stereo rectification -- replaces cv::remap(im, imRect, M1, M2, cv::INTER_LINEAR) of the stereo examples
  * (Examples/Stereo/stereo_euroc.cc:168-169) for 8-bit single-channel images with CV_32F maps, BORDER_CONSTANT 0.
  * src[i] / dst[i] / mapx / mapy are DEVICE pointers (the maps are uploaded once, e.g. with orbx_dev_alloc + orbx_memcpy_h2d);
- * maps and destination are dw x dh.  Enqueued on the extractor's stream. */
+ * maps and destination are dw x dh (any size, not tied to sw x sh).  Enqueued on the extractor's stream.
+ * Map entries nothing forbids: OpenCV converts with s = cvRound(v * 32) and keeps saturate_cast<short>(s >> 5), so a non-finite
+ * entry (x86's cvRound gives INT_MIN) or one with |s| >> 5 > 32767 addresses no pixel of any source it can hold: such a
+ * destination pixel is the border value 0, whatever the other coordinate says.  For the same reason sw or sh above 32767 is
+ * refused with ORBX_E_UNSUPPORTED before anything is enqueued. */
 int orbx_remap_linear(orbx_t*, const uint8_t* const* src, int nimg, int sw, int sh, int src_stride, const float* mapx, const float* mapy,
                       int dw, int dh, uint8_t* const* dst, int dst_stride);
 /* SURVEY 8(f).4  cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply(im, im) of the TUM-VI examples

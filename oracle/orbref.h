@@ -213,7 +213,9 @@ int orbref_stereo_matches(const orbref_t* left, const orbref_t* right,
  * coordinates.  OpenCV's routine is restated (cvUndistortPointsInternal: double arithmetic, exactly 5 fixed-point
  * iterations -- TermCriteria(MAX_ITER, 5, 0.01) -- with the `icdist < 0` bail-out; rational/thin-prism terms are zero for
  * the 4/5-coefficient models ORB-SLAM3 configures).  k = (fx, fy, cx, cy); dist = (k1, k2, p1, p2[, k3]).  dist[0] == 0
- * copies the input (Frame.cc:928-932).  Other keypoint fields are copied.  OpenCV version unpinned -> parity unpinned. */
+ * copies the input (Frame.cc:928-932).  Other keypoint fields are copied.  OpenCV version unpinned -> parity unpinned.
+ * Up to 14 coefficients are read (k4..k6, s1..s4 are applied); the tilt terms dist[12] / dist[13] have no inverse here, so a
+ * call with either nonzero returns -2 (orbref_image_bounds likewise). */
 int orbref_undistort_keypoints(const orbref_kp_t* kps, int n, const float* k, const float* dist, int ndist, const float* newk,
                                orbref_kp_t* out);
 /* Frame::ComputeImageBounds (Frame.cc:977-1021): bounds = (minX, maxX, minY, maxY) from the four undistorted corners. */
@@ -242,7 +244,9 @@ int orbref_gray_from_color(const uint8_t* src, int w, int h, int src_stride, int
  * (Examples/Stereo/stereo_euroc.cc:168-169), default BORDER_CONSTANT 0.  OpenCV's fixed-point path restated: coordinates
  * cvRound(map * 32) -> integer part >> 5, 5-bit fractions (INTER_BITS); weights (32-fx)(32-fy)*32 ... fx*fy*32 (they sum to
  * 1 << 15 exactly, so the table's sum correction never triggers for INTER_LINEAR); dst = (sum + (1 << 14)) >> 15; taps
- * outside the source read 0.  OpenCV version unpinned -> parity unpinned. */
+ * outside the source read 0.  OpenCV keeps saturate_cast<short>(s >> 5) of s = cvRound(map * 32): a non-finite entry (INT_MIN
+ * on x86) or one with |s| >> 5 > 32767 is outside every addressable source and gives 0; sw or sh above 32767 returns -2.
+ * OpenCV version unpinned -> parity unpinned. */
 int orbref_remap_linear(const uint8_t* src, int sw, int sh, int src_stride, const float* mapx, const float* mapy,
                         int dw, int dh, uint8_t* dst, int dst_stride);
 

@@ -944,6 +944,11 @@ static void undistort_point(double u, double v, const double k[14], double fx, d
     *ox = (float)(xx * ww); *oy = (float)(yy * ww);
 }
 
+static bool has_tilt(const float* dist, int ndist) {                 // tauX / tauY: no inverse tilt here, so such a call is refused (-2)
+    for (int i = 12; i < ndist && i < 14; ++i) if (!(dist[i] == 0.0f)) return true;
+    return false;
+}
+
 static void load_dist(const float* dist, int ndist, double k[14]) {
     for (int i = 0; i < 14; ++i) k[i] = 0.0;
     for (int i = 0; i < ndist && i < 14; ++i) k[i] = (double)dist[i];
@@ -951,7 +956,7 @@ static void load_dist(const float* dist, int ndist, double k[14]) {
 
 int orbref_undistort_keypoints(const orbref_kp_t* kps, int n, const float* kk, const float* dist, int ndist, const float* newk,
                                orbref_kp_t* out) {
-    if (n < 0 || !kk || !newk || (ndist > 0 && !dist)) return -2;
+    if (n < 0 || !kk || !newk || (ndist > 0 && !dist) || has_tilt(dist, ndist)) return -2;
     for (int i = 0; i < n; ++i) out[i] = kps[i];
     if (ndist < 1 || dist[0] == 0.0f) return n;                      // Frame.cc:928-932
     double k[14]; load_dist(dist, ndist, k);
@@ -962,7 +967,7 @@ int orbref_undistort_keypoints(const orbref_kp_t* kps, int n, const float* kk, c
 }
 
 int orbref_image_bounds(int cols, int rows, const float* kk, const float* dist, int ndist, const float* newk, float* bounds) {
-    if (!kk || !newk || !bounds) return -2;
+    if (!kk || !newk || !bounds || (ndist > 0 && !dist) || has_tilt(dist, ndist)) return -2;
     if (ndist < 1 || dist[0] == 0.0f) { bounds[0] = 0.f; bounds[1] = (float)cols; bounds[2] = 0.f; bounds[3] = (float)rows; return 0; }
     double k[14]; load_dist(dist, ndist, k);
     const float cxs[4] = {0.f, (float)cols, 0.f, (float)cols}, cys[4] = {0.f, 0.f, (float)rows, (float)rows};
@@ -1034,11 +1039,20 @@ int orbref_gray_from_color(const uint8_t* src, int w, int h, int src_stride, int
 
 int orbref_remap_linear(const uint8_t* src, int sw, int sh, int src_stride, const float* mapx, const float* mapy,
                         int dw, int dh, uint8_t* dst, int dst_stride) {
-    if (!src || !mapx || !mapy || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1) return -2;
+    if (!src || !mapx || !mapy || !dst || sw < 1 || sh < 1 || dw < 1 || dh < 1 || sw > 32767 || sh > 32767) return -2;
+    // cvRound(map * INTER_TAB_SIZE), then saturate_cast<short>(s >> 5): from |s| = 2^20 on, and for a non-finite entry (x86's
+    // cvRound gives INT_MIN), the short lands outside every source of at most 32767 columns / rows -> all four taps read 0
+    auto fix = [](float v, bool* outside) -> int {
+        const float r = std::nearbyint(v * 32.f);
+        *outside = !(std::fabs(r) < 1048576.f);
+        return *outside ? 0 : (int)r;
+    };
     auto at = [&](int x, int y) -> int { return (x >= 0 && x < sw && y >= 0 && y < sh) ? src[(size_t)y * src_stride + x] : 0; };
     for (int y = 0; y < dh; ++y)
         for (int x = 0; x < dw; ++x) {
-            const int sx = (int)lrintf(mapx[(size_t)y * dw + x] * 32.f), sy = (int)lrintf(mapy[(size_t)y * dw + x] * 32.f);   // cvRound(map * INTER_TAB_SIZE)
+            bool ox, oy;
+            const int sx = fix(mapx[(size_t)y * dw + x], &ox), sy = fix(mapy[(size_t)y * dw + x], &oy);
+            if (ox || oy) { dst[(size_t)y * dst_stride + x] = 0; continue; }
             const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
             const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
             const int v = at(ix, iy) * w00 + at(ix + 1, iy) * w01 + at(ix, iy + 1) * w10 + at(ix + 1, iy + 1) * w11;

@@ -2376,9 +2376,18 @@ static bool fill_undist(UndistParams& P, const float* k, const float* dist, int 
     return ndist < 1 || dist[0] == 0.0f;                         // Frame.cc:928: first coefficient zero -> no undistortion
 }
 
+// tauX / tauY (dist[12], dist[13]): undistort_point has no inverse tilt, so a call that sets either is refused instead of
+// quietly getting the 12-term answer
+static bool has_tilt(const float* dist, int ndist) {
+    for (int i = 12; i < ndist && i < 14; ++i)
+        if (!(dist[i] == 0.0f)) { set_merr("undistortion: the tilted sensor model (dist[12], dist[13] nonzero) is not implemented"); return true; }
+    return false;
+}
+
 int orbm_undistort_keypoints(orbm_t* m, int space, const orbm_kp_t* kps, int n, const float* k, const float* dist, int ndist,
                              const float* newk, orbm_kp_t* out) {
     if (!m || n < 0 || !k || !newk || ndist < 0 || ndist > 14 || (ndist > 0 && !dist) || (n > 0 && (!kps || !out))) return ORBM_E_INVALID;
+    if (has_tilt(dist, ndist)) return ORBM_E_INVALID;
     if (n == 0) return 0;
     MHIPCHK(hipSetDevice(m->device));
     UndistParams P;
@@ -2402,6 +2411,7 @@ int orbm_undistort_keypoints(orbm_t* m, int space, const orbm_kp_t* kps, int n, 
 
 int orbm_image_bounds(orbm_t* m, int cols, int rows, const float* k, const float* dist, int ndist, const float* newk, float* bounds) {
     if (!m || !k || !newk || !bounds || ndist < 0 || ndist > 14 || (ndist > 0 && !dist)) return ORBM_E_INVALID;
+    if (has_tilt(dist, ndist)) return ORBM_E_INVALID;
     if (ndist < 1 || dist[0] == 0.0f) { bounds[0] = 0.f; bounds[1] = (float)cols; bounds[2] = 0.f; bounds[3] = (float)rows; return ORBM_OK; }
     orbm_kp_t c[4], u[4];
     memset(c, 0, sizeof(c));

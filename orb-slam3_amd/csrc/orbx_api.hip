@@ -1733,6 +1733,8 @@ int orbx_remap_linear(orbx_t* o, const uint8_t* const* src, int nimg, int sw, in
                       int dw, int dh, uint8_t* const* dst, int dst_stride) {
     if (!o || !src || !dst || !mapx || !mapy || nimg < 1 || sw < 1 || sh < 1 || dw < 1 || dh < 1 || src_stride < sw || dst_stride < dw) return ORBX_E_INVALID;
     for (int i = 0; i < nimg; ++i) if (!src[i] || !dst[i]) return ORBX_E_EMPTY;
+    // cv::remap addresses the source with short coordinates: columns / rows from 32767 on cannot be reached
+    if (sw > 32767 || sh > 32767) { set_err("remap source %dx%d exceeds 32767 in a dimension", sw, sh); return ORBX_E_UNSUPPORTED; }
     HIPCHK(hipSetDevice(o->device));
     hipStream_t st = o->stream;
     const size_t tab = (sizeof(u8*) * nimg + 255) & ~(size_t)255;

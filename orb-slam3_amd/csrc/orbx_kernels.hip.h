@@ -2737,7 +2737,10 @@ __global__ __launch_bounds__(256) void k_remap(const u8* const* srcs, int sw, in
     for (int i = 0; i < 4; ++i) {
         if (i < n) {
             const size_t mi = (size_t)y * dw + x0 + i;
-            const int sx = __float2int_rn(mapx[mi] * 32.f), sy = __float2int_rn(mapy[mi] * 32.f);
+            // cvRound(map * 32) as a float first: OpenCV keeps saturate_cast<short>(s >> 5), so an entry with |s| >= 2^20 -- and a
+            // non-finite one, for which the compare is false -- lies outside every source it can address and reads the border
+            const float rx = rintf(mapx[mi] * 32.f), ry = rintf(mapy[mi] * 32.f);
+            const int sx = fabsf(rx) < 1048576.f ? (int)rx : -64, sy = fabsf(ry) < 1048576.f ? (int)ry : -64;   // -64: both taps left of / above the image
             const int ix = sx >> 5, iy = sy >> 5, fx = sx & 31, fy = sy & 31;
             const bool x0ok = ix >= 0 && ix < sw, x1ok = ix + 1 >= 0 && ix + 1 < sw, y0ok = iy >= 0 && iy < sh, y1ok = iy + 1 >= 0 && iy + 1 < sh;
             const u8* p = s + (size_t)iy * sstride + ix;
