@@ -81,9 +81,17 @@ struct orbx {
     std::vector<int> stripTile, stripQ;                       // per strip: tile bytes, worst-case queue entries
     std::vector<RzTab> xt, yt;
     std::vector<RzX4> x4;
-    std::vector<RzTask> rzTasks[12];
+    std::vector<RzTask> rzTasks[12];                          // per level: the full-tile tasks, then the packed remainder tasks
     RzX4* dX4 = nullptr; RzTask* dRzTasks = nullptr; size_t capX4 = 0, capRzTasks = 0;
     int rzTaskOff[12] = {}; bool rzStream[12] = {};
+    int rzNFull[12] = {}, rzNPack[12] = {}, rzPack[12] = {};  // task counts of the two kinds; frames per wave of the packed kind
+#ifdef ORBX_AB
+    bool rzNoPack = false;                                    // ORBX_RESIZE_NOPACK: A/B, one frame per wave everywhere (the form of a slab too large for 32-bit lane offsets)
+    bool rzV2p = false;                                       // ORBX_RESIZE_V2P: A/B, k_resize2p (8-row tasks of one frame) instead of k_resize2
+    std::vector<RzTaskP> rzTasksP[12];
+    RzTaskP* dRzTasksP = nullptr; size_t capRzTasksP = 0;
+    int rzTaskOffP[12] = {}; bool rzStreamP[12] = {};
+#endif
     int64_t algBytes = 0, fusedBytes = 0;
     size_t qtLds = 0, qt2Lds = 0;
     int qtFuseD = 3;
@@ -213,6 +221,9 @@ static int build_geometry(orbx* o, int w, int h) {
     g.nlevels = L; g.w0 = w; g.h0 = h; g.iniTh = o->iniTh; g.minTh = o->minTh; g.lowTh = std::min(o->iniTh, o->minTh);
     std::vector<Blur3Task> tiles3one;                         // one-tile k_blur3 tasks, appended behind the walks
     o->cells.clear(); o->tiles.clear(); o->tiles3.clear(); o->b3Th.clear(); o->b3Tv.clear(); o->strips.clear(); o->f3g.clear(); o->stripTile.clear(); o->stripQ.clear(); o->xt.clear(); o->yt.clear(); o->x4.clear(); for (auto& v : o->rzTasks) v.clear();
+#ifdef ORBX_AB
+    for (auto& v : o->rzTasksP) v.clear();
+#endif
     size_t off = 0, boff = 0;
     int totalSlots = 0, totalSel = 0, maxN = 0;
     int64_t sumAll = 0, sumSrc = 0, sumDst = 0;
@@ -394,18 +405,56 @@ static int build_geometry(orbx* o, int w, int h) {
                 const int sy = o->yt[D.rzy + dy].s;
                 if (sy < 0 || sy + 1 >= S.h || (dy > 0 && sy <= o->yt[D.rzy + dy - 1].s)) ok = false;
             }
-            for (int ty = 0; ty < D.h && ok; ty += RZ_R) {
-                const int ye = std::min(ty + RZ_R, D.h);
-                if (o->yt[D.rzy + ye - 1].s + 2 - o->yt[D.rzy + ty].s > RZ_SRC) ok = false;
-            }
-            o->rzStream[l] = ok;
-            if (ok)
-                for (int ty = 0; ty < D.h; ty += RZ_R)
-                    for (int gx = 0; gx * 4 < D.w; gx += 64) o->rzTasks[l].push_back(RzTask{(short)l, (short)gx, (short)ty, 0});
+            auto span_ok = [&](int R, int nsrcMax) {
+                for (int ty = 0; ty < D.h; ty += R)
+                    if (o->yt[D.rzy + std::min(ty + R, D.h) - 1].s + 2 - o->yt[D.rzy + ty].s > nsrcMax) return false;
+                return true;
+            };
+#ifdef ORBX_AB
+            o->rzStreamP[l] = ok && span_ok(RZP_R, RZP_SRC);
+            if (o->rzStreamP[l])
+                for (int ty = 0; ty < D.h; ty += RZP_R)
+                    for (int gx = 0; gx * 4 < D.w; gx += 64) o->rzTasksP[l].push_back(RzTaskP{(short)l, (short)gx, (short)ty, 0});
+#endif
+            o->rzStream[l] = ok && span_ok(RZ_R, RZ_SRC);        // (its task records need the slab size: below)
         }
         while (o->xt.size() % 4) o->xt.push_back(RzTab{0, 0, 0});      // keep every level's tap offset a multiple of 4
     }
     g.pyrFrameBytes = off;
+    // k_resize2's task records.  A level of ndw dwords has ndw / 64 full column tiles (a wave per tile and frame) and, for the
+    // remainder r = ndw % 64, one packed tile whose wave serves 64 / r consecutive frames.  The lanes of a packed wave reach their
+    // frames' slabs by 32-bit offsets from the first one's, so packing needs 64 slabs within 4 GiB; otherwise the tile keeps a frame per wave.
+    for (int l = 1; l < L; ++l) {
+        o->rzNFull[l] = o->rzNPack[l] = 0; o->rzPack[l] = 1;
+        if (!o->rzStream[l]) continue;
+        const LevelDesc &D = g.lv[l], &S = g.lv[l - 1];
+        const int ndw = (D.w + 3) / 4, nfullTiles = ndw / 64, r = ndw % 64;
+        bool canPack = (uint64_t)off * 64 <= (1ull << 32);
+#ifdef ORBX_AB
+        if (o->rzNoPack) canPack = false;
+#endif
+        const int pack = r && canPack ? 64 / r : 1;
+        std::vector<RzTask> packed;
+        for (int ty = 0; ty < D.h; ty += RZ_R) {
+            RzTask t{};
+            const int ye = std::min(ty + RZ_R, D.h);
+            t.y0 = ty; t.sFirst = o->yt[D.rzy + ty].s; t.nsrc = o->yt[D.rzy + ye - 1].s + 2 - t.sFirst;
+            for (int dy = ty; dy < ye; ++dy) {
+                const RzTab& e = o->yt[D.rzy + dy];
+                const int j = e.s + 1 - t.sFirst;                 // >= 1, distinct per dy (source rows strictly increase), < nsrc <= RZ_SRC
+                t.emit |= 1u << j;
+                t.taps[j] = (u32)(unsigned short)e.a0 | ((u32)(unsigned short)e.a1 << 16);
+            }
+            t.dpitch = D.pitch; t.doff = D.off; t.x4base = D.rzx / 4; t.spitch = S.pitch; t.soff = S.off;
+            for (int tile = 0; tile < nfullTiles; ++tile) { t.g0 = tile * 64; t.pack = 1; t.gw = 64; t.gmul = 1024; o->rzTasks[l].push_back(t); }
+            if (r) { t.g0 = nfullTiles * 64; t.pack = pack; t.gw = r; t.gmul = (65536 + r - 1) / r; packed.push_back(t); }
+        }
+        o->rzNFull[l] = (int)o->rzTasks[l].size(); o->rzNPack[l] = (int)packed.size(); o->rzPack[l] = pack;
+        o->rzTasks[l].insert(o->rzTasks[l].end(), packed.begin(), packed.end());
+        // the kernel divides a wave's index by a task count with one high multiply, exact while index * count < 2^32
+        const uint64_t nmax = (uint64_t)o->rzTasks[l].size() * (uint64_t)o->maxBatch;
+        if (nmax * (uint64_t)std::max(o->rzNFull[l], o->rzNPack[l]) >= (1ull << 32)) { o->rzStream[l] = false; o->rzTasks[l].clear(); }
+    }
     g.blurTiled = o->blurTiled ? 1 : 0;
     g.blrFrameBytes = o->blurTiled ? boff : off;
     g.totalCells = (int)o->cells.size();
@@ -464,6 +513,12 @@ static int build_geometry(orbx* o, int w, int h) {
         if (ensure(&o->dRzTasks, &o->capRzTasks, std::max<size_t>(1, all.size()))) return ORBX_E_HIP;
         if (!o->x4.empty()) HIPCHK(hipMemcpy(o->dX4, o->x4.data(), o->x4.size() * sizeof(RzX4), hipMemcpyHostToDevice));
         if (!all.empty()) HIPCHK(hipMemcpy(o->dRzTasks, all.data(), all.size() * sizeof(RzTask), hipMemcpyHostToDevice));
+#ifdef ORBX_AB
+        std::vector<RzTaskP> allP;
+        for (int l = 0; l < L; ++l) { o->rzTaskOffP[l] = (int)allP.size(); allP.insert(allP.end(), o->rzTasksP[l].begin(), o->rzTasksP[l].end()); }
+        if (ensure(&o->dRzTasksP, &o->capRzTasksP, std::max<size_t>(1, allP.size()))) return ORBX_E_HIP;
+        if (!allP.empty()) HIPCHK(hipMemcpy(o->dRzTasksP, allP.data(), allP.size() * sizeof(RzTaskP), hipMemcpyHostToDevice));
+#endif
     }
     if (ensure(&o->dCandCnt, &o->capCandCnt, (size_t)g.totalCells * B)) return ORBX_E_HIP;
     HIPCHK(hipMemset(o->dCandCnt, 0, sizeof(u32) * (size_t)g.totalCells * B));   // a cell no kernel has written yet is an EMPTY cell, not whatever the allocation held
@@ -732,6 +787,10 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     o->f3NoFixedPitch = ab_env("ORBX_FAST_PITCH0") != nullptr;
     o->fastV3 = ab_env("ORBX_FAST_V3") != nullptr;
     o->fastV4p = ab_env("ORBX_FAST_V4P") != nullptr;
+#ifdef ORBX_AB
+    o->rzNoPack = ab_env("ORBX_RESIZE_NOPACK") != nullptr;
+    o->rzV2p = ab_env("ORBX_RESIZE_V2P") != nullptr;
+#endif
     if (const char* e = ab_env("ORBX_QT_WIDE")) o->qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
     o->blurTiled = !o->blurV2 && !o->odV1 && ab_env("ORBX_BLUR_ROWMAJOR") == nullptr;
@@ -815,6 +874,9 @@ void orbx_destroy(orbx_t* o) {
     void* ptrs[] = {o->dPyr, o->dBlur, o->dL0, (void*)o->dL0Ptr, o->dCells, o->dTiles, o->dTiles3, o->dB3Th, o->dB3Tv, o->dStrips, o->dAux, o->dF4Items, o->dX4, o->dRzTasks, o->dXt, o->dYt, o->dCandCnt, o->dCandEnt,
                     o->dSel, o->dSelCnt, o->dKpNode, o->dDense, o->rb[0].base, o->rb[1].base, o->rb[2].base, o->rb[3].base, o->rb[4].base, o->rb[5].base, o->rb[6].base, o->rb[7].base, o->dWork, o->dLap, o->dErr, o->dPattern, o->dOvf, o->dOvfList, o->dOdW, (void*)o->dStamps};
     for (void* p : ptrs) if (p) (void)hipFree(p);
+#ifdef ORBX_AB
+    if (o->dRzTasksP) (void)hipFree(o->dRzTasksP);
+#endif
     for (auto& set : o->evr) for (auto& e : set) if (e) (void)hipEventDestroy(e);
     if (o->evDone) (void)hipEventDestroy(o->evDone);
     if (o->evGuard) (void)hipEventDestroy(o->evGuard);
@@ -923,10 +985,24 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     HIPCHK(hipStreamWaitEvent(s1, dep_ev(o, 0), 0));             // inputs uploaded; previous batch's readers of the pyramid are done
     STAGE_EV(7, s1);
     for (int l = 1; l < g.nlevels; ++l) {
+#ifdef ORBX_AB
+        if (o->rzV2p && o->rzStreamP[l]) {
+            const int nt = (int)o->rzTasksP[l].size();
+            hipLaunchKernelGGL(k_resize2p, dim3((nt + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr,
+                               o->dRzTasksP + o->rzTaskOffP[l], nt, o->dX4, o->dYt);
+        } else
+#endif
         if (o->rzStream[l]) {
-            const int nt = (int)o->rzTasks[l].size();
-            hipLaunchKernelGGL(k_resize2, dim3((nt + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr,
-                               o->dRzTasks + o->rzTaskOff[l], nt, o->dX4, o->dYt);
+            // a flat list of waves: full tiles x frames, then packed remainder tiles x groups of `pack` frames
+            RzLaunch P;
+            P.nFull = (u32)o->rzNFull[l]; P.nPack = (u32)o->rzNPack[l]; P.nimg = (u32)nimg;
+            P.nFullW = P.nFull * P.nimg;
+            P.nWaves = P.nFullW + P.nPack * (u32)((nimg + o->rzPack[l] - 1) / o->rzPack[l]);
+            P.mFull = P.nFull > 1 ? (u32)((1ull << 32) / P.nFull) + 1u : 0u;
+            P.mPack = P.nPack > 1 ? (u32)((1ull << 32) / P.nPack) + 1u : 0u;
+            auto kern = l == 1 ? k_resize2<true> : k_resize2<false>;
+            hipLaunchKernelGGL(kern, dim3((P.nWaves + 3) / 4), dim3(256), 0, s1, o->dL0Ptr, l0pitch, o->dPyr, g.pyrFrameBytes,
+                               o->dRzTasks + o->rzTaskOff[l], P, o->dX4);
         } else {                                                 // general fallback (large scale factors)
             dim3 grid((g.lv[l].w + 255) / 256, (g.lv[l].h + 3) / 4, nimg), block(64, 4);
             hipLaunchKernelGGL(k_resize, grid, block, 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, l, o->dXt, o->dYt);

@@ -76,10 +76,15 @@ __device__ __forceinline__ us2 pkmax3(us2 a, us2 b, us2 c) {
     return __builtin_bit_cast(us2, d);
 }
 
-__device__ __forceinline__ u32 ashr_pk_u8(u32 a, u32 b, u32 sh) {  // sat_u8(a >> sh) | sat_u8(b >> sh) << 8 (arithmetic shifts; upper half 0)
+// sat_u8(a >> sh) | sat_u8(b >> sh) << 8 in the LOW half of the result (arithmetic shifts).  The instruction writes 16 bits: the upper half
+// of the result is whatever the destination register held before, so it must not be used (pack2x16 below ignores it).
+__device__ __forceinline__ u32 ashr_pk_u8(u32 a, u32 b, u32 sh) {
     u32 d;
     asm("v_ashr_pk_u8_i32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(sh));
     return d;
+}
+__device__ __forceinline__ u32 pack2x16(u32 lo, u32 hi) {          // lo[15:0] | hi[15:0] << 16 in one v_perm, whatever the upper halves hold
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);
 }
 __device__ __forceinline__ u32 mad24(u32 a, u32 b, u32 c) {      // a*b + c on 24-bit operands, one VALU instruction
     u32 d;
@@ -190,20 +195,170 @@ __global__ __launch_bounds__(256) void k_resize(Geom g, const u8* const* l0, int
 // the four tap pairs of a lane span < 8 bytes for scale factors up to 1.5); the pair of pixel i is picked and widened
 // by ONE v_perm with a per-lane selector and reduced with one v_dot2_u32_u16 against (a0,a1).  The
 // horizontal result of source row sy+1 is reused as row sy of the next destination row (the reference's
-// cv::resize keeps the same two-row cache).  Row taps come from the scalar unit (wave-uniform).
+// cv::resize keeps the same two-row cache).
+//   * A task is a column tile of RZ_R destination rows.  Everything wave-uniform about it -- first source row, number of source
+//     rows, which source row completes a destination row and with which row taps, pitches and slab offsets of both levels -- is
+//     the same for every frame, so the host writes it into one 128-byte record (RzTask) that the wave takes with wide scalar loads
+//     in ONE round behind the kernel arguments; the empty asm statement names the values, so that the loads are not sunk into the
+//     row loop (profiles/NOTES.md, k_fast4).  The row loop branches on a bit of a scalar mask; no scalar load is left in it.
+//   * Full tiles (64 dwords) serve one frame per wave.  The remainder tile of a level (r = dwords mod 64) serves pack = 64 / r
+//     consecutive frames per wave: lane -> (frame k = lane / r, column lane % r).  The lanes of frame f0 + k address the slab of
+//     frame f0 plus a 32-bit offset k * pyrFrameBytes (the host packs only where 64 slabs fit 32 bits); level 1 reads the caller's
+//     frame pointers, per lane and 64 bits wide, in a body of its own (MODE 1).  A lane without a frame reads frame f0 and stores nothing.
+//   * One launch per level over a flat list of waves: full tasks x frames, then packed tasks x ceil(frames / pack).
+//   * All source rows of a task are in flight before any arithmetic.
 // ------------------------------------------------------------------------------------------------
 #define RZ_R 8
-#define RZ_SRC 12                                          // source rows one task may touch (host checks)
+#define RZ_SRC 12                                          // source rows one task may touch: what RZ_R rows need at scale factors up to 1.5 (host checks)
 struct RzX4 { int bs; u8 o[4]; u32 a[4]; };                // per destination dword: byte offset of the first tap, tap offsets from it (<= 6), (2*a0 | 2*a1<<16): DOUBLED Q11 taps
-struct RzTask { short level, g0, y0, pad; };
+struct alignas(64) RzTask {                                // 32 words
+    int g0, y0;                                            // first destination dword and row
+    int pack, gw, gmul;                                    // frames per wave, lanes per frame (64: full tile), ceil(65536 / gw)
+    int sFirst, nsrc;                                      // first source row, source rows (2 .. RZ_SRC)
+    u32 emit;                                              // bit j: source row sFirst + j completes a destination row (bit 0 is never set)
+    int dpitch, doff, x4base;                              // destination level: pitch, offset in the slab, first entry of the x4 table
+    int spitch, soff;                                      // source level (levels >= 1; level 0 is the caller's)
+    int pad[3];
+    u32 taps[16];                                          // [j]: a0 | a1 << 16 of the destination row that source row j completes
+};
+static_assert(sizeof(RzTask) == 128 && RZ_SRC == 12, "RzTask is read as 32 scalar words, of which 13 + 11 are pinned");
+struct RzLaunch { u32 nFull, nPack, nimg, nFullW, nWaves, mFull, mPack; };   // mX = floor(2^32 / nX) + 1: n / nX = umulhi(n, mX) while n * nX < 2^32 (host checks)
 
-__global__ __launch_bounds__(256) void k_resize2(Geom g, const u8* const* l0, int l0pitch, u8* pyr,
-                                                 const RzTask* __restrict__ tasks, int ntasks,
-                                                 const RzX4* __restrict__ x4, const RzTab* __restrict__ yt) {
+__device__ __forceinline__ RzX4 rz_x4_load(uintptr_t table, u32 i) {                 // table: a global address that has been through an asm statement
+    RzX4 X;
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(1))) u32* p = (const __attribute__((address_space(1))) u32*)(table + (uintptr_t)i * sizeof(RzX4));
+    X.bs = (int)p[0];
+    const u32 o = p[1];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { X.o[k] = (u8)(o >> (8 * k)); X.a[k] = p[2 + k]; }
+#else
+    X = ((const RzX4*)table)[i];
+#endif
+    return X;
+}
+
+// MODE 0: wave-uniform source base + 32-bit lane offset; MODE 1: 64-bit source address per lane (row offset added per row)
+template <int MODE>
+__device__ __forceinline__ void rz_rows(const u8* src, const u8* srcLane, u32 colo, int sp, int sFirst, int nsrc, u32 emit, const u32 (&T)[32],
+                                        const u32 (&xa)[4], const u32 (&sel)[4], u8* dst, u32 dcol, int dpitch, int y0, bool act) {
+    auto ld = [&](int j) -> uint2 {
+        const u32 ro = (u32)((sFirst + j) * sp);                                        // wave-uniform
+        return MODE == 0 ? gload64u_unaligned(src, ro + colo) : gload64u_unaligned(srcLane, ro);
+    };
+    auto hrow = [&](const uint2 v, int (&H)[4]) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const us2 s2 = as_us2(__builtin_amdgcn_perm(v.y, v.x, sel[i]));              // (byte o, byte o+1) as a u16 pair
+            // only (H >> 4) is ever used; it is kept as (H >> 4) << 5 -- the table's taps are doubled, so that is one AND -- for the
+            // 24-bit high multiply below
+            H[i] = (int)(__builtin_amdgcn_udot2(s2, as_us2(xa[i]), 0u, false) & ~31u);
+        }
+    };
+    // all source rows of the task in flight before any arithmetic (a row beyond nsrc is neither loaded nor read)
+    uint2 d[RZ_SRC];
+#pragma unroll
+    for (int j = 0; j < RZ_SRC; ++j)
+        if (j < nsrc) d[j] = ld(j);
+    int Hp[4];
+    hrow(d[0], Hp);                                                                     // nsrc >= 2
+    u32 drow = (u32)(y0 * dpitch);
+#pragma unroll
+    for (int j = 1; j < RZ_SRC; ++j) {
+        if (j < nsrc) {
+            int Hc[4];
+            hrow(d[j], Hc);
+            if ((emit >> j) & 1u) {                                 // rows (sy, sy+1) = (j-1, j) are both here: emit the next destination row
+                // (b * (H >> 4)) >> 16 as ONE v_mul_hi_u32_u24: (b << 11) * ((H >> 4) << 5) = b * (H >> 4) * 2^16, whose bits 47..32 are
+                // the wanted quotient (b <= 2048 -> 22 bits, (H >> 4) << 5 < 2^20: both operands fit 24 bits, nothing is rounded)
+                const u32 A0 = (T[16 + j] & 0xffffu) << 11, A1 = (T[16 + j] >> 16) << 11;
+                u32 sum[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sum[i] = mulhi24(A0, (u32)Hp[i]) + mulhi24(A1, (u32)Hc[i]) + 2u;
+                // each term is <= 1020, so (sum + 2) >> 2 <= 255: cv::resize's saturate_cast is the identity here.  gfx950's
+                // v_ashr_pk_u8_i32 shifts two sums and packs them as two bytes in one instruction (tools/ubench/isa_probe.hip)
+                const u32 packed = pack2x16(ashr_pk_u8(sum[0], sum[1], 2u), ashr_pk_u8(sum[2], sum[3], 2u));
+                if (act) gstore32u(dst, drow + dcol, packed);
+                drow += (u32)dpitch;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) Hp[i] = Hc[i];
+        }
+    }
+}
+
+template <bool L1>
+__global__ __launch_bounds__(256) void k_resize2(const u8* const* l0, int l0pitch, u8* pyr, size_t pyrFrameBytes,
+                                                 const RzTask* __restrict__ tasks, RzLaunch P, const RzX4* __restrict__ x4) {
+    const u32 lane = threadIdx.x & 63;
+    const u32 w = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+    // every kernel argument in the first round (pointers go through as integers and come back as global pointers, see k_fast4)
+    uintptr_t pyrI = (uintptr_t)pyr, x4I = (uintptr_t)x4, l0I = (uintptr_t)l0, tasksI = (uintptr_t)tasks;
+    asm volatile("" : "+s"(pyrI), "+s"(x4I), "+s"(l0I), "+s"(tasksI), "+s"(pyrFrameBytes), "+s"(l0pitch), "+s"(P.nFull), "+s"(P.nPack), "+s"(P.nimg),
+                 "+s"(P.nFullW), "+s"(P.nWaves), "+s"(P.mFull), "+s"(P.mPack));
+    pyr = (u8*)(__attribute__((address_space(1))) u8*)pyrI;
+    if (w >= P.nWaves) return;
+    // wave -> (task, frame or frame group)
+    const bool full = w < P.nFullW;
+    const u32 wq = full ? w : w - P.nFullW, nd = full ? P.nFull : P.nPack;
+    const u32 fq = nd == 1 ? wq : __umulhi(wq, full ? P.mFull : P.mPack);
+    const u32 ti = wq - fq * nd + (full ? 0u : P.nFull);
+    // the one scalar round: the task's record and, for a full tile of level 1, its frame's pointer (read through the constant address
+    // space: neither is written while the kernel runs)
+    const __attribute__((address_space(4))) u32* tp = (const __attribute__((address_space(4))) u32*)(tasksI + (uintptr_t)ti * sizeof(RzTask));
+    u32 T[32];
+#pragma unroll
+    for (int i = 0; i < 32; ++i) T[i] = tp[i];
+    uintptr_t l0f = 0;
+    if (L1) l0f = ((const __attribute__((address_space(4))) uintptr_t*)l0I)[full ? fq : 0u];
+    asm volatile("" : "+s"(T[0]), "+s"(T[1]), "+s"(T[2]), "+s"(T[3]), "+s"(T[4]), "+s"(T[5]), "+s"(T[6]), "+s"(T[7]), "+s"(T[8]), "+s"(T[9]),
+                 "+s"(T[10]), "+s"(T[11]), "+s"(T[12]), "+s"(l0f));
+    asm volatile("" : "+s"(T[17]), "+s"(T[18]), "+s"(T[19]), "+s"(T[20]), "+s"(T[21]), "+s"(T[22]), "+s"(T[23]), "+s"(T[24]), "+s"(T[25]), "+s"(T[26]),
+                 "+s"(T[27]));                                   // taps[1 .. RZ_SRC - 1]: source row 0 completes nothing
+    const int g0 = (int)T[0], y0 = (int)T[1], pack = (int)T[2], gw = (int)T[3], gmul = (int)T[4], sFirst = (int)T[5], nsrc = (int)T[6];
+    const u32 emit = T[7];
+    const int dpitch = (int)T[8], doff = (int)T[9], x4base = (int)T[10], spitch = (int)T[11], soff = (int)T[12];
+    const int sp = L1 ? l0pitch : spitch;
+    // lane -> (frame k of the wave's group, column c of the tile); a lane without a frame works on (0, 0) and never stores
+    u32 k = (lane * (u32)gmul) >> 16;                                      // lane / gw, exact for lane < 64
+    u32 c = lane - k * (u32)gw;
+    const u32 f0 = full ? fq : fq * (u32)pack;
+    const bool act = k < (u32)pack && f0 + k < P.nimg;
+    if (!act) { k = 0; c = 0; }
+    const u32 gcol = (u32)g0 + c;
+    const RzX4 X = rz_x4_load(x4I, (u32)x4base + gcol);
+    // the 8-byte window never leaves the row's pitch: near the right edge it slides left and the selectors follow
+    const int bsc = min(X.bs, sp - 8);
+    const u32 delta = (u32)(X.bs - bsc);                      // 0..6; every tap index + delta stays <= 7 (taps lie inside the row)
+    u32 sel[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sel[i] = 0x0c000c00u | ((u32)X.o[i] + delta) | (((u32)X.o[i] + delta + 1u) << 16);
+    const u32 xa[4] = {X.a[0], X.a[1], X.a[2], X.a[3]};
+    const u32 fo = k * (u32)pyrFrameBytes;                    // the lane's slab from the slab of frame f0 (k = 0 unless the host packs)
+    u8* slab = pyr + (size_t)f0 * pyrFrameBytes;
+    u8* dst = slab + doff;
+    const u32 dcol = fo + gcol * 4u;
+    if (L1 && !full) {
+        const u8* p = (const u8*)((const __attribute__((address_space(1))) uintptr_t*)l0I)[f0 + k];
+        rz_rows<1>(nullptr, p + bsc, 0u, sp, sFirst, nsrc, emit, T, xa, sel, dst, dcol, dpitch, y0, act);
+    } else {
+        const u8* src = L1 ? (const u8*)l0f : slab + soff;
+        rz_rows<0>(src, nullptr, (L1 ? 0u : fo) + (u32)bsc, sp, sFirst, nsrc, emit, T, xa, sel, dst, dcol, dpitch, y0, act);
+    }
+}
+
+#ifdef ORBX_AB   /* k_resize2p: A/B reference (8-row tasks of one frame, row taps reloaded per row), not in the product library */
+#define RZP_R 8
+#define RZP_SRC 12                                         // source rows one task may touch (host checks)
+struct RzTaskP { short level, g0, y0, pad; };
+
+__global__ __launch_bounds__(256) void k_resize2p(Geom g, const u8* const* l0, int l0pitch, u8* pyr,
+                                                  const RzTaskP* __restrict__ tasks, int ntasks,
+                                                  const RzX4* __restrict__ x4, const RzTab* __restrict__ yt) {
     const int lane = threadIdx.x & 63;
     const int ti = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ti >= ntasks) return;
-    RzTask t = tasks[ti];
+    RzTaskP t = tasks[ti];
     const int level = __builtin_amdgcn_readfirstlane(t.level);
     const int g0 = __builtin_amdgcn_readfirstlane(t.g0), y0 = __builtin_amdgcn_readfirstlane(t.y0);
     const int frame = blockIdx.y;
@@ -222,20 +377,20 @@ __global__ __launch_bounds__(256) void k_resize2(Geom g, const u8* const* l0, in
 #pragma unroll
     for (int i = 0; i < 4; ++i) sel[i] = 0x0c000c00u | ((u32)X.o[i] + delta) | (((u32)X.o[i] + delta + 1u) << 16);
     const u32 colo = (u32)bsc;
-    const int yend = min(y0 + RZ_R, D.h);
+    const int yend = min(y0 + RZP_R, D.h);
     const int sFirst = yt[D.rzy + y0].s;
-    const int nsrc = yt[D.rzy + yend - 1].s + 2 - sFirst;               // host guarantees 0 <= s, s+1 < S.h, nsrc <= RZ_SRC
+    const int nsrc = yt[D.rzy + yend - 1].s + 2 - sFirst;               // host guarantees 0 <= s, s+1 < S.h, nsrc <= RZP_SRC
     // all source rows of the task in flight before any arithmetic
-    uint2 d[RZ_SRC];
+    uint2 d[RZP_SRC];
 #pragma unroll
-    for (int j = 0; j < RZ_SRC; ++j) {
+    for (int j = 0; j < RZP_SRC; ++j) {
         d[j] = make_uint2(0, 0);
         if (j < nsrc) d[j] = gload64u_unaligned(src, (u32)((sFirst + j) * sp) + colo);     // level base + 32-bit offset (row part is wave-uniform)
     }
     int Hp[4] = {0, 0, 0, 0};
     int dy = y0;
 #pragma unroll
-    for (int j = 0; j < RZ_SRC; ++j) {
+    for (int j = 0; j < RZP_SRC; ++j) {
         if (j < nsrc) {
             int Hc[4];
 #pragma unroll
@@ -256,7 +411,7 @@ __global__ __launch_bounds__(256) void k_resize2(Geom g, const u8* const* l0, in
                     for (int i = 0; i < 4; ++i) sum[i] = mulhi24(A0, (u32)Hp[i]) + mulhi24(A1, (u32)Hc[i]) + 2u;
                     // each term is <= 1020, so (sum + 2) >> 2 <= 255: cv::resize's saturate_cast is the identity here.  gfx950's
                     // v_ashr_pk_u8_i32 shifts two sums and packs them as two bytes in one instruction (tools/ubench/isa_probe.hip)
-                    const u32 packed = ashr_pk_u8(sum[0], sum[1], 2u) | (ashr_pk_u8(sum[2], sum[3], 2u) << 16);
+                    const u32 packed = pack2x16(ashr_pk_u8(sum[0], sum[1], 2u), ashr_pk_u8(sum[2], sum[3], 2u));
                     if (act) gstore32u(dst, (u32)(dy * D.pitch) + (u32)gcol * 4u, packed);
                     ++dy;
                 }
@@ -266,6 +421,7 @@ __global__ __launch_bounds__(256) void k_resize2(Geom g, const u8* const* l0, in
         }
     }
 }
+#endif  /* ORBX_AB */
 
 // ------------------------------------------------------------------------------------------------
 // FAST-9/16 score  S = max(A,B) - 1  (cv::cornerScore<16>), branch-free:
