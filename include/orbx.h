@@ -109,6 +109,10 @@ int orbx_blur_in_pass(const orbx_t*);
 /* workgroup size the quadtree of the most recent batch was enqueued with: 1024 or 256 (k_quadtree2 takes the wide form when some
  * level wants >= 512 nodes or frames * levels <= 512), 0 for the first-generation kernel of the A/B library, -1 before any batch. */
 int orbx_quadtree_threads(const orbx_t*);
+/* form the Gaussian blur of the most recent batch was enqueued in: 0 = k_blur3 with one 26-row tile per workgroup (small batches,
+ * the single-frame call), 1 = k_blur3 walking chunks of up to 8 tiles (frames * walk tasks >= 2048), 2 = k_blur2 (the VALU kernel
+ * of the A/B library), -1 before any batch. */
+int orbx_blur_form(const orbx_t*);
 /* stage-boundary events are optional: with `on` = 0 only the dependency events are recorded (a few microseconds less per
  * batch); orbx_last_timings / orbx_mean_timings then fill ms8[6] (total), ms8[7] (the pass: to the later of FAST and an in-pass blur)
  * and ms8[1] (first launch -> end of the last FAST launch, i.e. pyramid+FAST without the blur's tail) and zero the rest.

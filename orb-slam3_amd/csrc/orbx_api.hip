@@ -102,6 +102,8 @@ struct orbx {
     bool qtWide = false;                                       // 1024-thread quadtree workgroups (large frames / feature counts)
     int qtWideForce = -1;                                      // ORBX_QT_WIDE=0/1: A/B switch
     int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
+    int blurFormLast = -1;                                     // orbx_blur_form: likewise (0 one-tile k_blur3, 1 walking k_blur3, 2 k_blur2)
+    int blurWalkForce = -1;                                    // ORBX_BLUR_WALK (A/B): 0 / 1 forces k_blur3's one-tile / walking form
     // device
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;
@@ -794,6 +796,7 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     if (const char* e = ab_env("ORBX_QT_WIDE")) o->qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
     o->blurTiled = !o->blurV2 && !o->odV1 && ab_env("ORBX_BLUR_ROWMAJOR") == nullptr;
+    if (const char* e = ab_env("ORBX_BLUR_WALK")) o->blurWalkForce = atoi(e) != 0 ? 1 : 0;
     o->dlKernel = ab_env("ORBX_DL_KERNEL") != nullptr;          // A/B: results-to-host copy by k_copy_out instead of the copy engine
     if (const char* e = ab_env("ORBX_DL_GRID")) o->dlGrid = std::max(1, atoi(e));
     if (const char* e = ab_env("ORBX_ONE_GRAPH")) o->oneOff = atoi(e) == 0;   // A/B: single-frame calls stay eager
@@ -1065,13 +1068,15 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     // blur (VALU + HBM) runs beside the quadtree (LDS-latency bound), not beside FAST (VALU bound)
     if (!o->serial && !o->blurEarly) HIPCHK(hipStreamWaitEvent(s1, dep_ev(o, 2), 0));
     STAGE_EV(11, s1);
-    if (o->blurV2)
+    if (o->blurV2) {
+        o->blurFormLast = 2;
         AB_LAUNCH(k_blur2, dim3((unsigned)(o->tiles.size() + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                   o->dTiles, (int)o->tiles.size(), o->blurSel);
-    else {
+    } else {
         // big batches: workgroups walk B3_CHUNK tiles (prologue amortised); small ones: one tile per workgroup (8x the workgroups,
         // an eighth of the latency -- the single-frame path)
-        const bool walk = (size_t)nimg * o->nTiles3Walk >= 2048;
+        const bool walk = o->blurWalkForce >= 0 ? o->blurWalkForce != 0 : (size_t)nimg * o->nTiles3Walk >= 2048;
+        o->blurFormLast = walk ? 1 : 0;
         const size_t first = walk ? 0 : o->nTiles3Walk, count = walk ? o->nTiles3Walk : o->tiles3.size() - o->nTiles3Walk;
         hipLaunchKernelGGL(k_blur3, dim3((unsigned)count, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                            o->dTiles3 + first, (const uint4*)o->dB3Th, (const uint4*)o->dB3Tv);
@@ -1732,6 +1737,7 @@ int orbx_mean_timings(orbx_t* o, float* ms8, int* nsamples) {
 
 int orbx_blur_in_pass(const orbx_t* o) { return o && o->blurEarly && !o->serial ? 1 : 0; }
 int orbx_quadtree_threads(const orbx_t* o) { return o ? o->qtThreadsLast : -1; }
+int orbx_blur_form(const orbx_t* o) { return o ? o->blurFormLast : -1; }
 
 int orbx_set_stage_timing(orbx_t* o, int on) {
     if (!o) return ORBX_E_INVALID;

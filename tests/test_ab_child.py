@@ -24,7 +24,7 @@ def test_product_library_has_no_ab_switches():
     """Not even the names: the switches are compiled out of liborbslam3_amd.so (csrc: ab_env / AB_LAUNCH), present in the _ab build."""
     names = [b"ORBX_FAST_V1", b"ORBX_QT_V1", b"ORBX_OD_V1", b"ORBX_BLUR_V2", b"ORBX_FAST_V3", b"ORBX_FAST_QCAP", b"ORBX_SERIAL",
              b"ORBM_KNN2_VALU", b"ORBM_WINDOW_CAP", b"ORBX_DL_KERNEL", b"ORBM_TOPK_WAVE", b"ORBM_CLAIM_V1", b"ORBX_BLUR_LATE",
-             b"ORBX_FAST_WGS"]
+             b"ORBX_FAST_WGS", b"ORBX_BLUR_WALK"]
     prod = open(os.path.join(ROOT, "orb-slam3_amd", "liborbslam3_amd.so"), "rb").read()
     ab = open(AB_LIB, "rb").read()
     for n in names:
