@@ -113,6 +113,10 @@ int orbx_quadtree_threads(const orbx_t*);
  * the single-frame call), 1 = k_blur3 walking chunks of up to 8 tiles (frames * walk tasks >= 2048), 2 = k_blur2 (the VALU kernel
  * of the A/B library), -1 before any batch. */
 int orbx_blur_form(const orbx_t*);
+/* form the orientation and descriptor kernel of the most recent batch was enqueued in: 0 = k_orient_desc2 reading the blurred levels
+ * as 16 x 8-px tiles, 1 = k_orient_desc2 reading them row-major (ORBX_BLUR_ROWMAJOR / ORBX_BLUR_V2 of the A/B library), 2 =
+ * k_orient_desc (one wavefront per keypoint, A/B library), -1 before any batch. */
+int orbx_orient_form(const orbx_t*);
 /* stage-boundary events are optional: with `on` = 0 only the dependency events are recorded (a few microseconds less per
  * batch); orbx_last_timings / orbx_mean_timings then fill ms8[6] (total), ms8[7] (the pass: to the later of FAST and an in-pass blur)
  * and ms8[1] (first launch -> end of the last FAST launch, i.e. pyramid+FAST without the blur's tail) and zero the rest.

@@ -103,6 +103,7 @@ struct orbx {
     int qtWideForce = -1;                                      // ORBX_QT_WIDE=0/1: A/B switch
     int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
     int blurFormLast = -1;                                     // orbx_blur_form: likewise (0 one-tile k_blur3, 1 walking k_blur3, 2 k_blur2)
+    int orientFormLast = -1;                                   // orbx_orient_form: likewise (0 k_orient_desc2 on tiles, 1 k_orient_desc2 on row-major levels, 2 k_orient_desc)
     int blurWalkForce = -1;                                    // ORBX_BLUR_WALK (A/B): 0 / 1 forces k_blur3's one-tile / walking form
     // device
     hipStream_t stream = nullptr;
@@ -1110,6 +1111,7 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     STAGE_EV(4, st);
     HIPCHK(hipStreamWaitEvent(st, dep_ev(o, 9), 0));
     STAGE_EV(5, st);
+    o->orientFormLast = o->odV1 ? 2 : g.blurTiled ? 0 : 1;
     if (o->odV1)
         AB_LAUNCH(k_orient_desc, dim3((g.kpCap + 3) / 4, nimg), dim3(256), 0, st, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                   o->dWork, o->dN, o->dKps, o->dDesc, o->dPattern, o->umax);
@@ -1738,6 +1740,7 @@ int orbx_mean_timings(orbx_t* o, float* ms8, int* nsamples) {
 int orbx_blur_in_pass(const orbx_t* o) { return o && o->blurEarly && !o->serial ? 1 : 0; }
 int orbx_quadtree_threads(const orbx_t* o) { return o ? o->qtThreadsLast : -1; }
 int orbx_blur_form(const orbx_t* o) { return o ? o->blurFormLast : -1; }
+int orbx_orient_form(const orbx_t* o) { return o ? o->orientFormLast : -1; }
 
 int orbx_set_stage_timing(orbx_t* o, int on) {
     if (!o) return ORBX_E_INVALID;
