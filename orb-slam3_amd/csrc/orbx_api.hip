@@ -1,6 +1,6 @@
 // orbx_api.hip -- C ABI (include/orbx.h) over the gfx950 extractor kernels.
-// Host side: replays the reference constructor tables and per-image geometry in the same float arithmetic
-// (ORBextractor.cc:468-571, 1038-1106, 1664-1672), owns the device-resident pyramid/scratch, launches the
+// Host side: has orbx_plan.h replay the reference constructor tables and per-image geometry in the same float arithmetic
+// (ORBextractor.cc:468-571, 1038-1106, 1664-1672), uploads the plan, owns the device-resident pyramid/scratch, launches the
 // pipeline on one HIP stream.  No CPU fallback: every failure surfaces as ORBX_E_*.
 #include "../../include/orbx.h"
 #include "orbx_kernels.hip.h"
@@ -12,9 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <condition_variable>
-#include <array>
 #include <deque>
-#include <map>
 #include <dlfcn.h>
 #include "hsa_copy.h"
 #include <chrono>
@@ -47,60 +45,25 @@ static inline const char* ab_env(const char*) { return nullptr; }
 #define AB_LAUNCH(...) ((void)0)                              /* (the flag that guards the call is never set in this build) */
 #endif
 
-static inline int cv_round_f(float v) { return (int)lrintf(v); }
-static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
-
 struct orbx {
-    int nfeatures, nlevels, iniTh, minTh, device, maxW, maxH, maxBatch;
-    double scaleFactor;
-    std::vector<float> sf, invsf, sig2, invsig2;
-    std::vector<int> nfeat;
-    Umax umax;
-    // geometry of the current image size
+    int device;
+    PlanConfig cfg;                                           // what orbx_create was given, and the planner's A/B knobs
+    ExtractorTables tab;                                      // the reference constructor's tables
+    // geometry of the current image size (0 x 0: none), planned on the host by orbx_plan.h
     int curW = 0, curH = 0;
-    Geom g;
-    std::vector<CellInfo> cells;
-    std::vector<BlurTask> tiles;
-    std::vector<Blur3Task> tiles3;                            // k_blur3 (matrix-core blur) tasks: B3_CHUNK-tile walks, then one-tile tasks
-    size_t nTiles3Walk = 0;                                   // (small batches take the one-tile list: more, shorter workgroups)
-    std::vector<u32> b3Th, b3Tv;                              // its weight fragments: [strip][2][64][4], [tile row][64][4]
-    BlurSel blurSel;
-    std::vector<StripInfo> strips;
+    Plan plan;
     StripInfo* dStrips = nullptr; size_t capStrips = 0;
-    std::vector<CellAux> aux; std::vector<F4Item> f4items;    // k_fast4: per-cell scalars and per-shape item tables
     CellAux* dAux = nullptr; size_t capAux = 0;
     F4Item* dF4Items = nullptr; size_t capF4Items = 0;
-    bool fastV3 = false;                                      // ORBX_FAST_V3: A/B, k_fast3 instead of k_fast4
     bool fastV4p = false;                                     // ORBX_FAST_V4P: A/B, k_fast4p (register-staged tile, separate store pass) instead of k_fast4
     bool fastV1 = false;
-    // k_fast3 launch groups: level 0 (needs no resize), the fine levels, the coarse levels.  Each group sizes its own LDS
-    // (tile of its tallest cell row + survivor queues), because occupancy -- 20 vs 28 waves per CU -- is worth ~15 %.
-    struct F3Group { int strip0 = 0, nstrips = 0, tile = 0, qcap = 0, lastLevel = 0, pitch = 0; size_t lds = 0; bool v4 = false; };   // pitch: 176 / 208 = compile-time tile pitch of the group, 0 = per strip
     hipEvent_t evLvl[12] = {};                                // "pyramid level l is resized" for the levels that end a FAST group
-    std::vector<F3Group> f3g;
-    std::vector<int> stripTile, stripQ;                       // per strip: tile bytes, worst-case queue entries
-    std::vector<RzTab> xt, yt;
-    std::vector<RzX4> x4;
-    std::vector<RzTask> rzTasks[12];                          // per level: the full-tile tasks, then the packed remainder tasks
     RzX4* dX4 = nullptr; RzTask* dRzTasks = nullptr; size_t capX4 = 0, capRzTasks = 0;
-    int rzTaskOff[12] = {}; bool rzStream[12] = {};
-    int rzNFull[12] = {}, rzNPack[12] = {}, rzPack[12] = {};  // task counts of the two kinds; frames per wave of the packed kind
 #ifdef ORBX_AB
-    bool rzNoPack = false;                                    // ORBX_RESIZE_NOPACK: A/B, one frame per wave everywhere (the form of a slab too large for 32-bit lane offsets)
     bool rzV2p = false;                                       // ORBX_RESIZE_V2P: A/B, k_resize2p (8-row tasks of one frame) instead of k_resize2
-    std::vector<RzTaskP> rzTasksP[12];
     RzTaskP* dRzTasksP = nullptr; size_t capRzTasksP = 0;
-    int rzTaskOffP[12] = {}; bool rzStreamP[12] = {};
 #endif
-    int64_t algBytes = 0, fusedBytes = 0;
-    size_t qtLds = 0, qt2Lds = 0;
-    int qtFuseD = 3;
-    int maxIni = 1;                                            // most quadtree roots of any level
-    int qt2Cap = 0, qt2Sort = 0;
     bool qtV1 = false, odV1 = false, serial = false, blurV2 = false, blurEarly = true;
-    bool blurTiled = true;                                     // k_blur3 writes / k_orient_desc2 reads the blurred levels as 16 x 8-px tiles (ORBX_BLUR_ROWMAJOR: A/B)
-    bool qtWide = false;                                       // 1024-thread quadtree workgroups (large frames / feature counts)
-    int qtWideForce = -1;                                      // ORBX_QT_WIDE=0/1: A/B switch
     int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
     int blurFormLast = -1;                                     // orbx_blur_form: likewise (0 one-tile k_blur3, 1 walking k_blur3, 2 k_blur2)
     int orientFormLast = -1;                                   // orbx_orient_form: likewise (0 k_orient_desc2 on tiles, 1 k_orient_desc2 on row-major levels, 2 k_orient_desc)
@@ -161,7 +124,6 @@ struct orbx {
     u32 *dCandCnt = nullptr, *dCandEnt = nullptr, *dSel = nullptr, *dSelCnt = nullptr;
     u16* dKpNode = nullptr;
     u32* dDense = nullptr;
-    int maxCells = 0;
     KpOut* dKps = nullptr; u8* dDesc = nullptr; KpWork* dWork = nullptr;
     int *dN = nullptr, *dMono = nullptr, *dLap = nullptr, *dErr = nullptr;
     bool stageTiming = true;                                   // record the stage-boundary events (orbx_set_stage_timing)
@@ -174,13 +136,11 @@ struct orbx {
     u8* hOne = nullptr; size_t capOne = 0;                    // pinned landing buffer of the single-frame call (k_fetch_one)
     u32 *dOvf = nullptr, *dOvfList = nullptr;                  // k_fast3 queue overflow list -> k_fast_fix
     size_t capOvfList = 0;
-    int f3QcapForce = 0;                                       // ORBX_FAST_QCAP: test knob, forces a small queue
-    bool f3NoFixedPitch = false;                               // ORBX_FAST_PITCH0: A/B, every group on the per-strip-pitch kernel
     int8_t* dPattern = nullptr;
     u32* dOdW = nullptr;                                       // IC_Angle byte weights (k_orient_desc2)
     size_t capL0 = 0, capPyr = 0, capCells = 0, capTiles = 0, capXt = 0, capYt = 0, capCandCnt = 0, capCandEnt = 0, capSel = 0;
     int lastBatch = 0;
-    int l0pitch = 0, lastL0Pitch = 0;
+    int lastL0Pitch = 0;
     std::vector<const u8*> hL0Ptr;
     bool l0Staged = false;                                     // the last batch's level 0 was uploaded FROM hPinned (host images): its host copy is still there
     std::vector<int> hLap;
@@ -200,10 +160,10 @@ template <class T> static int ensure(T** p, size_t* cap, size_t need) {
     return 0;
 }
 
-// ---- geometry (replays ORBextractor.cc:1669, 1053-1106, 695-699 in the reference's float arithmetic)
+// ---- geometry: the plan of the image size (orbx_plan.h), its device tables and the function attributes its LDS sizes need
 static int build_geometry(orbx* o, int w, int h) {
     if (o->curW == w && o->curH == h) return 0;
-    if (w > o->maxW || h > o->maxH) { set_err("image %dx%d exceeds the configured maximum %dx%d", w, h, o->maxW, o->maxH); return ORBX_E_CAPACITY; }
+    if (w > o->cfg.maxW || h > o->cfg.maxH) { set_err("image %dx%d exceeds the configured maximum %dx%d", w, h, o->cfg.maxW, o->cfg.maxH); return ORBX_E_CAPACITY; }
     if (o->capSlot >= 0) { set_err("the image size must not change while a graph is being captured"); return ORBX_E_INVALID; }
     // Everything below tears the current geometry down before it can fail (too small / unsupported / out of memory): mark the
     // handle as having NO geometry first, so that a failed rebuild can never be mistaken for a valid one by the next call
@@ -218,307 +178,37 @@ static int build_geometry(orbx* o, int w, int h) {
     o->oneW = o->oneH = 0; o->oneEager = 0;
     o->upPtr.clear(); o->upLap.clear();
     for (auto& v : o->attach) v.clear();                       // the block layout is about to change
-    Geom& g = o->g;
-    memset(&g, 0, sizeof g);
-    const int L = o->nlevels;
-    g.nlevels = L; g.w0 = w; g.h0 = h; g.iniTh = o->iniTh; g.minTh = o->minTh; g.lowTh = std::min(o->iniTh, o->minTh);
-    std::vector<Blur3Task> tiles3one;                         // one-tile k_blur3 tasks, appended behind the walks
-    o->cells.clear(); o->tiles.clear(); o->tiles3.clear(); o->b3Th.clear(); o->b3Tv.clear(); o->strips.clear(); o->f3g.clear(); o->stripTile.clear(); o->stripQ.clear(); o->xt.clear(); o->yt.clear(); o->x4.clear(); for (auto& v : o->rzTasks) v.clear();
-#ifdef ORBX_AB
-    for (auto& v : o->rzTasksP) v.clear();
-#endif
-    size_t off = 0, boff = 0;
-    int totalSlots = 0, totalSel = 0, maxN = 0;
-    int64_t sumAll = 0, sumSrc = 0, sumDst = 0;
-    for (int l = 0; l < L; ++l) {
-        LevelDesc& D = g.lv[l];
-        const float scale = o->invsf[l];
-        D.w = cv_round_f((float)w * scale); D.h = cv_round_f((float)h * scale);
-        if (D.w > 4095 || D.h > 4095) { set_err("level %d is %dx%d: packed candidates hold 12-bit coordinates", l, D.w, D.h); return ORBX_E_UNSUPPORTED; }
-        D.pitch = align_up(D.w, 64);
-        D.off = (int)off;
-        off += (size_t)align_up(D.pitch * D.h, 256);
-        // blurred copy: row-major twin of the level, or 16 x 8-px tiles (one more tile per tile row than the pitch needs: the
-        // descriptor kernel's 48-byte patch rows may start up to 10 bytes before the right edge)
-        D.btpr = D.pitch / 16 + 1;
-        D.boff = o->blurTiled ? (int)boff : D.off;
-        boff += (size_t)align_up(D.btpr * ((D.h + 7) / 8) * 128, 256);
-        D.sf = o->sf[l];
-        D.patch = (float)(int)(31 * o->sf[l]);
-        D.N = o->nfeat[l];
-        sumAll += (int64_t)D.w * D.h;
-        if (l < L - 1) sumSrc += (int64_t)D.w * D.h;
-        if (l > 0) sumDst += (int64_t)D.w * D.h;
-        // FAST cell grid
-        const int minB = 16, maxBX = D.w - 16, maxBY = D.h - 16;
-        const float width = (float)(maxBX - minB), height = (float)(maxBY - minB);
-        const float W = 35;
-        const int nCols = (int)(width / W), nRows = (int)(height / W);
-        if (nCols < 1 || nRows < 1) { set_err("level %d (%dx%d) is smaller than one FAST cell", l, D.w, D.h); return ORBX_E_TOO_SMALL; }
-        const int wCell = (int)std::ceil(width / nCols), hCell = (int)std::ceil(height / nRows);
-        D.cellBase = (int)o->cells.size();
-        D.slotBase = totalSlots;
-        D.slotCap = ((wCell + 1) / 2) * ((hCell + 1) / 2);
-        for (int i = 0; i < nRows; ++i) {
-            const float iniY = (float)(minB + i * hCell);
-            float maxY = iniY + hCell + 6;
-            if (iniY >= maxBY - 3) continue;
-            if (maxY > maxBY) maxY = (float)maxBY;
-            for (int j = 0; j < nCols; ++j) {
-                const float iniX = (float)(minB + j * wCell);
-                float maxX = iniX + wCell + 6;
-                if (iniX >= maxBX - 6) continue;
-                if (maxX > maxBX) maxX = (float)maxBX;
-                CellInfo c;
-                c.level = (short)l; c.x0 = (short)iniX; c.y0 = (short)iniY;
-                c.cw = (short)((int)maxX - (int)iniX); c.ch = (short)((int)maxY - (int)iniY);
-                c.addx = (short)(j * wCell); c.addy = (short)(i * hCell); c.pad = 0;
-                c.cnt = (int)o->cells.size();
-                c.slot = totalSlots;
-                if ((int)c.cw * c.ch > ORBX_FAST_TILE) { set_err("FAST cell %dx%d exceeds the LDS tile", c.cw, c.ch); return ORBX_E_UNSUPPORTED; }
-                totalSlots += D.slotCap;
-                o->cells.push_back(c);
-            }
-        }
-        D.nCells = (int)o->cells.size() - D.cellBase;
-        // strips for k_fast3: runs of <= 8 cells of one cell-row (one wavefront per cell); the tile pitch is a
-        // multiple of 16 bytes (<= 512) and starts >= 4 bytes left of the strip at a 16-byte aligned column
-        for (int ci = D.cellBase; ci < (int)o->cells.size();) {
-            const CellInfo& f = o->cells[ci];
-            const int Hs = f.ch;
-            if (Hs > 127) { set_err("FAST cell of %d rows exceeds the strip kernel's 127", Hs); return ORBX_E_UNSUPPORTED; }
-            const int xal = (f.x0 - 4) & ~15;
-            int n = 0, needed = 0;
-            while (ci + n < (int)o->cells.size() && n < F3_NT / 64) {
-                const CellInfo& c = o->cells[ci + n];
-                if (c.y0 != f.y0) break;
-                const int nd = c.x0 + c.cw - 3 - xal + 8;
-                if (nd > 512) break;
-                needed = nd; ++n;
-            }
-            if (n == 0) { set_err("FAST cell %dx%d does not fit the strip tile", f.cw, f.ch); return ORBX_E_UNSUPPORTED; }
-            const CellInfo& last = o->cells[ci + n - 1];
-            StripInfo st;
-            st.level = (short)l; st.ncell = (short)n; st.x0 = f.x0; st.y0 = f.y0;
-            st.w = (short)(last.x0 + last.cw - f.x0); st.h = (short)Hs; st.xal = (short)xal;
-            st.lp = (short)align_up(needed, 16); st.cell0 = ci;
-            int qworst = 64;
-            for (int k = 0; k < n; ++k) {
-                const CellInfo& c = o->cells[ci + k];
-                qworst = std::max(qworst, align_up(std::max(0, c.cw - 6) * std::max(0, c.ch - 6), 64));
-            }
-            o->stripTile.push_back((int)st.lp * Hs); o->stripQ.push_back(qworst);
-            o->strips.push_back(st);
-            ci += n;
-        }
-        if (totalSlots - D.slotBase >= (1 << 24)) { set_err("level %d has too many candidate slots", l); return ORBX_E_UNSUPPORTED; }
-        // quadtree roots (ORBextractor.cc:695-699)
-        D.qtW = maxBX - minB; D.qtH = maxBY - minB;
-        D.nIni = (int)std::round(static_cast<float>(D.qtW) / D.qtH);
-        if (D.nIni < 1 || D.nIni > 16) { set_err("aspect ratio of level %d unsupported (nIni=%d; the reference divides by zero for nIni=0)", l, D.nIni); return ORBX_E_UNSUPPORTED; }
-        D.hX = static_cast<float>(D.qtW) / D.nIni;
-        D.selBase = totalSel;
-        D.selCap = std::max(D.N + 3, 4 * D.nIni) + 1;
-        totalSel += D.selCap;
-        maxN = std::max(maxN, std::max(D.N, 4 * D.nIni));
-        // blur tasks: one wavefront per (248-px column strip, BL_R-row block); right-edge reflect-101 selectors
-        {   // strips of output dwords: the first stores from lane 0 (63 dwords), the others from lane 1 (62), and a strip whose
-            // lane 63 is the image's last dword stores that one too (k_blur2's doStore)
-            const int gl = (D.w - 1) >> 2;
-            for (int ty = 0; ty < D.h; ty += BL_R)
-                for (int g0 = 0; g0 <= gl;) {
-                    o->tiles.push_back(BlurTask{(short)l, (short)g0, (short)ty, 0});
-                    const int lead = g0 > 0 ? 1 : 0;
-                    int lastOut = g0 - lead + 62;
-                    if (g0 - lead + 63 == gl) lastOut = gl;
-                    g0 = lastOut + 1;
-                }
-        }
-        {   // k_blur3: one wavefront per 32-px column strip and chunk of up to B3_CHUNK 26-row tiles; weight fragments per
-            // strip (pass 1, reflect-101 folded at the left / right edge) and per tile row (pass 2, folded at top / bottom)
-            const int ntile = (D.h + B3_ROWS - 1) / B3_ROWS, nstrip = (D.w + 31) / 32;
-            const int th0 = (int)(o->b3Th.size() / 512), tv0 = (int)(o->b3Tv.size() / 256);
-            o->b3Th.resize(o->b3Th.size() + (size_t)nstrip * 512);
-            o->b3Tv.resize(o->b3Tv.size() + (size_t)ntile * 256);
-            for (int sx = 0; sx < nstrip; ++sx) b3_build_th(sx * 32, D.w, o->b3Th.data() + (size_t)(th0 + sx) * 512);
-            for (int t = 0; t < ntile; ++t) b3_build_tv(t * B3_ROWS, D.h, o->b3Tv.data() + (size_t)(tv0 + t) * 256);
-            for (int t0 = 0; t0 < ntile; t0 += B3_CHUNK)
-                for (int sx = 0; sx < nstrip; sx += 4)                  // a workgroup = four adjacent strips
-                    o->tiles3.push_back(Blur3Task{(short)l, (short)(sx * 32), (short)t0, (short)std::min(B3_CHUNK, ntile - t0), th0 + sx, tv0 + t0});
-            for (int t0 = 0; t0 < ntile; ++t0)
-                for (int sx = 0; sx < nstrip; sx += 4)
-                    tiles3one.push_back(Blur3Task{(short)l, (short)(sx * 32), (short)t0, 1, th0 + sx, tv0 + t0});
-        }
-        {
-            static const u32 kSelB[4] = {0x05060700u, 0x07000100u, 0x01020100u, 0x03020100u};   // k = (w-1)&3 valid bytes-1
-            static const u32 kSelC[4] = {0x04040404u, 0x04040506u, 0x05060700u, 0x07000102u};
-            const int k = (D.w - 1) & 3;
-            o->blurSel.selB[l] = kSelB[k]; o->blurSel.selC[l] = kSelC[k];
-        }
-        // resize taps from level l-1
-        D.rzx = (int)o->xt.size(); D.rzy = (int)o->yt.size();
-        if (l > 0) {
-            const LevelDesc& S = g.lv[l - 1];
-            const double scale_x = 1.0 / ((double)D.w / S.w), scale_y = 1.0 / ((double)D.h / S.h);
-            auto sat = [](float v) { int r = (int)lrintf(v); return (short)std::min(32767, std::max(-32768, r)); };
-            for (int dx = 0; dx < D.w; ++dx) {
-                float fx = (float)((dx + 0.5) * scale_x - 0.5);
-                int sx = (int)floorf(fx);
-                fx -= sx;
-                if (sx < 0) { fx = 0; sx = 0; }
-                if (sx >= S.w - 1) { fx = 0; sx = S.w - 1; }
-                o->xt.push_back(RzTab{sx, sat((1.f - fx) * 2048.f), sat(fx * 2048.f)});
-            }
-            for (int dy = 0; dy < D.h; ++dy) {
-                float fy = (float)((dy + 0.5) * scale_y - 0.5);
-                int sy = (int)floorf(fy);
-                fy -= sy;
-                o->yt.push_back(RzTab{sy, sat((1.f - fy) * 2048.f), sat(fy * 2048.f)});
-            }
-            // per-dword tables of the streaming kernel: it loads 8 bytes from the first tap, so every tap pair must start
-            // within 6 bytes of it (true for scale factors up to 1.5; otherwise the level uses k_resize)
-            while (o->x4.size() * 4 < (size_t)D.rzx) o->x4.push_back(RzX4{});
-            bool ok = (D.rzx % 4) == 0 && S.w >= 8;
-            for (int gx = 0; gx * 4 < D.w && ok; ++gx) {
-                RzX4 e{};
-                int sx[4];
-                for (int i = 0; i < 4; ++i) {
-                    const int dx = std::min(gx * 4 + i, D.w - 1);
-                    const RzTab& tb = o->xt[D.rzx + dx];
-                    if (tb.s < 0 || tb.a0 < 0 || tb.a1 < 0) { ok = false; break; }
-                    if (tb.s + 1 < S.w) {
-                        sx[i] = tb.s;
-                        e.a[i] = (u32)(unsigned short)(2 * tb.a0) | ((u32)(unsigned short)(2 * tb.a1) << 16);   // doubled taps (<= 4096): k_resize2 keeps (H >> 4) << 5
-                    } else {                                           // clamped last column (a1 == 0): pair (w-2, w-1), weight on the second
-                        sx[i] = tb.s - 1;
-                        e.a[i] = (u32)(unsigned short)(2 * tb.a0) << 16;
-                    }
-                }
-                if (!ok) break;
-                e.bs = *std::min_element(sx, sx + 4);
-                for (int i = 0; i < 4; ++i) {
-                    const int off = sx[i] - e.bs;
-                    if (off < 0 || off > 6) { ok = false; break; }
-                    e.o[i] = (u8)off;
-                }
-                o->x4.push_back(e);
-            }
-            // rows: strictly increasing source rows without clamping, and a bounded source span per task
-            for (int dy = 0; dy < D.h && ok; ++dy) {
-                const int sy = o->yt[D.rzy + dy].s;
-                if (sy < 0 || sy + 1 >= S.h || (dy > 0 && sy <= o->yt[D.rzy + dy - 1].s)) ok = false;
-            }
-            auto span_ok = [&](int R, int nsrcMax) {
-                for (int ty = 0; ty < D.h; ty += R)
-                    if (o->yt[D.rzy + std::min(ty + R, D.h) - 1].s + 2 - o->yt[D.rzy + ty].s > nsrcMax) return false;
-                return true;
-            };
-#ifdef ORBX_AB
-            o->rzStreamP[l] = ok && span_ok(RZP_R, RZP_SRC);
-            if (o->rzStreamP[l])
-                for (int ty = 0; ty < D.h; ty += RZP_R)
-                    for (int gx = 0; gx * 4 < D.w; gx += 64) o->rzTasksP[l].push_back(RzTaskP{(short)l, (short)gx, (short)ty, 0});
-#endif
-            o->rzStream[l] = ok && span_ok(RZ_R, RZ_SRC);        // (its task records need the slab size: below)
-        }
-        while (o->xt.size() % 4) o->xt.push_back(RzTab{0, 0, 0});      // keep every level's tap offset a multiple of 4
-    }
-    g.pyrFrameBytes = off;
-    // k_resize2's task records.  A level of ndw dwords has ndw / 64 full column tiles (a wave per tile and frame) and, for the
-    // remainder r = ndw % 64, one packed tile whose wave serves 64 / r consecutive frames.  The lanes of a packed wave reach their
-    // frames' slabs by 32-bit offsets from the first one's, so packing needs 64 slabs within 4 GiB; otherwise the tile keeps a frame per wave.
-    for (int l = 1; l < L; ++l) {
-        o->rzNFull[l] = o->rzNPack[l] = 0; o->rzPack[l] = 1;
-        if (!o->rzStream[l]) continue;
-        const LevelDesc &D = g.lv[l], &S = g.lv[l - 1];
-        const int ndw = (D.w + 3) / 4, nfullTiles = ndw / 64, r = ndw % 64;
-        bool canPack = (uint64_t)off * 64 <= (1ull << 32);
-#ifdef ORBX_AB
-        if (o->rzNoPack) canPack = false;
-#endif
-        const int pack = r && canPack ? 64 / r : 1;
-        std::vector<RzTask> packed;
-        for (int ty = 0; ty < D.h; ty += RZ_R) {
-            RzTask t{};
-            const int ye = std::min(ty + RZ_R, D.h);
-            t.y0 = ty; t.sFirst = o->yt[D.rzy + ty].s; t.nsrc = o->yt[D.rzy + ye - 1].s + 2 - t.sFirst;
-            for (int dy = ty; dy < ye; ++dy) {
-                const RzTab& e = o->yt[D.rzy + dy];
-                const int j = e.s + 1 - t.sFirst;                 // >= 1, distinct per dy (source rows strictly increase), < nsrc <= RZ_SRC
-                t.emit |= 1u << j;
-                t.taps[j] = (u32)(unsigned short)e.a0 | ((u32)(unsigned short)e.a1 << 16);
-            }
-            t.dpitch = D.pitch; t.doff = D.off; t.x4base = D.rzx / 4; t.spitch = S.pitch; t.soff = S.off;
-            for (int tile = 0; tile < nfullTiles; ++tile) { t.g0 = tile * 64; t.pack = 1; t.gw = 64; t.gmul = 1024; o->rzTasks[l].push_back(t); }
-            if (r) { t.g0 = nfullTiles * 64; t.pack = pack; t.gw = r; t.gmul = (65536 + r - 1) / r; packed.push_back(t); }
-        }
-        o->rzNFull[l] = (int)o->rzTasks[l].size(); o->rzNPack[l] = (int)packed.size(); o->rzPack[l] = pack;
-        o->rzTasks[l].insert(o->rzTasks[l].end(), packed.begin(), packed.end());
-        // the kernel divides a wave's index by a task count with one high multiply, exact while index * count < 2^32
-        const uint64_t nmax = (uint64_t)o->rzTasks[l].size() * (uint64_t)o->maxBatch;
-        if (nmax * (uint64_t)std::max(o->rzNFull[l], o->rzNPack[l]) >= (1ull << 32)) { o->rzStream[l] = false; o->rzTasks[l].clear(); }
-    }
-    g.blurTiled = o->blurTiled ? 1 : 0;
-    g.blrFrameBytes = o->blurTiled ? boff : off;
-    g.totalCells = (int)o->cells.size();
-    g.totalSlots = totalSlots;
-    g.totalSel = totalSel;
-    g.kpCap = totalSel;
-    // maxN = max over the levels of max(N, 4 * nIni) (above): the first pass of DistributeOctTree splits every root before it looks at
-    // N, so a level ends with up to 4 * nIni nodes whatever its budget.  k_quadtree (the A/B kernel) keeps the parents of a pass until
-    // its end: at most nIni + 4 * nIni nodes in the first pass and N + (N + 3) later, both within 2 * maxN + 64 for every nIni
-    g.nodeCap = 2 * maxN + 64;
-    int sc = 1; while (sc < maxN + 8) sc <<= 1;
-    g.sortCap = sc;
-    if (g.nodeCap > 65000) { set_err("nfeatures per level %d too large for 16-bit node ids", maxN); return ORBX_E_UNSUPPORTED; }
-    o->qtLds = (size_t)g.sortCap * 8 + (size_t)g.nodeCap * 56 + 64;
-    {   // k_quadtree2: list capacity max(N+3, 4*nIni) (+slack), power-of-two sort buffer.  The 4 * nIni term is inside maxN, so a
-        // wide frame with a small budget (six roots, N = 11: 24 nodes after the first pass) fits: tests/test_gpu_extract_second_reading.py
-        o->qt2Cap = maxN + 8;
-        int sc2 = 1; while (sc2 < o->qt2Cap) sc2 <<= 1;
-        o->qt2Sort = sc2;
-        o->maxCells = 0;
-        for (int l = 0; l < L; ++l) o->maxCells = std::max(o->maxCells, g.lv[l].nCells);
-        o->qtWide = o->qtWideForce >= 0 ? o->qtWideForce != 0 : maxN >= 512;   // many features per level: 1024-thread workgroups
-        o->maxIni = 1;
-        for (int l = 0; l < L; ++l) o->maxIni = std::max(o->maxIni, g.lv[l].nIni);
-        // + the fused first iterations' histograms (4 + 16 + 64 (+ 256) words per root), path table and per-node paths.  A fourth fused
-        // iteration only happens when some level wants more than ~512 nodes (128 + 3 * 128 <= N), and 12 path bits hold 16 roots * 4^4 / 16
-        o->qtFuseD = (maxN >= 512 && o->maxIni <= 4) ? 4 : 3;
-        const size_t hw = o->qtFuseD == 4 ? 340 : 84, tw = o->qtFuseD == 4 ? 256 : 64;
-        o->qt2Lds = (size_t)sc2 * 8 + (size_t)o->qt2Cap * (16 * 2 + 16 + 4 + 4 + 8 + 2 + 1 + 1) + (size_t)(o->maxCells + 1) * 4 + 64 +
-                    (size_t)o->maxIni * (hw * 4 + tw * 2) + (size_t)o->qt2Cap * 4 + 8;
-        if (o->qt2Lds > 160 * 1024 - 512) { set_err("quadtree for %d features/level needs %zu B of LDS (> 160 KiB)", maxN, o->qt2Lds); return ORBX_E_UNSUPPORTED; }
-    }
-    if (o->qtLds > 160 * 1024 - 512) { set_err("quadtree for %d features/level needs %zu B of LDS (> 160 KiB)", maxN, o->qtLds); return ORBX_E_UNSUPPORTED; }
-    o->algBytes = sumSrc + sumDst + sumAll;      // read L0..L6 + write L1..L7 + read L0..L7
-    o->fusedBytes = sumSrc + sumDst;
-    o->l0pitch = align_up(w, 64);
-
-    const size_t B = (size_t)o->maxBatch;
-    if (ensure(&o->dPyr, &o->capPyr, off * B)) return ORBX_E_HIP;
-    { size_t c2 = 0; u8* old = o->dBlur; if (old) (void)hipFree(old); o->dBlur = nullptr; if (ensure(&o->dBlur, &c2, g.blrFrameBytes * B)) return ORBX_E_HIP; }
-    if (ensure(&o->dL0, &o->capL0, (size_t)o->l0pitch * h * B)) return ORBX_E_HIP;
-    if (ensure(&o->dCells, &o->capCells, o->cells.size())) return ORBX_E_HIP;
-    if (ensure(&o->dTiles, &o->capTiles, o->tiles.size())) return ORBX_E_HIP;
-    o->nTiles3Walk = o->tiles3.size();
-    o->tiles3.insert(o->tiles3.end(), tiles3one.begin(), tiles3one.end());
-    if (ensure(&o->dTiles3, &o->capTiles3, o->tiles3.size())) return ORBX_E_HIP;
-    if (ensure(&o->dB3Th, &o->capB3Th, o->b3Th.size())) return ORBX_E_HIP;
-    if (ensure(&o->dB3Tv, &o->capB3Tv, o->b3Tv.size())) return ORBX_E_HIP;
-    if (ensure(&o->dStrips, &o->capStrips, o->strips.size())) return ORBX_E_HIP;
-    if (ensure(&o->dXt, &o->capXt, std::max<size_t>(1, o->xt.size()))) return ORBX_E_HIP;
-    if (ensure(&o->dYt, &o->capYt, std::max<size_t>(1, o->yt.size()))) return ORBX_E_HIP;
     {
-        std::vector<RzTask> all;
-        for (int l = 0; l < L; ++l) { o->rzTaskOff[l] = (int)all.size(); all.insert(all.end(), o->rzTasks[l].begin(), o->rzTasks[l].end()); }
-        if (ensure(&o->dX4, &o->capX4, std::max<size_t>(1, o->x4.size()))) return ORBX_E_HIP;
+        char why[512];
+        const int rc = plan_geometry(o->cfg, o->tab, w, h, o->plan, why, sizeof why);
+        if (rc) { set_err("%s", why); return rc; }
+    }
+    const Plan& p = o->plan;
+    const Geom& g = p.g;
+    const int L = g.nlevels;
+
+    const size_t B = (size_t)o->cfg.maxBatch;
+    if (ensure(&o->dPyr, &o->capPyr, g.pyrFrameBytes * B)) return ORBX_E_HIP;
+    { size_t c2 = 0; u8* old = o->dBlur; if (old) (void)hipFree(old); o->dBlur = nullptr; if (ensure(&o->dBlur, &c2, g.blrFrameBytes * B)) return ORBX_E_HIP; }
+    if (ensure(&o->dL0, &o->capL0, (size_t)p.l0pitch * h * B)) return ORBX_E_HIP;
+    if (ensure(&o->dCells, &o->capCells, p.cells.size())) return ORBX_E_HIP;
+    if (ensure(&o->dTiles, &o->capTiles, p.tiles.size())) return ORBX_E_HIP;
+    if (ensure(&o->dTiles3, &o->capTiles3, p.tiles3.size())) return ORBX_E_HIP;
+    if (ensure(&o->dB3Th, &o->capB3Th, p.b3Th.size())) return ORBX_E_HIP;
+    if (ensure(&o->dB3Tv, &o->capB3Tv, p.b3Tv.size())) return ORBX_E_HIP;
+    if (ensure(&o->dStrips, &o->capStrips, p.strips.size())) return ORBX_E_HIP;
+    if (ensure(&o->dXt, &o->capXt, std::max<size_t>(1, p.xt.size()))) return ORBX_E_HIP;
+    if (ensure(&o->dYt, &o->capYt, std::max<size_t>(1, p.yt.size()))) return ORBX_E_HIP;
+    {
+        std::vector<RzTask> all;                               // (level l's records start at p.rzTaskOff[l])
+        for (int l = 0; l < L; ++l) all.insert(all.end(), p.rzTasks[l].begin(), p.rzTasks[l].end());
+        if (ensure(&o->dX4, &o->capX4, std::max<size_t>(1, p.x4.size()))) return ORBX_E_HIP;
         if (ensure(&o->dRzTasks, &o->capRzTasks, std::max<size_t>(1, all.size()))) return ORBX_E_HIP;
-        if (!o->x4.empty()) HIPCHK(hipMemcpy(o->dX4, o->x4.data(), o->x4.size() * sizeof(RzX4), hipMemcpyHostToDevice));
+        if (!p.x4.empty()) HIPCHK(hipMemcpy(o->dX4, p.x4.data(), p.x4.size() * sizeof(RzX4), hipMemcpyHostToDevice));
         if (!all.empty()) HIPCHK(hipMemcpy(o->dRzTasks, all.data(), all.size() * sizeof(RzTask), hipMemcpyHostToDevice));
 #ifdef ORBX_AB
         std::vector<RzTaskP> allP;
-        for (int l = 0; l < L; ++l) { o->rzTaskOffP[l] = (int)allP.size(); allP.insert(allP.end(), o->rzTasksP[l].begin(), o->rzTasksP[l].end()); }
+        for (int l = 0; l < L; ++l) allP.insert(allP.end(), p.rzTasksP[l].begin(), p.rzTasksP[l].end());
         if (ensure(&o->dRzTasksP, &o->capRzTasksP, std::max<size_t>(1, allP.size()))) return ORBX_E_HIP;
         if (!allP.empty()) HIPCHK(hipMemcpy(o->dRzTasksP, allP.data(), allP.size() * sizeof(RzTaskP), hipMemcpyHostToDevice));
 #endif
@@ -546,126 +236,35 @@ static int build_geometry(orbx* o, int w, int h) {
         (void)orbx_set_result_block(o, o->curBlock);
         HIPCHK(hipMalloc((void**)&o->dWork, sizeof(KpWork) * g.kpCap * B));
     }
-    HIPCHK(hipMemcpy(o->dCells, o->cells.data(), o->cells.size() * sizeof(CellInfo), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(o->dTiles, o->tiles.data(), o->tiles.size() * sizeof(BlurTask), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(o->dTiles3, o->tiles3.data(), o->tiles3.size() * sizeof(Blur3Task), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(o->dB3Th, o->b3Th.data(), o->b3Th.size() * sizeof(u32), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(o->dB3Tv, o->b3Tv.data(), o->b3Tv.size() * sizeof(u32), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(o->dStrips, o->strips.data(), o->strips.size() * sizeof(StripInfo), hipMemcpyHostToDevice));
-    if (!o->xt.empty()) HIPCHK(hipMemcpy(o->dXt, o->xt.data(), o->xt.size() * sizeof(RzTab), hipMemcpyHostToDevice));
-    if (!o->yt.empty()) HIPCHK(hipMemcpy(o->dYt, o->yt.data(), o->yt.size() * sizeof(RzTab), hipMemcpyHostToDevice));
-    {   // FAST launch groups.  Boundaries: [level 0] [levels 1..k] [levels k+1..], k = the smallest level after which at most
-        // 15 % of the cells remain: the coarse levels have few cells, but the tallest cell rows (an image 102 rows high is
-        // cut into 2 cell rows of 51) and the densest corners, so they keep the worst-case queue.  The other groups bound the
-        // queue so that 7 workgroups fit a CU; a cell that overflows it is redone by k_fast_fix.
-        const int nS = (int)o->strips.size();
-        std::vector<int> cellsAfter(g.nlevels + 1, 0);
-        for (int l = g.nlevels - 1; l >= 0; --l) cellsAfter[l] = cellsAfter[l + 1] + g.lv[l].nCells;
-        int k = g.nlevels - 1;
-        while (k > 0 && cellsAfter[k] * 100 <= 15 * g.totalCells) --k;      // levels > k hold <= 15 % of the cells
-        int b0 = 0, b1 = 0;
-        for (const StripInfo& stp : o->strips) { if (stp.level == 0) ++b0; if (stp.level <= k) ++b1; }
-        const int bounds[4] = {0, b0, std::max(b0, b1), nS};
-        size_t maxLds = 0;
-        for (int gi = 0; gi < 3; ++gi) {
-            orbx::F3Group G;
-            G.strip0 = bounds[gi]; G.nstrips = bounds[gi + 1] - bounds[gi];
-            if (G.nstrips <= 0) continue;
-            int qworst = 64, maxLp = 0, maxH = 0;
-            for (int si = G.strip0; si < G.strip0 + G.nstrips; ++si) {
-                G.tile = std::max(G.tile, o->stripTile[si]); qworst = std::max(qworst, o->stripQ[si]);
-                maxLp = std::max(maxLp, (int)o->strips[si].lp); maxH = std::max(maxH, (int)o->strips[si].h);
-            }
-            // one compile-time tile pitch for the whole group when its strips allow it (35..40-px cells, 4 per strip: <= 208 bytes)
-            G.pitch = o->f3NoFixedPitch ? 0 : maxLp <= 176 ? 176 : maxLp <= 208 ? 208 : 0;
-            // (>= 1 KiB: k_fast4 writes a fixed-pitch tile in wave-instructions of 64 x 16 bytes, a shorter strip as one of them)
-            if (G.pitch) G.tile = std::max(G.pitch * maxH, 1024);
-            G.tile = align_up(G.tile, 16);
-            G.lastLevel = o->strips[G.strip0 + G.nstrips - 1].level;
-            G.qcap = qworst;
-            if (gi < 2) {
-                int wgs = 7;
-                if (const char* e = ab_env("ORBX_FAST_WGS")) wgs = std::max(1, atoi(e));
-                const int budget = (160 * 1024 / wgs - 2 * G.tile) / (2 * (F3_NT / 64));
-                G.qcap = std::min(qworst, std::max(wgs > 7 ? 256 : 512, budget / 64 * 64));
-            } else {
-                // coarse levels: dense corners (over half of a cell's pixels survive on the synthetic stream), so only a mild
-                // bound -- 5 workgroups per CU instead of 4 -- and only if the queue still holds >= 3/4 of the worst case
-                const int budget = (160 * 1024 / 5 - 2 * G.tile) / (2 * (F3_NT / 64));
-                const int q5 = budget / 64 * 64;
-                if (q5 < qworst && q5 * 4 >= qworst * 3) G.qcap = q5;
-            }
-            if (o->f3QcapForce > 0) G.qcap = std::min(G.qcap, align_up(o->f3QcapForce, 64));
-            G.lds = (size_t)2 * G.tile + (size_t)(F3_NT / 64) * G.qcap * 2;
-            if (const char* e = ab_env("ORBX_FAST_LDSPAD")) G.lds += (size_t)atoi(e);   // experiment: occupancy sensitivity
-            if (G.lds > 160 * 1024 - 256) { set_err("FAST strip needs %zu B of LDS", G.lds); return ORBX_E_UNSUPPORTED; }
-            maxLds = std::max(maxLds, G.lds);
-            o->f3g.push_back(G);
-        }
-        // k_fast4 tables: per cell the scalars a wave needs, per distinct cell shape (pitch, window width, window height, column
-        // phase) the lane -> (tile bytes, valid pixels, queue-entry base) list of every quick-pass iteration
-        o->aux.assign(o->cells.size(), CellAux{});
-        o->f4items.clear();
-        std::map<std::array<int, 4>, u32> shapes;
-        for (orbx::F3Group& G : o->f3g) {
-            G.v4 = !o->fastV3;
-            for (int si = G.strip0; si < G.strip0 + G.nstrips && G.v4; ++si) {
-                const StripInfo& stp = o->strips[si];
-                const int Pb = G.pitch ? G.pitch : (int)stp.lp;
-                for (int k = 0; k < stp.ncell && G.v4; ++k) {
-                    const CellInfo& c = o->cells[stp.cell0 + k];
-                    CellAux& A = o->aux[stp.cell0 + k];
-                    A.slot = c.slot; A.cnt = c.cnt;
-                    const int cx0 = c.x0 + 3 - stp.xal, vw = c.cw - 6, vh = stp.h - 6;
-                    if (vw <= 0 || vh <= 0) { A.nit = 0; continue; }
-                    const int a = cx0 & 3, s4 = cx0 - a, ncol = (a + vw + 7) / 8, nitems = vh * ncol, nit = (nitems + 63) / 64;
-                    // limits of the 16-bit fields (entry: 7-bit row, 7-bit xs; item: 16-bit tile offset); beyond them the group stays on k_fast3
-                    if (ncol > 16 || vh > 127 || (vh - 1) * Pb + 8 * (ncol - 1) > 65535 || 3 * Pb + s4 > 65535 || s4 < 4) { G.v4 = false; break; }
-                    const std::array<int, 4> key = {Pb, vw, vh, a};
-                    auto itS = shapes.find(key);
-                    if (itS == shapes.end()) {
-                        const u32 t0 = (u32)o->f4items.size();
-                        o->f4items.resize(t0 + (size_t)nit * 64);
-                        for (int i = 0; i < nit * 64; ++i) {
-                            F4Item& I = o->f4items[t0 + i];
-                            I.mask = 0; I.offq = 0;
-                            if (i >= nitems) continue;                  // idle lane of the last iteration: reads (row 0, column 0), keeps nothing
-                            const int row = i / ncol, col = i % ncol;
-                            for (int px = 0; px < 8; ++px) { const int xs = 8 * col + px; if (xs >= a && xs < a + vw) I.mask |= 1u << (4 * px + 3); }
-                            I.offq = (u32)(row * Pb + 8 * col) | ((u32)((row << 9) | (col << 5)) << 16);
-                        }
-                        itS = shapes.emplace(key, t0).first;
-                    }
-                    A.tab = itS->second;
-                    A.base = (u16)(3 * Pb + s4); A.nit = (u16)nit;
-                    A.outx = (short)(c.x0 + 3 - 16 - a); A.outy = (short)(stp.y0 + 3 - 16);
-                    A.xlo = (u16)a; A.xhi = (u16)(a + vw - 1);
-                }
-            }
-        }
-        if (o->f4items.size() < 64) o->f4items.resize(64, F4Item{0, 0});    // (k_fast4's waves without a cell read one iteration of table 0)
-        if (ensure(&o->dAux, &o->capAux, o->aux.size())) return ORBX_E_HIP;
-        if (ensure(&o->dF4Items, &o->capF4Items, o->f4items.size())) return ORBX_E_HIP;
-        HIPCHK(hipMemcpy(o->dAux, o->aux.data(), o->aux.size() * sizeof(CellAux), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(o->dF4Items, o->f4items.data(), o->f4items.size() * sizeof(F4Item), hipMemcpyHostToDevice));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
+    HIPCHK(hipMemcpy(o->dCells, p.cells.data(), p.cells.size() * sizeof(CellInfo), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dTiles, p.tiles.data(), p.tiles.size() * sizeof(BlurTask), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dTiles3, p.tiles3.data(), p.tiles3.size() * sizeof(Blur3Task), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dB3Th, p.b3Th.data(), p.b3Th.size() * sizeof(u32), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dB3Tv, p.b3Tv.data(), p.b3Tv.size() * sizeof(u32), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dStrips, p.strips.data(), p.strips.size() * sizeof(StripInfo), hipMemcpyHostToDevice));
+    if (!p.xt.empty()) HIPCHK(hipMemcpy(o->dXt, p.xt.data(), p.xt.size() * sizeof(RzTab), hipMemcpyHostToDevice));
+    if (!p.yt.empty()) HIPCHK(hipMemcpy(o->dYt, p.yt.data(), p.yt.size() * sizeof(RzTab), hipMemcpyHostToDevice));
+    if (ensure(&o->dAux, &o->capAux, p.aux.size())) return ORBX_E_HIP;
+    if (ensure(&o->dF4Items, &o->capF4Items, p.f4items.size())) return ORBX_E_HIP;
+    HIPCHK(hipMemcpy(o->dAux, p.aux.data(), p.aux.size() * sizeof(CellAux), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(o->dF4Items, p.f4items.data(), p.f4items.size() * sizeof(F4Item), hipMemcpyHostToDevice));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
 #ifdef ORBX_AB
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast3<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast3<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
-        HIPCHK(hipFuncSetAttribute((const void*)k_fast3<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)maxLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast4p<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast3<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast3<176>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_fast3<208>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.fastLds));
 #endif
-    }
     if (ensure(&o->dOvfList, &o->capOvfList, (size_t)g.totalCells * B)) return ORBX_E_HIP;
 #ifdef ORBX_AB
-    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)o->qtLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qtLds));
 #endif
-    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)o->qt2Lds));
-    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)o->qt2Lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
     o->curW = w; o->curH = h;
     return 0;
 }
@@ -777,8 +376,11 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     if (device_id < 0 || device_id >= ndev) { set_err("device %d out of range (%d devices)", device_id, ndev); return ORBX_E_INVALID; }
     HIPCHK(hipSetDevice(device_id));
     orbx* o = new orbx;
-    o->nfeatures = nfeatures; o->nlevels = nlevels; o->iniTh = ini_th; o->minTh = min_th; o->device = device_id;
-    o->maxW = max_w; o->maxH = max_h; o->maxBatch = max_batch;
+    o->device = device_id;
+    PlanConfig& cfg = o->cfg;
+    cfg.nfeatures = nfeatures; cfg.nlevels = nlevels; cfg.iniTh = ini_th; cfg.minTh = min_th;
+    cfg.maxW = max_w; cfg.maxH = max_h; cfg.maxBatch = max_batch;
+    cfg.scaleFactor = scale_factor;                             // double member initialised from float (ORBextractor.h:96)
     o->fastV1 = ab_env("ORBX_FAST_V1") != nullptr;
     o->qtV1 = ab_env("ORBX_QT_V1") != nullptr;
     // default: the matrix-core blur (k_blur3) directly behind the resize chain, i.e. beside FAST (which is VALU/LDS-bound, while
@@ -786,39 +388,25 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     // ORBX_BLUR_LATE = k_blur3 but beside the quadtree.
     o->blurV2 = ab_env("ORBX_BLUR_V2") != nullptr;
     o->odV1 = ab_env("ORBX_OD_V1") != nullptr;
-    if (const char* e = ab_env("ORBX_FAST_QCAP")) o->f3QcapForce = atoi(e);
-    o->f3NoFixedPitch = ab_env("ORBX_FAST_PITCH0") != nullptr;
-    o->fastV3 = ab_env("ORBX_FAST_V3") != nullptr;
+    if (const char* e = ab_env("ORBX_FAST_QCAP")) cfg.f3QcapForce = atoi(e);
+    cfg.f3NoFixedPitch = ab_env("ORBX_FAST_PITCH0") != nullptr;
+    cfg.fastV3 = ab_env("ORBX_FAST_V3") != nullptr;
+    if (const char* e = ab_env("ORBX_FAST_WGS")) cfg.fastWgs = std::max(1, atoi(e));
+    if (const char* e = ab_env("ORBX_FAST_LDSPAD")) cfg.fastLdsPad = atoi(e);   // experiment: occupancy sensitivity
     o->fastV4p = ab_env("ORBX_FAST_V4P") != nullptr;
 #ifdef ORBX_AB
-    o->rzNoPack = ab_env("ORBX_RESIZE_NOPACK") != nullptr;
+    cfg.rzNoPack = ab_env("ORBX_RESIZE_NOPACK") != nullptr;
     o->rzV2p = ab_env("ORBX_RESIZE_V2P") != nullptr;
 #endif
-    if (const char* e = ab_env("ORBX_QT_WIDE")) o->qtWideForce = atoi(e) != 0 ? 1 : 0;
+    if (const char* e = ab_env("ORBX_QT_WIDE")) cfg.qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
-    o->blurTiled = !o->blurV2 && !o->odV1 && ab_env("ORBX_BLUR_ROWMAJOR") == nullptr;
+    cfg.blurTiled = !o->blurV2 && !o->odV1 && ab_env("ORBX_BLUR_ROWMAJOR") == nullptr;
     if (const char* e = ab_env("ORBX_BLUR_WALK")) o->blurWalkForce = atoi(e) != 0 ? 1 : 0;
     o->dlKernel = ab_env("ORBX_DL_KERNEL") != nullptr;          // A/B: results-to-host copy by k_copy_out instead of the copy engine
     if (const char* e = ab_env("ORBX_DL_GRID")) o->dlGrid = std::max(1, atoi(e));
     if (const char* e = ab_env("ORBX_ONE_GRAPH")) o->oneOff = atoi(e) == 0;   // A/B: single-frame calls stay eager
     o->serial = ab_env("ORBX_SERIAL") != nullptr;            // A/B switch: simple per-cell reference kernel
-    o->scaleFactor = scale_factor;                              // double member initialised from float (ORBextractor.h:96)
-    const int L = nlevels;
-    o->sf.resize(L); o->sig2.resize(L); o->invsf.resize(L); o->invsig2.resize(L); o->nfeat.resize(L);
-    o->sf[0] = 1.0f; o->sig2[0] = 1.0f;
-    for (int i = 1; i < L; ++i) { o->sf[i] = (float)(o->sf[i - 1] * o->scaleFactor); o->sig2[i] = o->sf[i] * o->sf[i]; }
-    for (int i = 0; i < L; ++i) { o->invsf[i] = 1.0f / o->sf[i]; o->invsig2[i] = 1.0f / o->sig2[i]; }
-    float factor = (float)(1.0f / o->scaleFactor);
-    float nDesired = nfeatures * (1 - factor) / (1 - (float)std::pow((double)factor, (double)L));
-    int sum = 0;
-    for (int l = 0; l < L - 1; ++l) { o->nfeat[l] = cv_round_f(nDesired); sum += o->nfeat[l]; nDesired *= factor; }
-    o->nfeat[L - 1] = std::max(nfeatures - sum, 0);
-    {   // umax (ORBextractor.cc:542-570)
-        int* um = o->umax.v;
-        int v, v0, vmax = (int)floorf(15 * sqrtf(2.f) / 2 + 1), vmin = (int)ceilf(15 * sqrtf(2.f) / 2);
-        for (v = 0; v <= vmax; ++v) um[v] = (int)lrint(std::sqrt(225.0 - v * v));
-        for (v = 15, v0 = 0; v >= vmin; --v) { while (um[v0] == um[v0 + 1]) ++v0; um[v] = v0; ++v0; }
-    }
+    o->tab = plan_tables(cfg);
     int rc = ORBX_OK;
     do {
         if (hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&o->stream2, hipStreamNonBlocking) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipStreamCreate failed"); break; }
@@ -836,21 +424,7 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
         if (hipMalloc((void**)&o->dL0Ptr, sizeof(u8*) * B) != hipSuccess || hipMalloc((void**)&o->dSelCnt, sizeof(u32) * 12 * B) != hipSuccess ||
             hipMalloc((void**)&o->dLap, sizeof(int) * 2 * B) != hipSuccess || hipMalloc((void**)&o->dErr, sizeof(int)) != hipSuccess ||
             hipMalloc((void**)&o->dPattern, 1024) != hipSuccess || hipMalloc((void**)&o->dOdW, sizeof(u32) * OD_WTAB) != hipSuccess || hipMalloc((void**)&o->dOvf, 2 * sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMalloc failed"); break; }
-        {   // IC_Angle weights for v_dot4: entry [|v|][j] packs, for the 4 bytes of dword j of a 32-byte patch row (it starts at
-            // cx-15) at distance |v| from the centre, (u + 16) where the pixel lies inside the disc (|u| <= umax[|v|]) and 0
-            // elsewhere; u = 4j + b - 15.  Row 16 is all zero (lanes past the 31st row).
-            std::vector<u32> wt(OD_WTAB, 0u);
-            for (int va = 0; va < 16; ++va)
-                for (int j = 0; j < 8; ++j) {
-                    u32 wv = 0;
-                    for (int b = 0; b < 4; ++b) {
-                        const int u = 4 * j + b - 15;
-                        if (std::abs(u) <= o->umax.v[va]) wv |= (u32)(u + 16) << (8 * b);
-                    }
-                    wt[va * 8 + j] = wv;
-                }
-            if (hipMemcpy(o->dOdW, wt.data(), sizeof(u32) * OD_WTAB, hipMemcpyHostToDevice) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
-        }
+        if (hipMemcpy(o->dOdW, o->tab.odW.data(), sizeof(u32) * OD_WTAB, hipMemcpyHostToDevice) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
         if (hipMemcpy(o->dPattern, kPattern, 1024, hipMemcpyHostToDevice) != hipSuccess || hipMemset(o->dErr, 0, sizeof(int)) != hipSuccess || hipMemset(o->dOvf, 0, 2 * sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
         o->hL0Ptr.resize(B); o->hLap.resize(2 * B);
         rc = build_geometry(o, max_w, max_h);
@@ -896,7 +470,7 @@ void orbx_destroy(orbx_t* o) {
     delete o;
 }
 
-int orbx_max_keypoints(const orbx_t* o) { return o ? o->g.kpCap : ORBX_E_INVALID; }
+int orbx_max_keypoints(const orbx_t* o) { return o ? o->plan.g.kpCap : ORBX_E_INVALID; }
 
 static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int img_space, int nimg, int w, int h, int stride,
                                     const int* lap01);
@@ -909,14 +483,14 @@ int orbx_extract_batch_async(orbx_t* o, const uint8_t* const* imgs, int img_spac
 static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int img_space, int nimg, int w, int h, int stride,
                                     const int* lap01) {
     if (!o || !imgs || nimg < 1) return ORBX_E_INVALID;
-    if (nimg > o->maxBatch) { set_err("batch %d exceeds max_batch %d", nimg, o->maxBatch); return ORBX_E_CAPACITY; }
+    if (nimg > o->cfg.maxBatch) { set_err("batch %d exceeds max_batch %d", nimg, o->cfg.maxBatch); return ORBX_E_CAPACITY; }
     if (w <= 0 || h <= 0) return ORBX_E_EMPTY;
     for (int i = 0; i < nimg; ++i) if (!imgs[i]) return ORBX_E_EMPTY;
     if (stride < w) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
     int rc = build_geometry(o, w, h);
     if (rc) return rc;
-    const Geom& g = o->g;
+    const Geom& g = o->plan.g;
     hipStream_t st = o->stream;
     const bool capturing = o->capSlot >= 0;
     if (!capturing) { rc = dl_wait_block(o, o->curBlock); if (rc) return rc; }   // this block may still be on its way to the host
@@ -933,15 +507,15 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     } else if (img_space == ORBX_DEVICE) {                    // kernels use 16-byte row loads: stage misaligned inputs
         o->l0Staged = false;                                  // dL0 is filled device-to-device: hPinned (if any) holds an OLDER host batch
         for (int i = 0; i < nimg; ++i) {
-            u8* d = o->dL0 + (size_t)i * o->l0pitch * h;
-            HIPCHK(hipMemcpy2DAsync(d, o->l0pitch, imgs[i], stride, w, h, hipMemcpyDeviceToDevice, st));
+            u8* d = o->dL0 + (size_t)i * o->plan.l0pitch * h;
+            HIPCHK(hipMemcpy2DAsync(d, o->plan.l0pitch, imgs[i], stride, w, h, hipMemcpyDeviceToDevice, st));
             o->hL0Ptr[i] = d;
         }
-        l0pitch = o->l0pitch;
+        l0pitch = o->plan.l0pitch;
     } else {
         // host images: packed into one pinned staging buffer (CPU memcpy), then ONE asynchronous copy for the whole batch --
         // per-image copies from pageable memory run at ~3 GB/s and block the calling thread
-        const size_t imgBytes = (size_t)o->l0pitch * h, need = imgBytes * nimg;
+        const size_t imgBytes = (size_t)o->plan.l0pitch * h, need = imgBytes * nimg;
         if (need > o->capPinned) {
             if (o->hPinned) (void)hipHostFree(o->hPinned);
             o->hPinned = nullptr; o->capPinned = 0;
@@ -953,13 +527,13 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
         else HIPCHK(hipEventSynchronize(o->evH2D));               // the previous batch's DMA out of the staging buffer is done
         for (int i = 0; i < nimg; ++i) {
             u8* p = o->hPinned + imgBytes * i;
-            if (stride == o->l0pitch) memcpy(p, imgs[i], (size_t)stride * h);
-            else for (int y = 0; y < h; ++y) memcpy(p + (size_t)y * o->l0pitch, imgs[i] + (size_t)y * stride, (size_t)w);
+            if (stride == o->plan.l0pitch) memcpy(p, imgs[i], (size_t)stride * h);
+            else for (int y = 0; y < h; ++y) memcpy(p + (size_t)y * o->plan.l0pitch, imgs[i] + (size_t)y * stride, (size_t)w);
             o->hL0Ptr[i] = o->dL0 + imgBytes * i;
         }
         HIPCHK(hipMemcpyAsync(o->dL0, o->hPinned, need, hipMemcpyHostToDevice, st));
         HIPCHK(hipEventRecord(o->evH2D, st));
-        l0pitch = o->l0pitch;
+        l0pitch = o->plan.l0pitch;
         o->l0Staged = true;
     }
     for (int i = 0; i < nimg; ++i) { o->hLap[2 * i] = lap01 ? lap01[2 * i] : 0; o->hLap[2 * i + 1] = lap01 ? lap01[2 * i + 1] : 0; }
@@ -990,29 +564,24 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     STAGE_EV(7, s1);
     for (int l = 1; l < g.nlevels; ++l) {
 #ifdef ORBX_AB
-        if (o->rzV2p && o->rzStreamP[l]) {
-            const int nt = (int)o->rzTasksP[l].size();
+        if (o->rzV2p && o->plan.rzStreamP[l]) {
+            const int nt = (int)o->plan.rzTasksP[l].size();
             hipLaunchKernelGGL(k_resize2p, dim3((nt + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr,
-                               o->dRzTasksP + o->rzTaskOffP[l], nt, o->dX4, o->dYt);
+                               o->dRzTasksP + o->plan.rzTaskOffP[l], nt, o->dX4, o->dYt);
         } else
 #endif
-        if (o->rzStream[l]) {
+        if (o->plan.rzStream[l]) {
             // a flat list of waves: full tiles x frames, then packed remainder tiles x groups of `pack` frames
-            RzLaunch P;
-            P.nFull = (u32)o->rzNFull[l]; P.nPack = (u32)o->rzNPack[l]; P.nimg = (u32)nimg;
-            P.nFullW = P.nFull * P.nimg;
-            P.nWaves = P.nFullW + P.nPack * (u32)((nimg + o->rzPack[l] - 1) / o->rzPack[l]);
-            P.mFull = P.nFull > 1 ? (u32)((1ull << 32) / P.nFull) + 1u : 0u;
-            P.mPack = P.nPack > 1 ? (u32)((1ull << 32) / P.nPack) + 1u : 0u;
+            const RzLaunch P = rz_launch(o->plan, l, nimg);
             auto kern = l == 1 ? k_resize2<true> : k_resize2<false>;
             hipLaunchKernelGGL(kern, dim3((P.nWaves + 3) / 4), dim3(256), 0, s1, o->dL0Ptr, l0pitch, o->dPyr, g.pyrFrameBytes,
-                               o->dRzTasks + o->rzTaskOff[l], P, o->dX4);
+                               o->dRzTasks + o->plan.rzTaskOff[l], P, o->dX4);
         } else {                                                 // general fallback (large scale factors)
             dim3 grid((g.lv[l].w + 255) / 256, (g.lv[l].h + 3) / 4, nimg), block(64, 4);
             hipLaunchKernelGGL(k_resize, grid, block, 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, l, o->dXt, o->dYt);
         }
         if (!o->fastV1 && l < g.nlevels - 1)
-            for (const orbx::F3Group& G : o->f3g) if (G.lastLevel == l) HIPCHK(hipEventRecord(o->evLvl[l], s1));
+            for (const F3Group& G : o->plan.f3g) if (G.lastLevel == l) HIPCHK(hipEventRecord(o->evLvl[l], s1));
     }
     HIPCHK(rec_ev(o, 8, s1, true));                              // pyramid ready
     if (o->fastV1) {
@@ -1025,7 +594,7 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
         // every group waits only for the pyramid levels it reads: the fine levels start while the coarse ones are still
         // being resized (the 7 resizes are a dependent chain of small kernels, ~160 us)
         bool first = true;
-        for (const orbx::F3Group& G : o->f3g) {
+        for (const F3Group& G : o->plan.f3g) {
             const bool lvl0 = G.lastLevel == 0;
             if (!lvl0) {
                 if (first) STAGE_EV(10, st);   // level-0 FAST done
@@ -1071,35 +640,30 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     STAGE_EV(11, s1);
     if (o->blurV2) {
         o->blurFormLast = 2;
-        AB_LAUNCH(k_blur2, dim3((unsigned)(o->tiles.size() + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
-                  o->dTiles, (int)o->tiles.size(), o->blurSel);
+        AB_LAUNCH(k_blur2, dim3((unsigned)(o->plan.tiles.size() + 3) / 4, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
+                  o->dTiles, (int)o->plan.tiles.size(), o->plan.blurSel);
     } else {
-        // big batches: workgroups walk B3_CHUNK tiles (prologue amortised); small ones: one tile per workgroup (8x the workgroups,
-        // an eighth of the latency -- the single-frame path)
-        const bool walk = o->blurWalkForce >= 0 ? o->blurWalkForce != 0 : (size_t)nimg * o->nTiles3Walk >= 2048;
+        const bool walk = blur_walks(o->plan, nimg, o->blurWalkForce);
         o->blurFormLast = walk ? 1 : 0;
-        const size_t first = walk ? 0 : o->nTiles3Walk, count = walk ? o->nTiles3Walk : o->tiles3.size() - o->nTiles3Walk;
+        const size_t first = walk ? 0 : o->plan.nTiles3Walk, count = walk ? o->plan.nTiles3Walk : o->plan.tiles3.size() - o->plan.nTiles3Walk;
         hipLaunchKernelGGL(k_blur3, dim3((unsigned)count, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                            o->dTiles3 + first, (const uint4*)o->dB3Th, (const uint4*)o->dB3Tv);
     }
     HIPCHK(rec_ev(o, 9, s1, true));                              // blur ready
     if (o->qtV1) o->qtThreadsLast = 0;
     if (o->qtV1)
-        AB_LAUNCH(k_quadtree, dim3(nimg, g.nlevels), dim3(256), o->qtLds, st, g, o->dCells, o->dCandCnt, o->dCandEnt,
+        AB_LAUNCH(k_quadtree, dim3(nimg, g.nlevels), dim3(256), o->plan.qtLds, st, g, o->dCells, o->dCandCnt, o->dCandEnt,
                   o->dKpNode, o->dSel, o->dSelCnt, o->dErr);
     else {
-        Geom g2 = g; g2.nodeCap = o->qt2Cap; g2.sortCap = o->qt2Sort;
-        // few workgroups (small batches, the single-frame call): the kernel's time is one workgroup's latency, and 1024 threads walk
-        // a level's candidates four times faster than 256 (one frame: 0.276 -> 0.237 ms end to end); many workgroups: 256 threads
-        // (shorter barriers, more workgroups per CU: 0.24 vs 0.56 ms per 512 frames)
-        const bool wide = o->qtWideForce >= 0 ? o->qtWide : (o->qtWide || nimg * g.nlevels <= 512);
+        Geom g2 = g; g2.nodeCap = o->plan.qt2Cap; g2.sortCap = o->plan.qt2Sort;
+        const bool wide = qt_wide(o->plan, nimg, g.nlevels, o->cfg.qtWideForce);
         o->qtThreadsLast = wide ? 1024 : 256;
         if (wide)
-            hipLaunchKernelGGL(k_quadtree2<1024>, dim3(nimg, g.nlevels), dim3(1024), o->qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
-                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->maxCells, o->maxIni, o->qtFuseD);
+            hipLaunchKernelGGL(k_quadtree2<1024>, dim3(nimg, g.nlevels), dim3(1024), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
+                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
         else
-            hipLaunchKernelGGL(k_quadtree2<256>, dim3(nimg, g.nlevels), dim3(256), o->qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
-                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->maxCells, o->maxIni, o->qtFuseD);
+            hipLaunchKernelGGL(k_quadtree2<256>, dim3(nimg, g.nlevels), dim3(256), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
+                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
     }
     STAGE_EV(3, st);
     if (o->guardPending) {                                       // k_slots is the first writer of the result block (orbx_guard_results)
@@ -1114,7 +678,7 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
     o->orientFormLast = o->odV1 ? 2 : g.blurTiled ? 0 : 1;
     if (o->odV1)
         AB_LAUNCH(k_orient_desc, dim3((g.kpCap + 3) / 4, nimg), dim3(256), 0, st, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
-                  o->dWork, o->dN, o->dKps, o->dDesc, o->dPattern, o->umax);
+                  o->dWork, o->dN, o->dKps, o->dDesc, o->dPattern, o->tab.umax);
     else
         hipLaunchKernelGGL(k_orient_desc2, dim3((g.kpCap + 15) / 16, nimg), dim3(256), 0, st, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                            o->dWork, o->dN, o->dKps, o->dDesc, o->dPattern, o->dOdW);
@@ -1317,7 +881,7 @@ int orbx_result_device(const orbx_t* o, const orbx_kp_t** kps, const uint8_t** d
     if (desc) *desc = o->dDesc;
     if (counts) *counts = o->dN;
     if (monos) *monos = o->dMono;
-    if (cap) *cap = o->g.kpCap;
+    if (cap) *cap = o->plan.g.kpCap;
     return ORBX_OK;
 }
 
@@ -1329,8 +893,8 @@ int orbx_result_fetch(orbx_t* o, int i, orbx_kp_t* kps, uint8_t* desc, int cap, 
     const int n = o->hN[i], mono = o->hMono[i];
     if (n > cap) { set_err("%d keypoints exceed caller capacity %d", n, cap); return ORBX_E_CAPACITY; }
     if (n > 0) {
-        if (kps) HIPCHK(hipMemcpy(kps, o->dKps + (size_t)i * o->g.kpCap, sizeof(KpOut) * n, hipMemcpyDeviceToHost));
-        if (desc) HIPCHK(hipMemcpy(desc, o->dDesc + (size_t)i * o->g.kpCap * 32, (size_t)32 * n, hipMemcpyDeviceToHost));
+        if (kps) HIPCHK(hipMemcpy(kps, o->dKps + (size_t)i * o->plan.g.kpCap, sizeof(KpOut) * n, hipMemcpyDeviceToHost));
+        if (desc) HIPCHK(hipMemcpy(desc, o->dDesc + (size_t)i * o->plan.g.kpCap * 32, (size_t)32 * n, hipMemcpyDeviceToHost));
     }
     if (mono_index) *mono_index = mono;
     return n;
@@ -1341,7 +905,7 @@ int orbx_result_fetch_all(orbx_t* o, orbx_kp_t* kps, uint8_t* desc, int cap_per_
     HIPCHK(hipSetDevice(o->device));
     int rc = fetch_counts(o);
     if (rc) return rc;
-    const int B = o->lastBatch, dc = o->g.kpCap;
+    const int B = o->lastBatch, dc = o->plan.g.kpCap;
     for (int i = 0; i < B; ++i) if (o->hN[i] > cap_per_img) { set_err("%d keypoints exceed caller capacity %d", o->hN[i], cap_per_img); return ORBX_E_CAPACITY; }
     if (cap_per_img == dc) {                                    // same layout as the device buffers: one copy each
         if (kps) HIPCHK(hipMemcpy(kps, o->dKps, sizeof(KpOut) * (size_t)dc * B, hipMemcpyDeviceToHost));
@@ -1363,7 +927,7 @@ int orbx_result_fetch_all(orbx_t* o, orbx_kp_t* kps, uint8_t* desc, int cap_per_
 static size_t one_desc_off(int kc) { return (16 + (size_t)kc * 28 + 15) & ~(size_t)15; }
 
 static int one_landing(orbx* o) {                                // pinned landing buffer [header | kps | desc | lapping area]
-    const int kc = o->g.kpCap;
+    const int kc = o->plan.g.kpCap;
     const size_t need = one_desc_off(kc) + (size_t)kc * 32 + 16;
     if (need > o->capOne) {
         if (o->hOne) (void)hipHostFree(o->hOne);
@@ -1376,7 +940,7 @@ static int one_landing(orbx* o) {                                // pinned landi
 }
 
 static int one_results(orbx* o, orbx_kp_t* kps, uint8_t* desc, int cap, int* mono_index) {
-    const int kc = o->g.kpCap;
+    const int kc = o->plan.g.kpCap;
     const u32* hd = (const u32*)o->hOne;
     const int n = (int)hd[0], mono = (int)hd[1], e = (int)hd[2];
     if (e) { set_err("device-side overflow flag %d", e); (void)hipMemset(o->dErr, 0, sizeof(int)); return ORBX_E_INTERNAL; }
@@ -1391,7 +955,7 @@ static int one_results(orbx* o, orbx_kp_t* kps, uint8_t* desc, int cap, int* mon
 }
 
 static void one_launch_fetch(orbx* o) {
-    const int kc = o->g.kpCap;
+    const int kc = o->plan.g.kpCap;
     hipLaunchKernelGGL(k_fetch_one, dim3(8), dim3(256), 0, o->stream, o->dKps, o->dDesc, o->dN, o->dMono, o->dErr, 0, kc, (u32*)o->hOne,
                        (int)(one_desc_off(kc) / 4));
 }
@@ -1410,9 +974,9 @@ static void one_capture(orbx* o, int w, int h) {
     G.launches = 0; G.nimg = 0;
     o->oneW = o->oneH = 0;
     if (hipStreamSynchronize(o->stream) != hipSuccess || hipStreamSynchronize(o->stream2) != hipSuccess || dl_drain(o)) { o->oneOff = true; return; }
-    const int kc = o->g.kpCap;
+    const int kc = o->plan.g.kpCap;
     int* lapPinned = (int*)(o->hOne + one_desc_off(kc) + (size_t)kc * 32);
-    const size_t imgBytes = (size_t)o->l0pitch * h;
+    const size_t imgBytes = (size_t)o->plan.l0pitch * h;
     if (hipStreamBeginCapture(o->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) { (void)hipGetLastError(); o->oneOff = true; return; }
     o->capSlot = slot; o->capFailed = false;
     bool ok = hipMemcpyAsync(o->dL0, o->hPinned, imgBytes, hipMemcpyHostToDevice, o->stream) == hipSuccess &&
@@ -1421,7 +985,7 @@ static void one_capture(orbx* o, int w, int h) {
         const uint8_t* dimg = o->dL0;
         const int lap[2] = {lapPinned[0], lapPinned[1]};
         o->upLap.assign(lap, lap + 2);                           // the captured copy above uploads them on every replay
-        ok = orbx_extract_batch_async(o, &dimg, ORBX_DEVICE, 1, w, h, o->l0pitch, lap) == ORBX_OK;
+        ok = orbx_extract_batch_async(o, &dimg, ORBX_DEVICE, 1, w, h, o->plan.l0pitch, lap) == ORBX_OK;
     }
     if (ok) { one_launch_fetch(o); ok = hipGetLastError() == hipSuccess; }
     o->capSlot = -1;
@@ -1467,17 +1031,17 @@ int orbx_extract(orbx_t* o, const uint8_t* img, int w, int h, int stride, int la
         // ---- replay
         orbx::GraphSlot& G = o->gs[orbx::kSlots];
         { const int rc = dl_wait_block(o, G.block); if (rc) return rc; }
-        const int kc = o->g.kpCap;
+        const int kc = o->plan.g.kpCap;
         if (o->evH2D) HIPCHK(hipEventSynchronize(o->evH2D));     // an asynchronous batch of host images may still be leaving the staging buffer
         u8* p = o->hPinned;
-        if (stride == o->l0pitch) memcpy(p, img, (size_t)stride * h);
-        else for (int y = 0; y < h; ++y) memcpy(p + (size_t)y * o->l0pitch, img + (size_t)y * stride, (size_t)w);
+        if (stride == o->plan.l0pitch) memcpy(p, img, (size_t)stride * h);
+        else for (int y = 0; y < h; ++y) memcpy(p + (size_t)y * o->plan.l0pitch, img + (size_t)y * stride, (size_t)w);
         int* lapPinned = (int*)(o->hOne + one_desc_off(kc) + (size_t)kc * 32);
         lapPinned[0] = lap0; lapPinned[1] = lap1;
         HIPCHK(hipGraphLaunch(G.exec, o->stream));
         ++G.launches;
         { const int rc = orbx_set_result_block(o, G.block); if (rc) return rc; }
-        o->hL0Ptr[0] = o->dL0; o->lastL0Pitch = o->l0pitch; o->l0Staged = true;
+        o->hL0Ptr[0] = o->dL0; o->lastL0Pitch = o->plan.l0pitch; o->l0Staged = true;
         o->hLap[0] = lap0; o->hLap[1] = lap1; o->upLap.assign(lap, lap + 2);
         o->lastBatch = 1; o->countsValid = false; o->timed = true; o->graphMode = true;
         HIPCHK(hipStreamSynchronize(o->stream));
@@ -1499,7 +1063,7 @@ int orbx_extract(orbx_t* o, const uint8_t* img, int w, int h, int stride, int la
     if (n >= 0 && graphOk) {
         if (o->oneW == w && o->oneH == h) o->oneEager = 0;
         else if (++o->oneEager >= 2) {                           // same geometry twice in a row on the eager path: worth a graph
-            int* lapPinned = (int*)(o->hOne + one_desc_off(o->g.kpCap) + (size_t)o->g.kpCap * 32);
+            int* lapPinned = (int*)(o->hOne + one_desc_off(o->plan.g.kpCap) + (size_t)o->plan.g.kpCap * 32);
             lapPinned[0] = lap0; lapPinned[1] = lap1;
             one_capture(o, w, h);
             o->oneEager = 0;
@@ -1509,34 +1073,34 @@ int orbx_extract(orbx_t* o, const uint8_t* img, int w, int h, int stride, int la
 }
 
 int orbx_level_size(const orbx_t* o, int level, int* w, int* h) {
-    if (!o || level < 0 || level >= o->nlevels || !o->curW) return ORBX_E_INVALID;
-    *w = o->g.lv[level].w; *h = o->g.lv[level].h;
+    if (!o || level < 0 || level >= o->cfg.nlevels || !o->curW) return ORBX_E_INVALID;
+    *w = o->plan.g.lv[level].w; *h = o->plan.g.lv[level].h;
     return ORBX_OK;
 }
 
 int orbx_level_image(orbx_t* o, int frame, int level, int blurred, uint8_t* dst, int dst_stride) {
-    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->nlevels) return ORBX_E_INVALID;
+    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->cfg.nlevels) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
     HIPCHK(hipStreamSynchronize(o->stream));
-    const LevelDesc& D = o->g.lv[level];
+    const LevelDesc& D = o->plan.g.lv[level];
     if (level == 0 && !blurred) {
         // level 0 lives wherever the caller's image (or its staged copy) is
         const u8* src = o->hL0Ptr[frame];
-        int pitch = (src >= o->dL0 && src < o->dL0 + o->capL0) ? o->l0pitch : 0;
+        int pitch = (src >= o->dL0 && src < o->dL0 + o->capL0) ? o->plan.l0pitch : 0;
         if (!pitch) { set_err("level 0 of a device-resident input is the caller's own buffer"); return ORBX_E_INVALID; }
         HIPCHK(hipMemcpy2D(dst, dst_stride, src, pitch, D.w, D.h, hipMemcpyDeviceToHost));
         return ORBX_OK;
     }
-    if (blurred && o->g.blurTiled) {                             // de-tile on the host (a debug / test accessor)
+    if (blurred && o->plan.g.blurTiled) {                             // de-tile on the host (a debug / test accessor)
         const size_t nb = (size_t)D.btpr * ((D.h + 7) / 8) * 128;
         std::vector<u8> raw(nb);
-        HIPCHK(hipMemcpy(raw.data(), o->dBlur + (size_t)frame * o->g.blrFrameBytes + D.boff, nb, hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(raw.data(), o->dBlur + (size_t)frame * o->plan.g.blrFrameBytes + D.boff, nb, hipMemcpyDeviceToHost));
         for (int y = 0; y < D.h; ++y)
             for (int x = 0; x < D.w; ++x)
                 dst[(size_t)y * dst_stride + x] = raw[((size_t)(y >> 3) * D.btpr + (x >> 4)) * 128 + (size_t)(y & 7) * 16 + (x & 15)];
         return ORBX_OK;
     }
-    const u8* base = blurred ? o->dBlur + (size_t)frame * o->g.blrFrameBytes + D.boff : o->dPyr + (size_t)frame * o->g.pyrFrameBytes + D.off;
+    const u8* base = blurred ? o->dBlur + (size_t)frame * o->plan.g.blrFrameBytes + D.boff : o->dPyr + (size_t)frame * o->plan.g.pyrFrameBytes + D.off;
     // one contiguous copy of the level (rows with their pitch) into pinned memory, then host row copies: a 2-D copy into pageable
     // memory goes row by row through the runtime (1.2 ms for a 752x480 level)
     const size_t nb = (size_t)D.pitch * D.h;
@@ -1557,7 +1121,7 @@ int orbx_level_image(orbx_t* o, int frame, int level, int blurred, uint8_t* dst,
 int orbx_pyramid_fetch(orbx_t* o, int frame, uint8_t* const* dst, const int* dst_stride) {
     if (!o || !dst || !dst_stride || frame < 0 || frame >= o->lastBatch || !o->curW) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
-    const Geom& g = o->g;
+    const Geom& g = o->plan.g;
     if (g.pyrFrameBytes > o->capPyrHost) {
         if (o->hPyr) (void)hipHostFree(o->hPyr);
         o->hPyr = nullptr; o->capPyrHost = 0;
@@ -1571,10 +1135,10 @@ int orbx_pyramid_fetch(orbx_t* o, int frame, uint8_t* const* dst, const int* dst
         if (!dst[l]) continue;
         if (l == 0) {
             const u8* src = o->hL0Ptr[frame];
-            const bool staged = o->l0Staged && o->hPinned && src >= o->dL0 && src < o->dL0 + o->capL0 && (size_t)(src - o->dL0) + (size_t)o->l0pitch * D.h <= o->capPinned;
+            const bool staged = o->l0Staged && o->hPinned && src >= o->dL0 && src < o->dL0 + o->capL0 && (size_t)(src - o->dL0) + (size_t)o->plan.l0pitch * D.h <= o->capPinned;
             if (staged) {                                        // the host copy of what was uploaded is still in the staging buffer
                 const u8* hp = o->hPinned + (src - o->dL0);
-                for (int y = 0; y < D.h; ++y) memcpy(dst[0] + (size_t)y * dst_stride[0], hp + (size_t)y * o->l0pitch, (size_t)D.w);
+                for (int y = 0; y < D.h; ++y) memcpy(dst[0] + (size_t)y * dst_stride[0], hp + (size_t)y * o->plan.l0pitch, (size_t)D.w);
             } else {
                 const int rc = orbx_level_image(o, frame, 0, 0, dst[0], dst_stride[0]);
                 if (rc) return rc;
@@ -1594,7 +1158,7 @@ int orbx_pyramid_fetch(orbx_t* o, int frame, uint8_t* const* dst, const int* dst
 int orbx_pyramid_map(orbx_t* o, int frame, const uint8_t** ptr, int* pitch) {
     if (!o || !ptr || !pitch || frame < 0 || frame >= o->lastBatch || !o->curW) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
-    const Geom& g = o->g;
+    const Geom& g = o->plan.g;
     if (g.pyrFrameBytes > o->capPyrHost) {
         if (o->hPyr) (void)hipHostFree(o->hPyr);
         o->hPyr = nullptr; o->capPyrHost = 0;
@@ -1604,32 +1168,32 @@ int orbx_pyramid_map(orbx_t* o, int frame, const uint8_t** ptr, int* pitch) {
     if (g.nlevels > 1) HIPCHK(hipMemcpyAsync(o->hPyr, o->dPyr + (size_t)frame * g.pyrFrameBytes, g.pyrFrameBytes, hipMemcpyDeviceToHost, o->stream));
     HIPCHK(hipStreamSynchronize(o->stream));
     const u8* src = o->hL0Ptr[frame];
-    const bool staged = o->l0Staged && o->hPinned && src >= o->dL0 && src < o->dL0 + o->capL0 && (size_t)(src - o->dL0) + (size_t)o->l0pitch * g.lv[0].h <= o->capPinned;
-    ptr[0] = staged ? o->hPinned + (src - o->dL0) : nullptr; pitch[0] = staged ? o->l0pitch : 0;
+    const bool staged = o->l0Staged && o->hPinned && src >= o->dL0 && src < o->dL0 + o->capL0 && (size_t)(src - o->dL0) + (size_t)o->plan.l0pitch * g.lv[0].h <= o->capPinned;
+    ptr[0] = staged ? o->hPinned + (src - o->dL0) : nullptr; pitch[0] = staged ? o->plan.l0pitch : 0;
     for (int l = 1; l < g.nlevels; ++l) { ptr[l] = o->hPyr + g.lv[l].off; pitch[l] = g.lv[l].pitch; }
     return ORBX_OK;
 }
 
 void orbx_scale_tables(const orbx_t* o, float* sf, float* inv_sf, float* sig2, float* inv_sig2) {
-    for (int i = 0; i < o->nlevels; ++i) {
-        if (sf) sf[i] = o->sf[i];
-        if (inv_sf) inv_sf[i] = o->invsf[i];
-        if (sig2) sig2[i] = o->sig2[i];
-        if (inv_sig2) inv_sig2[i] = o->invsig2[i];
+    for (int i = 0; i < o->cfg.nlevels; ++i) {
+        if (sf) sf[i] = o->tab.sf[i];
+        if (inv_sf) inv_sf[i] = o->tab.invsf[i];
+        if (sig2) sig2[i] = o->tab.sig2[i];
+        if (inv_sig2) inv_sig2[i] = o->tab.invsig2[i];
     }
 }
 
 int orbx_features_per_level(const orbx_t* o, int* nfeat) {
     if (!o) return ORBX_E_INVALID;
-    for (int i = 0; i < o->nlevels; ++i) nfeat[i] = o->nfeat[i];
-    return o->nlevels;
+    for (int i = 0; i < o->cfg.nlevels; ++i) nfeat[i] = o->tab.nfeat[i];
+    return o->cfg.nlevels;
 }
 
 int orbx_level_candidates(orbx_t* o, int frame, int level, int32_t* xyr, int cap) {
-    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->nlevels) return ORBX_E_INVALID;
+    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->cfg.nlevels) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
     HIPCHK(hipStreamSynchronize(o->stream));
-    const Geom& g = o->g;
+    const Geom& g = o->plan.g;
     const LevelDesc& D = g.lv[level];
     std::vector<u32> cnt(D.nCells), ent((size_t)D.nCells * D.slotCap);
     HIPCHK(hipMemcpy(cnt.data(), o->dCandCnt + (size_t)frame * g.totalCells + D.cellBase, sizeof(u32) * D.nCells, hipMemcpyDeviceToHost));
@@ -1645,10 +1209,10 @@ int orbx_level_candidates(orbx_t* o, int frame, int level, int32_t* xyr, int cap
 }
 
 int orbx_level_selected(orbx_t* o, int frame, int level, int32_t* xyr, int cap) {
-    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->nlevels) return ORBX_E_INVALID;
+    if (!o || frame < 0 || frame >= o->lastBatch || level < 0 || level >= o->cfg.nlevels) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
     HIPCHK(hipStreamSynchronize(o->stream));
-    const Geom& g = o->g;
+    const Geom& g = o->plan.g;
     const LevelDesc& D = g.lv[level];
     u32 n = 0;
     HIPCHK(hipMemcpy(&n, o->dSelCnt + frame * g.nlevels + level, sizeof(u32), hipMemcpyDeviceToHost));
@@ -1863,8 +1427,8 @@ int orbx_clahe(orbx_t* o, const uint8_t* const* src, int nimg, int w, int h, int
 
 int64_t orbx_algorithmic_bytes(const orbx_t* o, int64_t* fused_lower_bound) {
     if (!o) return ORBX_E_INVALID;
-    if (fused_lower_bound) *fused_lower_bound = o->fusedBytes;
-    return o->algBytes;
+    if (fused_lower_bound) *fused_lower_bound = o->plan.fusedBytes;
+    return o->plan.algBytes;
 }
 
 // internal (not part of include/orbx.h): device pointers of the pyramid levels of batch slot `frame`, used by the
@@ -1874,14 +1438,14 @@ int orbx_internal_levels(orbx_t* o, int frame, int* nlevels, const uint8_t** ptr
     if (!o || frame < 0 || frame >= o->lastBatch) return ORBX_E_INVALID;
     HIPCHK(hipSetDevice(o->device));
     HIPCHK(hipStreamSynchronize(o->stream));
-    *nlevels = o->nlevels; *device = o->device;
-    for (int l = 0; l < o->nlevels; ++l) {
-        const LevelDesc& D = o->g.lv[l];
+    *nlevels = o->cfg.nlevels; *device = o->device;
+    for (int l = 0; l < o->cfg.nlevels; ++l) {
+        const LevelDesc& D = o->plan.g.lv[l];
         if (l == 0) {
             ptr[0] = o->hL0Ptr[frame];
-            pitch[0] = (ptr[0] >= o->dL0 && ptr[0] < o->dL0 + o->capL0) ? o->l0pitch : o->lastL0Pitch;
-        } else { ptr[l] = o->dPyr + (size_t)frame * o->g.pyrFrameBytes + D.off; pitch[l] = D.pitch; }
-        w[l] = D.w; h[l] = D.h; sf[l] = o->sf[l]; isf[l] = o->invsf[l];
+            pitch[0] = (ptr[0] >= o->dL0 && ptr[0] < o->dL0 + o->capL0) ? o->plan.l0pitch : o->lastL0Pitch;
+        } else { ptr[l] = o->dPyr + (size_t)frame * o->plan.g.pyrFrameBytes + D.off; pitch[l] = D.pitch; }
+        w[l] = D.w; h[l] = D.h; sf[l] = o->tab.sf[l]; isf[l] = o->tab.invsf[l];
     }
     return ORBX_OK;
 }
@@ -1891,9 +1455,9 @@ int orbx_internal_levels(orbx_t* o, int frame, int* nlevels, const uint8_t** ptr
 int orbx_internal_batch_layout(orbx_t* o, const uint8_t* const** l0tab, int* l0pitch, const uint8_t** pyr, size_t* frameBytes,
                                int* nlevels, int* off, int* pitch, int* w, int* h, float* sf, float* isf, int* device, int* maxBatch, int* kpCap) {
     if (!o || !o->curW) return ORBX_E_INVALID;
-    *l0tab = o->dL0Ptr; *l0pitch = o->lastL0Pitch ? o->lastL0Pitch : o->l0pitch; *pyr = o->dPyr; *frameBytes = o->g.pyrFrameBytes;
-    *nlevels = o->nlevels; *device = o->device; *maxBatch = o->maxBatch; *kpCap = o->g.kpCap;
-    for (int l = 0; l < o->nlevels; ++l) { const LevelDesc& D = o->g.lv[l]; off[l] = D.off; pitch[l] = D.pitch; w[l] = D.w; h[l] = D.h; sf[l] = o->sf[l]; isf[l] = o->invsf[l]; }
+    *l0tab = o->dL0Ptr; *l0pitch = o->lastL0Pitch ? o->lastL0Pitch : o->plan.l0pitch; *pyr = o->dPyr; *frameBytes = o->plan.g.pyrFrameBytes;
+    *nlevels = o->cfg.nlevels; *device = o->device; *maxBatch = o->cfg.maxBatch; *kpCap = o->plan.g.kpCap;
+    for (int l = 0; l < o->cfg.nlevels; ++l) { const LevelDesc& D = o->plan.g.lv[l]; off[l] = D.off; pitch[l] = D.pitch; w[l] = D.w; h[l] = D.h; sf[l] = o->tab.sf[l]; isf[l] = o->tab.invsf[l]; }
     return ORBX_OK;
 }
 

@@ -16,49 +16,18 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "orbx_plan.h"                                      // the records the host planner fills, and the constants it shares with the kernels
 
 namespace orbxk {
 
-typedef uint32_t u32;
-typedef uint16_t u16;
-typedef uint8_t u8;
-
+// (u32, u16, u8: orbx_plan.h)
 typedef unsigned short us2 __attribute__((ext_vector_type(2)));
 typedef short ss2 __attribute__((ext_vector_type(2)));
-struct RzTab { int s; short a0, a1; };                     // source index + two Q11 taps (8 bytes)
-
-struct LevelDesc {                                         // one pyramid level of the current geometry
-    int w, h, pitch;
-    int off;                                               // byte offset inside a frame's pyramid slab (levels >= 1)
-    int boff, btpr;                                        // blurred copy: byte offset inside a frame's blurred slab; tiles per tile row (tiled layout)
-    int rzx, rzy;                                          // offsets into the resize tap tables
-    int cellBase, nCells;                                  // active FAST cells of this level in the cell table
-    int slotBase, slotCap;                                 // candidate slots: slotBase + cell*slotCap + k
-    int N, nIni, qtW, qtH;                                 // quadtree target, roots, extent (maxX-minX, maxY-minY)
-    float hX;
-    int selBase, selCap;                                   // quadtree output slots inside a frame
-    float sf;                                              // mvScaleFactor[level]
-    float patch;                                           // (float)(int)(31*sf)
-};
-
-struct CellInfo {                                          // one FAST cell (sub-image handed to cv::FAST)
-    short level, x0, y0, cw, ch, addx, addy, pad;
-    int slot;                                              // index of slot 0 of this cell within the frame
-    int cnt;                                               // index of the count word within the frame
-};
+// (RzTab, LevelDesc, CellInfo: orbx_plan.h)
 
 struct TileInfo { short level, x0, y0, pad; };            // blur tiles
 
-struct Geom {                                              // kernel argument block (passed by value)
-    int nlevels, w0, h0;
-    int iniTh, minTh, lowTh;
-    int totalCells, totalSlots, totalSel, kpCap;
-    int nodeCap, sortCap;
-    size_t pyrFrameBytes;                                  // per-frame slab holding levels 1..L-1 (and a copy slot for 0)
-    size_t blrFrameBytes;                                  // per-frame slab of the blurred levels
-    int blurTiled;                                         // blurred levels are stored as 16 x 8-px tiles (one 128-byte line each), see k_blur3
-    LevelDesc lv[12];
-};
+// (Geom, the kernel argument block passed by value: orbx_plan.h)
 
 __device__ __forceinline__ us2 as_us2(u32 v) { return __builtin_bit_cast(us2, v); }
 __device__ __forceinline__ u32 as_u32(us2 v) { return __builtin_bit_cast(u32, v); }
@@ -208,21 +177,7 @@ __global__ __launch_bounds__(256) void k_resize(Geom g, const u8* const* l0, int
 //   * One launch per level over a flat list of waves: full tasks x frames, then packed tasks x ceil(frames / pack).
 //   * All source rows of a task are in flight before any arithmetic.
 // ------------------------------------------------------------------------------------------------
-#define RZ_R 8
-#define RZ_SRC 12                                          // source rows one task may touch: what RZ_R rows need at scale factors up to 1.5 (host checks)
-struct RzX4 { int bs; u8 o[4]; u32 a[4]; };                // per destination dword: byte offset of the first tap, tap offsets from it (<= 6), (2*a0 | 2*a1<<16): DOUBLED Q11 taps
-struct alignas(64) RzTask {                                // 32 words
-    int g0, y0;                                            // first destination dword and row
-    int pack, gw, gmul;                                    // frames per wave, lanes per frame (64: full tile), ceil(65536 / gw)
-    int sFirst, nsrc;                                      // first source row, source rows (2 .. RZ_SRC)
-    u32 emit;                                              // bit j: source row sFirst + j completes a destination row (bit 0 is never set)
-    int dpitch, doff, x4base;                              // destination level: pitch, offset in the slab, first entry of the x4 table
-    int spitch, soff;                                      // source level (levels >= 1; level 0 is the caller's)
-    int pad[3];
-    u32 taps[16];                                          // [j]: a0 | a1 << 16 of the destination row that source row j completes
-};
-static_assert(sizeof(RzTask) == 128 && RZ_SRC == 12, "RzTask is read as 32 scalar words, of which 13 + 11 are pinned");
-struct RzLaunch { u32 nFull, nPack, nimg, nFullW, nWaves, mFull, mPack; };   // mX = floor(2^32 / nX) + 1: n / nX = umulhi(n, mX) while n * nX < 2^32 (host checks)
+// (RZ_R, RZ_SRC, RzX4, RzTask, RzLaunch: orbx_plan.h)
 
 __device__ __forceinline__ RzX4 rz_x4_load(uintptr_t table, u32 i) {                 // table: a global address that has been through an asm statement
     RzX4 X;
@@ -348,9 +303,7 @@ __global__ __launch_bounds__(256) void k_resize2(const u8* const* l0, int l0pitc
 }
 
 #ifdef ORBX_AB   /* k_resize2p: A/B reference (8-row tasks of one frame, row taps reloaded per row), not in the product library */
-#define RZP_R 8
-#define RZP_SRC 12                                         // source rows one task may touch (host checks)
-struct RzTaskP { short level, g0, y0, pad; };
+// (RZP_R, RZP_SRC, RzTaskP: orbx_plan.h)
 
 __global__ __launch_bounds__(256) void k_resize2p(Geom g, const u8* const* l0, int l0pitch, u8* pyr,
                                                   const RzTaskP* __restrict__ tasks, int ntasks,
@@ -505,7 +458,7 @@ __device__ __forceinline__ ss2 fast_score16x2(const u8* ta, const u8* tb, int p)
 // local maxima is threshold independent: keypoints@ini = maxima with S >= ini, else maxima with S >= min.
 // Output: packed (x | y<<12 | S<<24) in row-major order into the cell's slot array + its count.
 // ------------------------------------------------------------------------------------------------
-#define ORBX_FAST_TILE 6400
+// (ORBX_FAST_TILE: orbx_plan.h)
 __device__ __forceinline__ void fast_cell_block(const Geom& g, const u8* const* l0, int l0pitch, const u8* pyr,
                                                 const CellInfo* __restrict__ cells, u32* candCnt, u32* candEnt,
                                                 int* err, int cellIdx, int frame) {
@@ -602,9 +555,7 @@ __global__ __launch_bounds__(256) void k_fast_fix(Geom g, const u8* const* l0, i
     if (threadIdx.x == 0 && atomicAdd(&ovf[1], 1u) == gridDim.x - 1) { ovf[0] = 0; ovf[1] = 0; }
 }
 
-struct StripInfo { short level, ncell, x0, y0, w, h, xal, lp; int cell0; };   // lp = LDS tile pitch in bytes
-
-#define F3_NT 256
+// (StripInfo, F3_NT: orbx_plan.h)
 #ifndef F3_XCD
 #define F3_XCD 1                                            // neighbouring strips (they share 6 columns and whole lines) on one XCD
 #endif
@@ -900,16 +851,7 @@ __global__ __launch_bounds__(F3_NT) void k_fast3(Geom g, const u8* const* l0, in
 // Queue entry (u16): row << 9 | xs << 2 | 3, xs = column relative to the cell's first 4-aligned column (so xs = 8 * col + k and
 // the low five bits are the sparse mask's bit index 4k + 3: the append loop ORs the bit position in, no shift).
 // ------------------------------------------------------------------------------------------------
-struct CellAux {                                            // 32 bytes, read with one scalar load
-    u32 tab;                                                // first F4Item of the cell's shape table: [nit][64]
-    int slot, cnt;                                          // as CellInfo
-    u16 base;                                               // tile byte offset of (row 0, xs 0): 3 * pitch + s4
-    u16 nit;                                                // quick-pass iterations (0: empty window)
-    short outx, outy;                                       // packed output coordinates of (row 0, xs 0)
-    u16 xlo, xhi;                                           // xs of the window's first / last column
-    u32 pad[2];
-};
-struct F4Item { u32 mask; u32 offq; };                      // mask: pixel k of the lane's 8 inside the window -> bit 4k+3; offq: lo16 = row * pitch + 8 * col, hi16 = row << 9 | col << 5
+// (CellAux, F4Item: orbx_plan.h)
 
 // LDS accesses of k_fast4 by ABSOLUTE 32-bit LDS address (base of the dynamic allocation folded into wave-uniform offsets once):
 // `shared_array + offset` makes the compiler add the array's (zero) address per access and widen pointer arithmetic to 64 bits.
@@ -2220,56 +2162,12 @@ __device__ __forceinline__ int reflect101(int p, int n) {   // valid for -n < p 
 // geometry -- Th on (level, strip), Tv on (level, tile row) -- and are tabulated by the host in fragment order when the
 // geometry is built (built in the kernel they cost more than the tiles themselves); border folds are just table entries.
 // ------------------------------------------------------------------------------------------------
-#define B3_ROWS 26
+// (B3_ROWS, B3_CHUNK, Blur3Task, b3_toep, b3_build_th, b3_build_tv: orbx_plan.h)
 #ifndef B3_XCD
 #define B3_XCD 1                                            // adjacent column groups on one XCD: their shared halo lines hit in L2
 #endif
-#ifndef B3_CHUNK
-#define B3_CHUNK 8
-#endif
-struct Blur3Task { short level, x0, t0, nt; int th, tv; };   // th / tv: entries of the weight tables (tv: of tile t0)
 typedef int b3_i32x4 __attribute__((ext_vector_type(4)));
 typedef int b3_i32x16 __attribute__((ext_vector_type(16)));
-
-// weight of source position p in output position `out` of an n-long line: sum_i [reflect101(out + i - 3) == p] * K[i]
-// (host side: the weight fragments are tabulated per column strip and per tile row when the geometry is built)
-static inline int b3_toep(int p, int out, int n) {
-    const int K[7] = {18, 34, 48, 56, 48, 34, 18};
-    int wsum = 0;
-    for (int i = 0; i < 7; ++i) {
-        int q = out + i - 3;
-        q = q < 0 ? -q : q;
-        q = q >= n ? 2 * n - 2 - q : q;
-        wsum += q == p ? K[i] : 0;
-    }
-    return wsum;
-}
-// pass-1 weights (B operand) of the strip at x0: [k-step s][lane] uint4; lane (r, hh) holds column x0 + r, element j of
-// k-step s <-> pixel x0 - 16 + 32 s + 16 hh + j
-static inline void b3_build_th(int x0, int w, u32* out /* [2][64][4] */) {
-    for (int s = 0; s < 2; ++s)
-        for (int lane = 0; lane < 64; ++lane)
-            for (int e = 0; e < 4; ++e) {
-                const int r = lane & 31, hh = lane >> 5;
-                u32 v = 0;
-                for (int b = 0; b < 4; ++b) v |= (u32)b3_toep(x0 - 16 + 32 * s + 16 * hh + 4 * e + b, x0 + r, w) << (8 * b);
-                out[(s * 64 + lane) * 4 + e] = v;
-            }
-}
-// pass-2 weights (A operand) of the tile at y0: [lane] uint4; lane (r, hh) holds output row y0 + r (26 valid), element j <->
-// H row (j&3) + 8 (j>>2) + 4 hh of the tile = image row y0 - 3 + that (the register order of the pass-1 accumulator)
-static inline void b3_build_tv(int y0, int h, u32* out /* [64][4] */) {
-    for (int lane = 0; lane < 64; ++lane)
-        for (int e = 0; e < 4; ++e) {
-            const int r = lane & 31, hh = lane >> 5;
-            u32 v = 0;
-            for (int b = 0; b < 4; ++b) {
-                const int j = 4 * e + b, krow = (j & 3) + 8 * (j >> 2) + 4 * hh;
-                v |= (r < B3_ROWS ? (u32)b3_toep(y0 - 3 + krow, y0 + r, h) : 0u) << (8 * b);
-            }
-            out[lane * 4 + e] = v;
-        }
-}
 
 #define B3_OROW 144                                        // output staging row stride (128 B + 16 B pad)
 #define B3_LROW 176                                        // LDS row stride: 160 B of pixels + 16 B pad (b128 reads conflict-free)
@@ -2411,10 +2309,7 @@ __global__ __launch_bounds__(256) void k_blur3(Geom g, const u8* const* l0, int 
 #endif
 }
 
-#define BL_R 32
-struct BlurTask { short level, g0, y0, pad; };            // g0 = first dword column of the strip, y0 = first output row
-
-struct BlurSel { u32 selB[12], selC[12]; };               // per level: right-edge fix-up selectors
+// (BL_R, BlurTask, BlurSel: orbx_plan.h)
 
 #ifdef ORBX_AB   /* A/B reference, not in the product library */
 __global__ __launch_bounds__(256) void k_blur2(Geom g, const u8* const* l0, int l0pitch, const u8* pyr, u8* blr,
@@ -2534,7 +2429,7 @@ __device__ __forceinline__ float fast_atan2_deg(float y, float x) {
 #define OD_FN __device__ __forceinline__
 #include "od_sincos.h"
 
-struct Umax { int v[16]; };
+// (Umax: orbx_plan.h)
 
 #ifdef ORBX_AB   /* A/B reference, not in the product library */
 __global__ __launch_bounds__(256) void k_orient_desc(Geom g, const u8* const* l0, int l0pitch, const u8* pyr,
@@ -2606,7 +2501,7 @@ __global__ __launch_bounds__(256) void k_orient_desc(Geom g, const u8* const* l0
 #endif
 #define OD_PPITCH 40
 #define OD_PPITCH_T 48                                     // tiled blurred level: 6 aligned 8-byte pieces per patch row
-#define OD_WTAB (17 * 8)                                   // IC_Angle weight table: [|v| (16 = zero row)][dword of the 32-byte patch row]
+// (OD_WTAB: orbx_plan.h)
 #define OD_PATCH (37 * OD_PPITCH)
 #define OD_PATCH_T (37 * OD_PPITCH_T)
 __global__ __launch_bounds__(256) void k_orient_desc2(Geom g, const u8* const* l0, int l0pitch, const u8* pyr,

@@ -172,7 +172,7 @@ def fast_cells(w, h):
 
 def fast_queue_caps(level_sizes):
     """Entries of the survivor queue a wave of k_fast4 has for a cell, per level: a restatement of the host code that sizes it
-    (orb-slam3_amd/csrc/orbx_api.hip, "strips for k_fast3" and "FAST launch groups"; 256 threads = 4 waves per workgroup).  A cell whose
+    (orb-slam3_amd/csrc/orbx_plan.h, "strips for k_fast3" and "FAST launch groups"; 256 threads = 4 waves per workgroup).  A cell whose
     quick-test survivors outnumber it is redone by k_fast_fix.  Level 0 and the fine levels get max(512, what lets 7 workgroups share a
     CU's 160 KB), never more than the worst case of their cells; the coarse levels keep the worst case unless 5 workgroups fit at
     >= 3/4 of it.  This is derived from the code, not read from the device: nothing in the product's ABI reports it."""

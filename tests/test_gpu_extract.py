@@ -79,7 +79,7 @@ def test_batch_equals_single(pkg, oracle, synth):
 
 @pytest.mark.parametrize("nframes", [48, 71])
 def test_large_batch_paths(pkg, oracle, synth, nframes):
-    # from ~40 frames of this size on, k_blur3's workgroups walk eight tiles each instead of one (orbx_api.hip: `walk`);
+    # from ~40 frames of this size on, k_blur3's workgroups walk eight tiles each instead of one (orbx_plan.h: `blur_walks`);
     # every frame of such a batch -- odd one out included -- must still equal the oracle
     imgs = [synth.gen_image(752, 480, 900 + (i % 5)) for i in range(nframes - 1)] + [synth.gen_image(752, 480, 3, "lowcontrast")]
     ex = pkg.ORBextractor(1000, max_size=(752, 480), max_batch=len(imgs))

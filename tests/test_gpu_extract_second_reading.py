@@ -78,7 +78,7 @@ def test_single_and_batched_frames_equal_the_reading(pkg, k):
 
 def test_wide_frames_with_small_budgets_return_four_nodes_per_root(pkg):
     """1241 x 376 (four roots) and 2400 x 420 (six) with budgets below 4 * nIni: the first pass of DistributeOctTree splits every root
-    before it looks at N, so a level returns 16 / 24 keypoints -- k_quadtree2's list must hold them (orbx_api.hip: qt2Cap)."""
+    before it looks at N, so a level returns 16 / 24 keypoints -- k_quadtree2's list must hold them (orbx_plan.h: qt2Cap)."""
     for name, n in (("wide_1241_nl1_N4", 16), ("wide_1241_nl1_N7", 16), ("wide_2400_nl1_N11", 24), ("wide_2400_nl1_N15", 24)):
         c = next(c for c in CASES if c["name"] == name)
         ex = make_extractor(pkg, ec.key(c))
@@ -91,9 +91,9 @@ def test_wide_frames_with_small_budgets_return_four_nodes_per_root(pkg):
 
 
 # k_quadtree2 runs 1024 threads per (frame, level) when some level wants >= 512 nodes or the grid is small (frames * levels <= 512),
-# 256 otherwise (orbx_api.hip, "const bool wide").  One frame takes the wide form; 520 one-level / 260 two-level frames the narrow one.
+# 256 otherwise (orbx_plan.h, qt_wide).  One frame takes the wide form; 520 one-level / 260 two-level frames the narrow one.
 def _max_n(k):
-    """maxN of orbx_api.hip: the largest max(N, 4 * nIni) of any level; the wide form is chosen from 512 on."""
+    """maxN of orbx_plan.h: the largest max(N, 4 * nIni) of any level; the wide form is chosen from 512 on."""
     w, h, nf, nl, sf = k[:5]
     budget = sr.features_per_level(nf, sf, nl)
     return max(max(n, 4 * sr.c_round(np.float32(lw - 32) / np.float32(lh - 32))) for n, (lw, lh) in zip(budget, sr.level_sizes(w, h, sf, nl)))

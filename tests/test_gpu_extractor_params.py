@@ -1,6 +1,6 @@
 """The extractor and the batched matchers beyond the default ORB parameters (scaleFactor 1.2, nLevels 8, iniThFAST 20, minThFAST 7).
 
-orbx_create accepts 1..12 levels, any scale factor above 1 and FAST thresholds 1..255, and the host planner (orbx_api.hip) picks
+orbx_create accepts 1..12 levels, any scale factor above 1 and FAST thresholds 1..255, and the host planner (orbx_plan.h) picks
 kernels and table layouts from the geometry those produce: k_resize (the general resize) wherever k_resize2's tap plan is refused,
 other FAST launch-group splits, 12-entry scale tables in the matchers, 4 * nIni quadtree nodes on levels whose budget rounds to 0.
 Every case is bit-exact against the CPU oracle at the same parameters, stage by stage (tests/test_gpu_extract.py::_check).  The
