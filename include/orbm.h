@@ -86,7 +86,12 @@ typedef struct {
 } orbm_frame_t;
 
 /* M14  Frame::AssignFeaturesToGrid + PosInGrid (Frame.cc:446-480, 883-899) on the GPU.
- * grid_start[3073], grid_idx[n] are host outputs; returns the number of keypoints placed. */
+ * grid_start[3073], grid_idx[n] are host outputs; returns the number of keypoints placed.
+ * The limit of the three grid builders (this call, orbm_frame_create, orbm_grid_build_batch_async): n, or cap, <= 65535 keypoints per
+ * frame -- the batched searches' own limit, so every pool row they accept has a grid from here.  Above it this call and
+ * orbm_frame_create return ORBM_E_CAPACITY, orbm_grid_build_batch_async ORBM_E_INVALID.  Up to 8192 keypoints a counting sort over the
+ * 3072 cells, up to 32768 a bitonic sort of cell << 16 | index keys in LDS, above that the counting sort again with every cell list of
+ * more than 64 entries put in order by the whole workgroup (155 666 B of LDS at 65535); the result is the same CSR in each. */
 int orbm_grid_build(orbm_t*, const orbm_kp_t* kps, int n, float min_x, float min_y, float inv_w, float inv_h,
                     int32_t* grid_start, int32_t* grid_idx);
 
@@ -118,7 +123,8 @@ int orbm_search_by_projection_points(orbm_t*, const orbm_frame_t* f, const uint8
 /* ---- frames resident in HBM.  Tracking runs 2-4 searches on the same Frame (TrackWithMotionModel / TrackReferenceKeyFrame,
  * then SearchLocalPoints; Tracking.cc:3002-3211, 3867-3891): orbm_frame_create uploads keypoints, descriptors and mvuRight
  * ONCE (space = ORBM_HOST), or adopts device arrays without copying them (space = ORBM_DEVICE: an extractor's result block,
- * orbx_result_device -- they must stay valid while the frame lives), and builds the 64 x 48 grid (M14) on the device.  The
+ * orbx_result_device -- they must stay valid while the frame lives), and builds the 64 x 48 grid (M14) on the device (n <= 65535,
+ * the builders' limit at orbm_grid_build).  The
  * *_resident searches then send only their queries and get back, per query, the candidate count and the 8 best (distance,
  * visiting-order) candidates -- all the claim replay can look at unless every one of them is blocked, in which case the call
  * falls back to the full candidate lists by itself.  Same arguments and results as M4 / M3 above. */
@@ -244,7 +250,8 @@ int orbm_search_for_triangulation_gated(orbm_t*, int n1, const orbm_kp_t* kps1, 
 
 /* ---- batched, DEVICE-resident forms: frame-to-frame tracking chained behind orbx_extract_batch_async with no host round
  * trip (kps/desc/counts are the extractor's result block, orbx_result_device; all pointers are device pointers).
- * orbm_grid_build_batch_async: M14 for every frame of the block; grid_start [nframes][3073], grid_idx [nframes][cap].
+ * orbm_grid_build_batch_async: M14 for every frame of the block; grid_start [nframes][3073], grid_idx [nframes][cap]; cap <= 65535
+ * (the builders' limit, at orbm_grid_build); frame f holds min(counts[f], cap) keypoints.
  * orbm_track_window_batch_async: for pair p the keypoints of frame q_first+p search frame t_first+p inside the mono
  * SearchByProjection window (centre (x+dx, y+dy), radius th*scale[octave], levels octave-1..octave+1,
  * ORBmatcher.cc:2543-2549): first-minimum best index/distance and runner-up distance per keypoint, [npairs][cap].

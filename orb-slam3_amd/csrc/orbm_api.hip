@@ -82,6 +82,12 @@ struct orbm_dframe {
 };
 
 static inline size_t grid_cs_lds(int n) { return (size_t)(2 * GRID_CELLS + 1) * sizeof(int) + (size_t)std::max(n, 1) * sizeof(unsigned short) + 16; }
+// Above GRID_WIDE_MIN keypoints the grid builders run the WIDE counting form, whose dynamic LDS (155 666 B at 65535, with 2 068 B static
+// beside it: 160 KB hold both) is above 48 KB: the attribute always at the largest legal size, so that a graph captured earlier with
+// bigger rows still launches after a call with smaller ones.
+static inline hipError_t grid_wide_attr(const void* kernel) {
+    return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)grid_cs_lds(65535));
+}
 
 namespace { int knn2_host(orbm* m, const uint8_t* q, int q_stride, const int32_t* nq, const uint8_t* t, int t_stride, const int32_t* nt,
                           int npairs, int32_t* idx2, int32_t* dist2); }
@@ -480,7 +486,6 @@ int orbm_grid_build(orbm_t* m, const orbm_kp_t* kps, int n, float min_x, float m
     if (n > 65535) { set_merr("grid build supports at most 65535 keypoints"); return ORBM_E_CAPACITY; }
     MHIPCHK(hipSetDevice(m->device));
     int n2 = 64; while (n2 < n) n2 <<= 1;
-    if ((size_t)n2 * 4 > 150 * 1024) { set_merr("too many keypoints for the LDS sort"); return ORBM_E_CAPACITY; }
     DevBuf dk, dgs, dgi, dpl;
     arena_reset(m);
     UP(dk, kps, sizeof(KpIn) * n);
@@ -489,7 +494,11 @@ int orbm_grid_build(orbm_t* m, const orbm_kp_t* kps, int n, float min_x, float m
     if (n <= GRID_CS_MAX)
         hipLaunchKernelGGL(k_grid_build_cs, dim3(1), dim3(256), grid_cs_lds(n), m->stream, dk.as<KpIn>(), n, min_x, min_y, inv_w, inv_h,
                            dgs.as<int>(), dgi.as<int>(), dpl.as<int>());
-    else {
+    else if (n > GRID_WIDE_MIN) {
+        MHIPCHK(grid_wide_attr((const void*)k_grid_build_wide));
+        hipLaunchKernelGGL(k_grid_build_wide, dim3(1), dim3(256), grid_cs_lds(n), m->stream, dk.as<KpIn>(), n, min_x, min_y, inv_w, inv_h,
+                           dgs.as<int>(), dgi.as<int>(), dpl.as<int>());
+    } else {
         MHIPCHK(hipFuncSetAttribute((const void*)k_grid_build, hipFuncAttributeMaxDynamicSharedMemorySize, n2 * 4));
         hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), (size_t)n2 * 4, m->stream, dk.as<KpIn>(), n, n2, min_x, min_y, inv_w, inv_h,
                            dgs.as<int>(), dgi.as<int>(), dpl.as<int>());
@@ -704,7 +713,6 @@ int orbm_frame_create(orbm_t* m, int space, int n, const orbm_kp_t* kps, const u
     *out = nullptr;
     if (n > 65535) { set_merr("a resident frame holds at most 65535 keypoints"); return ORBM_E_CAPACITY; }
     int n2 = 64; while (n2 < n) n2 <<= 1;
-    if ((size_t)n2 * 4 > 150 * 1024) { set_merr("too many keypoints for the LDS sort"); return ORBM_E_CAPACITY; }
     MHIPCHK(hipSetDevice(m->device));
     orbm_dframe* f = new orbm_dframe;
     f->device = m->device; f->n = n; f->min_x = min_x; f->min_y = min_y; f->inv_w = inv_w; f->inv_h = inv_h;
@@ -734,7 +742,10 @@ int orbm_frame_create(orbm_t* m, int space, int n, const orbm_kp_t* kps, const u
     if (e == hipSuccess && n > 0) {
         if (n <= GRID_CS_MAX)
             hipLaunchKernelGGL(k_grid_build_cs, dim3(1), dim3(256), grid_cs_lds(n), m->stream, f->dKps, n, min_x, min_y, inv_w, inv_h, f->dGs, f->dGi, dPlaced);
-        else {
+        else if (n > GRID_WIDE_MIN) {
+            e = grid_wide_attr((const void*)k_grid_build_wide);
+            if (e == hipSuccess) hipLaunchKernelGGL(k_grid_build_wide, dim3(1), dim3(256), grid_cs_lds(n), m->stream, f->dKps, n, min_x, min_y, inv_w, inv_h, f->dGs, f->dGi, dPlaced);
+        } else {
             if (n2 * 4 > 48 * 1024) e = hipFuncSetAttribute((const void*)k_grid_build, hipFuncAttributeMaxDynamicSharedMemorySize, n2 * 4);
             if (e == hipSuccess) hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(256), (size_t)n2 * 4, m->stream, f->dKps, n, n2, min_x, min_y, inv_w, inv_h, f->dGs, f->dGi, dPlaced);
         }
@@ -1106,12 +1117,15 @@ int orbm_grid_build_batch_async(orbm_t* m, const orbm_kp_t* kps, const int32_t* 
     if (!m || !kps || !counts || !grid_start || !grid_idx || nframes < 1 || cap < 1 || cap > 65535) return ORBM_E_INVALID;
     MHIPCHK(hipSetDevice(m->device));
     int n2 = 64; while (n2 < cap) n2 <<= 1;
-    if ((size_t)n2 * 4 > 150 * 1024) { set_merr("too many keypoints per frame for the LDS sort"); return ORBM_E_CAPACITY; }
-    if (cap > GRID_CS_MAX && n2 * 4 > 48 * 1024) MHIPCHK(hipFuncSetAttribute((const void*)k_grid_build_batch, hipFuncAttributeMaxDynamicSharedMemorySize, n2 * 4));
+    if (cap > GRID_WIDE_MIN) MHIPCHK(grid_wide_attr((const void*)k_grid_build_batch_wide));
+    else if (cap > GRID_CS_MAX && n2 * 4 > 48 * 1024) MHIPCHK(hipFuncSetAttribute((const void*)k_grid_build_batch, hipFuncAttributeMaxDynamicSharedMemorySize, n2 * 4));
     MHIPCHK(rec_time(m, m->e2));
     m->gridFirst = true;                                                    // orbm_last_timing then spans grid build + the next kernel
     if (cap <= GRID_CS_MAX)
         hipLaunchKernelGGL(k_grid_build_batch_cs, dim3(nframes), dim3(256), grid_cs_lds(cap), m->stream, (const KpIn*)kps, counts, cap,
+                           min_x, min_y, inv_w, inv_h, grid_start, grid_idx);
+    else if (cap > GRID_WIDE_MIN)
+        hipLaunchKernelGGL(k_grid_build_batch_wide, dim3(nframes), dim3(256), grid_cs_lds(cap), m->stream, (const KpIn*)kps, counts, cap,
                            min_x, min_y, inv_w, inv_h, grid_start, grid_idx);
     else
         hipLaunchKernelGGL(k_grid_build_batch, dim3(nframes), dim3(256), (size_t)n2 * 4, m->stream, (const KpIn*)kps, counts, cap, n2,

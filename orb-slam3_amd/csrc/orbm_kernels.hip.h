@@ -258,10 +258,40 @@ struct KpIn { float x, y, size, angle, response; int octave, class_id; };
 // Counting sort form of the grid build (n <= GRID_CS_MAX): cell histogram in LDS -> exclusive scan over the 3072 cells ->
 // scatter into a per-cell cursor -> each cell's short list sorted by keypoint index (insertion order of the reference,
 // Frame.cc:446-480: i ascending) -> written out.  One pass over the keypoints instead of a 66-stage bitonic sort of n keys.
+// Above GRID_WIDE_MIN keypoints (where the bitonic form's n2 = 65536 keys no longer fit the LDS) the counting form runs again as
+// WIDE: the same histogram, scan and scatter, but a cell list longer than GRID_WIDE_SHORT is put in order by the whole workgroup
+// (grid_sort_list) instead of by one lane, so that the time is bounded whatever the keypoints' spread.
 #define GRID_CS_MAX 8192
 #define GRID_CELLS (64 * 48)
+#define GRID_WIDE_MIN 32768
+#define GRID_WIDE_SHORT 64
+#define GRID_WIDE_LONG_CELLS 1024                              // cells of more than 64 entries among at most 65535 keypoints: <= 1008
+
+// Ascending in-place sort of p[0, len) (distinct keys) by the 256 threads of the workgroup; every thread calls it with the same
+// arguments.  The bitonic network in its one-direction form (first step of a merge pairs i with i ^ (k - 1), the others i with i ^ j,
+// the smaller key always to the lower index), so that positions at and past len stand for +inf keys that no exchange ever moves and
+// are never touched.  sum over k = 2 .. len2 of log2 k steps (136 at len = 65535), each ceil(len / 256) iterations per thread.
+__device__ __forceinline__ void grid_sort_list(unsigned short* p, int len) {
+    const int tid = threadIdx.x;
+    for (int k = 2; (k >> 1) < len; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const int mask = j == (k >> 1) ? k - 1 : j;
+            for (int i = tid; i < len; i += 256) {
+                const int o = i ^ mask;
+                if (o > i && o < len) {
+                    const unsigned short a = p[i], b = p[o];
+                    if (a > b) { p[i] = b; p[o] = a; }
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+template <bool WIDE>
 __device__ __forceinline__ int grid_build_counting(const KpIn* __restrict__ kp, int n, float min_x, float min_y, float inv_w, float inv_h,
-                                                   int* __restrict__ gs, int* __restrict__ gi, unsigned char* smem) {
+                                                   int* __restrict__ gs, int* __restrict__ gi, unsigned char* smem,
+                                                   int* s_nlong = nullptr, unsigned short* s_long = nullptr) {   // WIDE: the long cells, [1] and [GRID_WIDE_LONG_CELLS] in LDS
     int* hist = (int*)smem;                                    // [GRID_CELLS + 1] counts -> starts
     int* cur = hist + GRID_CELLS + 1;                          // [GRID_CELLS] fill cursors
     unsigned short* lgi = (unsigned short*)(cur + GRID_CELLS); // [n] indices, cell by cell
@@ -299,8 +329,17 @@ __device__ __forceinline__ int grid_build_counting(const KpIn* __restrict__ kp, 
         if (px >= 0 && px < 64 && py >= 0 && py < 48) lgi[atomicAdd(&cur[px * 48 + py], 1)] = (unsigned short)i;
     }
     __syncthreads();
+    if (WIDE) {
+        if (tid == 0) *s_nlong = 0;
+        __syncthreads();
+    }
     for (int c = tid; c < GRID_CELLS; c += 256) {                            // restore insertion order inside every cell (lists are short)
         const int a = hist[c], b = hist[c + 1];
+        if (WIDE && b - a > GRID_WIDE_SHORT) {                               // ... and where one is not, it is left to the whole workgroup
+            const int k = atomicAdd(s_nlong, 1);
+            if (k < GRID_WIDE_LONG_CELLS) s_long[k] = (unsigned short)c;
+            continue;
+        }
         for (int i = a + 1; i < b; ++i) {
             const unsigned short v = lgi[i];
             int j = i - 1;
@@ -309,13 +348,20 @@ __device__ __forceinline__ int grid_build_counting(const KpIn* __restrict__ kp, 
         }
     }
     __syncthreads();
+    if (WIDE) {
+        const int nlong = min(*s_nlong, GRID_WIDE_LONG_CELLS);                // the same for every thread: the barriers inside are uniform
+        for (int k = 0; k < nlong; ++k) {
+            const int c = s_long[k];
+            grid_sort_list(lgi + hist[c], hist[c + 1] - hist[c]);
+        }
+    }
     for (int i = tid; i < total; i += 256) gi[i] = (int)lgi[i];
     return total;
 }
 __global__ __launch_bounds__(256) void k_grid_build_cs(const KpIn* __restrict__ kps, int n, float min_x, float min_y, float inv_w, float inv_h,
                                                        int* __restrict__ grid_start, int* __restrict__ grid_idx, int* __restrict__ placed) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
-    const int total = grid_build_counting(kps, n, min_x, min_y, inv_w, inv_h, grid_start, grid_idx, gsm);
+    const int total = grid_build_counting<false>(kps, n, min_x, min_y, inv_w, inv_h, grid_start, grid_idx, gsm);
     if (threadIdx.x == 0) *placed = total;
 }
 __global__ __launch_bounds__(256) void k_grid_build_batch_cs(const KpIn* __restrict__ kps, const int* __restrict__ counts, int cap,
@@ -323,8 +369,27 @@ __global__ __launch_bounds__(256) void k_grid_build_batch_cs(const KpIn* __restr
                                                              int* __restrict__ grid_start, int* __restrict__ grid_idx) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
     const int frame = blockIdx.x;
-    (void)grid_build_counting(kps + (size_t)frame * cap, min(counts[frame], cap), min_x, min_y, inv_w, inv_h,
-                              grid_start + (size_t)frame * (GRID_CELLS + 1), grid_idx + (size_t)frame * cap, gsm);
+    (void)grid_build_counting<false>(kps + (size_t)frame * cap, min(counts[frame], cap), min_x, min_y, inv_w, inv_h,
+                                     grid_start + (size_t)frame * (GRID_CELLS + 1), grid_idx + (size_t)frame * cap, gsm);
+}
+// the WIDE forms, for n / cap above GRID_WIDE_MIN
+__global__ __launch_bounds__(256) void k_grid_build_wide(const KpIn* __restrict__ kps, int n, float min_x, float min_y, float inv_w, float inv_h,
+                                                         int* __restrict__ grid_start, int* __restrict__ grid_idx, int* __restrict__ placed) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
+    __shared__ int s_nlong;
+    __shared__ unsigned short s_long[GRID_WIDE_LONG_CELLS];
+    const int total = grid_build_counting<true>(kps, n, min_x, min_y, inv_w, inv_h, grid_start, grid_idx, gsm, &s_nlong, s_long);
+    if (threadIdx.x == 0) *placed = total;
+}
+__global__ __launch_bounds__(256) void k_grid_build_batch_wide(const KpIn* __restrict__ kps, const int* __restrict__ counts, int cap,
+                                                               float min_x, float min_y, float inv_w, float inv_h,
+                                                               int* __restrict__ grid_start, int* __restrict__ grid_idx) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char gsm[];
+    __shared__ int s_nlong;
+    __shared__ unsigned short s_long[GRID_WIDE_LONG_CELLS];
+    const int frame = blockIdx.x;
+    (void)grid_build_counting<true>(kps + (size_t)frame * cap, max(min(counts[frame], cap), 0), min_x, min_y, inv_w, inv_h,
+                                    grid_start + (size_t)frame * (GRID_CELLS + 1), grid_idx + (size_t)frame * cap, gsm, &s_nlong, s_long);
 }
 
 __global__ __launch_bounds__(256) void k_grid_build(const KpIn* __restrict__ kps, int n, int n2, float min_x, float min_y,
