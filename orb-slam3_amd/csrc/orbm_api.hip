@@ -317,13 +317,37 @@ struct RotHist {                                             // rotation-consist
         for (int i = 0; i < ORBM_HISTO_LENGTH; ++i) sz[i] = (int)bins[i].size();
         orbm_three_maxima(sz, ORBM_HISTO_LENGTH, ind);
     }
+    // fn(entry) for every entry of every bin outside the three maxima, in bin order then insertion order (e.g. :2694-2707); an
+    // entry that sits in the histogram twice is handed over twice
+    template <class Fn> void cull(Fn fn) const {
+        int ind[3];
+        maxima(ind);
+        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b)
+            if (b != ind[0] && b != ind[1] && b != ind[2])
+                for (int e : bins[b]) fn(e);
+    }
 };
 
-// runs k_window for nq windows against frame f; candidate lists come back in host vectors
-int window_pass(orbm* m, const orbm_frame_t* f, int nq, const float* qx, const float* qy, const float* qr,
-                const int32_t* minl, const int32_t* maxl, const float* qur, const float* qer, const uint8_t* qdesc,
-                int& cap, std::vector<int>& cnt, std::vector<int>& idx, std::vector<int>& dist, bool retry = false, const orbm_dframe* df = nullptr) {
+// The queries of one window pass: centre, radius (r < 0: no window), level band [lo, hi] (hi < 0: no upper bound), the stereo gate's
+// expected uright and tolerance (both may be NULL; er < 0: no gate) and the descriptors.
+struct WindowQuery { int nq; const float *x, *y, *r; const int32_t *lo, *hi; const float *ur, *er; const uint8_t* desc; };
+
+// the three tables a search computes per query
+struct WindowTables {
+    std::vector<float> r; std::vector<int32_t> lo, hi;
+    explicit WindowTables(int nq) : r(nq), lo(nq), hi(nq) {}
+    void skip(int i) { r[i] = -1.f; lo[i] = 0; hi[i] = -1; }                // a query that is not searched: an empty window
+    void set(int i, float radius, int l, int h) { r[i] = radius; lo[i] = l; hi[i] = h; }
+    WindowQuery query(const float* x, const float* y, const float* ur, const float* er, const uint8_t* desc) const {
+        return WindowQuery{(int)r.size(), x, y, r.data(), lo.data(), hi.data(), ur, er, desc};
+    }
+};
+
+// runs k_window for q.nq windows against frame f; candidate lists come back in host vectors
+int window_pass(orbm* m, const orbm_frame_t* f, const WindowQuery& q, int& cap, std::vector<int>& cnt, std::vector<int>& idx, std::vector<int>& dist,
+                bool retry = false, const orbm_dframe* df = nullptr) {
     // `cap` in: capacity of a window on the device; out: row stride of idx / dist (= the longest candidate list, >= 1)
+    const int nq = q.nq;
     cnt.assign(nq, 0);
     if (nq == 0 || f->n == 0) return ORBM_OK;
     if (const char* e = retry ? nullptr : ab_env("ORBM_WINDOW_CAP")) cap = std::max(1, std::min(cap, atoi(e)));   // test knob: a small first capacity forces the retry below
@@ -336,11 +360,11 @@ int window_pass(orbm* m, const orbm_frame_t* f, int nq, const float* qx, const f
         UP(dgs, f->grid_start, sizeof(int) * (ORBM_GRID_COLS * ORBM_GRID_ROWS + 1));
         UP(dgi, f->grid_idx, sizeof(int) * f->n);
     }
-    UP(dqx, qx, sizeof(float) * nq); UP(dqy, qy, sizeof(float) * nq); UP(dqr, qr, sizeof(float) * nq);
-    UP(dmin, minl, sizeof(int) * nq); UP(dmax, maxl, sizeof(int) * nq);
-    if (qur) UP(dqu, qur, sizeof(float) * nq);
-    if (qer) UP(dqe, qer, sizeof(float) * nq);
-    UP(dqd, qdesc, (size_t)32 * nq);
+    UP(dqx, q.x, sizeof(float) * nq); UP(dqy, q.y, sizeof(float) * nq); UP(dqr, q.r, sizeof(float) * nq);
+    UP(dmin, q.lo, sizeof(int) * nq); UP(dmax, q.hi, sizeof(int) * nq);
+    if (q.ur) UP(dqu, q.ur, sizeof(float) * nq);
+    if (q.er) UP(dqe, q.er, sizeof(float) * nq);
+    UP(dqd, q.desc, (size_t)32 * nq);
     AL(dcnt, sizeof(int) * nq); AL(dovf, sizeof(int));
     AL_BIG(didx, sizeof(int) * (size_t)nq * cap); AL_BIG(ddist, sizeof(int) * (size_t)nq * cap);   // [nq][cap]: only the used columns come back
     AL_BIG(dpack, 2 * sizeof(int) * (size_t)nq * cap);       // packed copy of the used columns (reserved now: the arena must not grow after the launch)
@@ -351,7 +375,7 @@ int window_pass(orbm* m, const orbm_frame_t* f, int nq, const float* qx, const f
                        df ? (f->uright ? df->dUr : nullptr) : (f->uright ? du.as<float>() : nullptr), df ? df->dGs : dgs.as<int>(), df ? df->dGi : dgi.as<int>(),
                        f->min_x, f->min_y, f->inv_w, f->inv_h,
                        nq, dqx.as<float>(), dqy.as<float>(), dqr.as<float>(), dmin.as<int>(), dmax.as<int>(),
-                       qur ? dqu.as<float>() : nullptr, qer ? dqe.as<float>() : nullptr, dqd.as<uint8_t>(), cap,
+                       q.ur ? dqu.as<float>() : nullptr, q.er ? dqe.as<float>() : nullptr, dqd.as<uint8_t>(), cap,
                        dcnt.as<int>(), didx.as<int>(), ddist.as<int>(), dovf.as<int>());
     MHIPCHK(rec_time(m, m->e1));
     m->timed = true;
@@ -380,7 +404,7 @@ int window_pass(orbm* m, const orbm_frame_t* f, int nq, const float* qx, const f
         // frames, the 100-px initialisation window) is simply run again with room for every keypoint of the frame
         if (devCap < f->n) {
             cap = f->n;
-            return window_pass(m, f, nq, qx, qy, qr, minl, maxl, qur, qer, qdesc, cap, cnt, idx, dist, true, df);
+            return window_pass(m, f, q, cap, cnt, idx, dist, true, df);
         }
         set_merr("a search window returned more than %d candidates", devCap);
         return ORBM_E_CAPACITY;
@@ -399,20 +423,19 @@ int window_pass(orbm* m, const orbm_frame_t* f, int nq, const float* qx, const f
 
 // k_window_topk against a resident frame: per window the candidate count and the WT_K smallest (distance, position) keys.
 // One upload of the queries, one kernel, one download.
-int window_topk_pass(orbm* m, const orbm_dframe* df, bool stereo_gate, int nq, const float* qx, const float* qy, const float* qr,
-                     const int32_t* minl, const int32_t* maxl, const float* qur, const float* qer, const uint8_t* qdesc,
-                     const int** cnt, const unsigned int** keys) {
+int window_topk_pass(orbm* m, const orbm_dframe* df, bool stereo_gate, const WindowQuery& q, const int** cnt, const unsigned int** keys) {
     // results stay in the arena's pinned mirror (valid until the handle's next call): *cnt [nq], *keys [nq][WT_K]
     *cnt = nullptr; *keys = nullptr;
+    const int nq = q.nq;
     if (nq == 0 || df->n == 0) return ORBM_OK;
     MHIPCHK(hipSetDevice(m->device));
     DevBuf dqx, dqy, dqr, dmin, dmax, dqu, dqe, dqd, dcnt, dkeys;
     arena_reset(m);
-    UP(dqx, qx, sizeof(float) * nq); UP(dqy, qy, sizeof(float) * nq); UP(dqr, qr, sizeof(float) * nq);
-    UP(dmin, minl, sizeof(int) * nq); UP(dmax, maxl, sizeof(int) * nq);
-    if (qur) UP(dqu, qur, sizeof(float) * nq);
-    if (qer) UP(dqe, qer, sizeof(float) * nq);
-    UP(dqd, qdesc, (size_t)32 * nq);
+    UP(dqx, q.x, sizeof(float) * nq); UP(dqy, q.y, sizeof(float) * nq); UP(dqr, q.r, sizeof(float) * nq);
+    UP(dmin, q.lo, sizeof(int) * nq); UP(dmax, q.hi, sizeof(int) * nq);
+    if (q.ur) UP(dqu, q.ur, sizeof(float) * nq);
+    if (q.er) UP(dqe, q.er, sizeof(float) * nq);
+    UP(dqd, q.desc, (size_t)32 * nq);
     AL(dcnt, sizeof(int) * nq); AL(dkeys, sizeof(unsigned int) * (size_t)nq * WT_K);
     static const bool prof = getenv("ORBM_PROFILE") != nullptr;
     static const bool copies = ab_env("ORBM_TOPK_COPIES") != nullptr;     // A/B: staged copies instead of zero-copy
@@ -427,7 +450,7 @@ int window_topk_pass(orbm* m, const orbm_dframe* df, bool stereo_gate, int nq, c
 #define QP(buf, T_) (copies ? (buf).as<T_>() : (T_*)hp(buf))
     hipLaunchKernelGGL(k_window_topk, dim3((nq + 3) / 4), dim3(256), 0, m->stream, df->dKps, df->dDesc, stereo_gate ? df->dUr : nullptr, df->dGs, df->dGi,
                        df->min_x, df->min_y, df->inv_w, df->inv_h, nq, QP(dqx, float), QP(dqy, float), QP(dqr, float), QP(dmin, int), QP(dmax, int),
-                       qur ? QP(dqu, float) : nullptr, qer ? QP(dqe, float) : nullptr, QP(dqd, uint8_t), QP(dcnt, int), QP(dkeys, unsigned int));
+                       q.ur ? QP(dqu, float) : nullptr, q.er ? QP(dqe, float) : nullptr, QP(dqd, uint8_t), QP(dcnt, int), QP(dkeys, unsigned int));
 #undef QP
     if (prof) { MHIPCHK(rec_time(m, m->e1)); m->timed = true; }
     MHIPCHK(hipGetLastError());
@@ -476,6 +499,126 @@ int bucket_pass(orbm* m, const uint8_t* d1, int n1, const uint8_t* d2, int n2, c
     return ORBM_OK;
 }
 
+void join_nodes(int nn1, const int32_t* nodes1, const int32_t* start1, const int32_t* idx1, int nn2, const int32_t* nodes2,
+                const int32_t* start2, JoinJobs& J) {
+    int a = 0, b = 0;                                                       // lower_bound jumps == this linear merge on sorted keys
+    while (a < nn1 && b < nn2) {
+        if (nodes1[a] == nodes2[b]) {
+            const int len = start2[b + 1] - start2[b];
+            for (int i = start1[a]; i < start1[a + 1]; ++i) {
+                J.q.push_back(idx1[i]); J.l2.push_back(start2[b]); J.len.push_back(len); J.off.push_back(J.total); J.node_b.push_back(b);
+                J.total += len;
+            }
+            ++a; ++b;
+        } else if (nodes1[a] < nodes2[b]) ++a; else ++b;
+    }
+}
+
+// The jobs of a BoW search as its replay walks them, in the reference's (node, side-1 feature) order: job j is side-1 feature
+// query(j) against the count(j) side-2 features of the common node, index(j, c) at distance(j, c).
+struct BucketJobs {
+    JoinJobs J; std::vector<int> dist; const int32_t* idx2 = nullptr;
+    size_t size() const { return J.q.size(); }
+    int query(size_t j) const { return J.q[j]; }
+    int count(size_t j) const { return J.len[j]; }
+    int index(size_t j, int c) const { return idx2[J.l2[j] + c]; }
+    int distance(size_t j, int c) const { return dist[J.off[j] + c]; }
+};
+
+// prologue of M7 / M7-fisheye / M8 / M10: join the two FeatureVectors, one distance pass over every job, `out` reset to -1
+int bucket_jobs(orbm* m, const uint8_t* desc1, int n1, int nn1, const int32_t* nodes1, const int32_t* start1, const int32_t* idx1,
+                const uint8_t* desc2, int n2, int nn2, const int32_t* nodes2, const int32_t* start2, const int32_t* idx2,
+                int32_t* out, int nout, BucketJobs& B) {
+    join_nodes(nn1, nodes1, start1, idx1, nn2, nodes2, start2, B.J);
+    B.idx2 = idx2;
+    const int rc = bucket_pass(m, desc1, n1, desc2, n2, idx2, start2[nn2], B.J, B.dist);
+    if (rc) return rc;
+    for (int i = 0; i < nout; ++i) out[i] = -1;
+    return ORBM_OK;
+}
+
+// Candidate lists as the claim replays see them: either the full [queries][stride] lists of window_pass (window_lists, which
+// owns them), or the K best (distance, position) keys of window_topk_pass, which are a prefix of the list in exactly the order
+// that matters to a `dist < bestDist` scan (see k_window_topk).  trunc(i): the list of query i was cut.
+struct CandLists {
+    std::vector<int> ownCnt, ownIdx, ownDist;                           // storage of the full lists
+    const int* cnt = nullptr; const int* idx = nullptr; const int* dist = nullptr; int stride = 0;
+    const unsigned int* keys = nullptr;                                 // dist << 20 | keypoint index, in (distance, visiting order) rank
+    CandLists() = default;
+    CandLists(const CandLists&) = delete;                               // cnt / idx / dist point into the own vectors
+    int count(int i) const { return keys ? std::min(cnt[i], (int)WT_K) : std::min(cnt[i], stride); }   // (never beyond a row: window_pass has checked)
+    bool trunc(int i) const { return keys && cnt[i] > WT_K; }
+    int index(int i, int c) const { return keys ? (int)(keys[(size_t)i * WT_K + c] & 0xFFFFFu) : idx[(size_t)i * stride + c]; }
+    int distance(int i, int c) const { return keys ? (int)(keys[(size_t)i * WT_K + c] >> 20) : dist[(size_t)i * stride + c]; }
+};
+
+// Full candidate lists of q's windows in `frame` (df: its resident twin, or NULL).  A search without a stereo gate sweeps a copy
+// of the frame without uright.  first_cap: the window capacity of the first attempt (window_pass runs again with room for the
+// whole frame when one overflows); the row stride of the lists is whatever the pass packed them to.
+int window_lists(orbm* m, const orbm_frame_t* frame, bool stereo_gate, const WindowQuery& q, int first_cap, CandLists& out, const orbm_dframe* df = nullptr) {
+    orbm_frame_t f = *frame;
+    if (!stereo_gate) f.uright = nullptr;
+    int cap = std::max(1, std::min(f.n, first_cap));
+    const int rc = window_pass(m, &f, q, cap, out.ownCnt, out.ownIdx, out.ownDist, false, df);
+    if (rc) return rc;
+    out.cnt = out.ownCnt.data(); out.idx = out.ownIdx.data(); out.dist = out.ownDist.data(); out.stride = cap; out.keys = nullptr;
+    return ORBM_OK;
+}
+
+// first minimum over the candidates of query i that `blocked` does not exclude: (bestDist, bestIdx), (256, -1) without one
+std::pair<int, int> best_unblocked(const CandLists& L, int i, const uint8_t* blocked) {
+    int bestDist = 256, bestIdx = -1;
+    for (int c = 0, nc = L.count(i); c < nc; ++c) {
+        const int k = L.index(i, c);
+        if (blocked[k]) continue;
+        const int d = L.distance(i, c);
+        if (d < bestDist) { bestDist = d; bestIdx = k; }
+    }
+    return {bestDist, bestIdx};
+}
+
+// best and second-best distance over the unblocked candidates of query i, with their pyramid levels (ORBmatcher.cc:119-141);
+// seen: how many candidates were unblocked
+struct BestTwo { int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1, seen = 0; };
+BestTwo best_two_levels(const CandLists& L, int i, const uint8_t* blocked, const orbm_kp_t* kps) {
+    BestTwo b;
+    for (int c = 0, nc = L.count(i); c < nc; ++c) {
+        const int k = L.index(i, c);
+        if (blocked[k]) continue;
+        ++b.seen;
+        const int d = L.distance(i, c);
+        if (d < b.bestDist) { b.bestDist2 = b.bestDist; b.bestDist = d; b.bestLevel2 = b.bestLevel; b.bestLevel = kps[k].octave; b.bestIdx = k; }
+        else if (d < b.bestDist2) { b.bestLevel2 = kps[k].octave; b.bestDist2 = d; }
+    }
+    return b;
+}
+
+// Driver of the resident M3 / M4: replay the WT_K best keys of every window; where a cut list ran out of candidates the replay
+// returns false and runs again over the full lists.  Without a resident frame the full lists at once.  replay(lists) fills
+// match and nmatches; an empty pass (no query, no keypoint) leaves match at -1 and returns 0.
+template <class Replay>
+int search_lists(orbm* m, const orbm_frame_t* f, const orbm_dframe* df, const WindowQuery& q, bool profile, int32_t* match, const int& nmatches, Replay replay) {
+    if (df) {
+        static const bool env = getenv("ORBM_PROFILE") != nullptr;
+        const bool prof = env && profile;
+        auto T = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+        const double t0 = prof ? T() : 0;
+        CandLists Lk;
+        const int rc = window_topk_pass(m, df, f->uright != nullptr, q, &Lk.cnt, &Lk.keys);
+        if (rc) return rc;
+        const double t1 = prof ? T() : 0;
+        if (!Lk.cnt) for (int i = 0; i < f->n; ++i) match[i] = -1;
+        const bool done = !Lk.cnt || replay(Lk);
+        if (prof) fprintf(stderr, "orbm profile: top-K pass %.1f us, replay %.1f us%s\n", t1 - t0, T() - t1, done ? "" : " (fallback)");
+        if (done) return Lk.cnt ? nmatches : 0;
+    }
+    CandLists Lf;
+    const int rc = window_lists(m, f, true, q, 2048, Lf, df);
+    if (rc) return rc;
+    replay(Lf);
+    return nmatches;
+}
+
 }  // namespace
 
 extern "C" {
@@ -519,7 +662,7 @@ int orbm_window_candidates(orbm_t* m, const orbm_frame_t* f, int nq, const float
     if (!m || !f || nq < 0 || cap < 1) return ORBM_E_INVALID;
     std::vector<int> cnt, idx, dist;
     int stride = cap;                                        // in: window capacity; out: row stride of the packed lists
-    int rc = window_pass(m, f, nq, qx, qy, qr, min_level, max_level, q_ur, q_er_max, qdesc, stride, cnt, idx, dist);
+    int rc = window_pass(m, f, WindowQuery{nq, qx, qy, qr, min_level, max_level, q_ur, q_er_max, qdesc}, stride, cnt, idx, dist);
     if (rc && rc != ORBM_E_CAPACITY) return rc;
     for (int i = 0; i < nq; ++i) {
         out_cnt[i] = cnt[i];
@@ -532,34 +675,21 @@ int orbm_window_candidates(orbm_t* m, const orbm_frame_t* f, int nq, const float
     return rc;
 }
 
-// Candidate lists as the claim replays see them: either the full [queries][stride] lists of window_pass, or the K best
-// (distance, position) keys of window_topk_pass, which are a prefix of the list in exactly the order that matters to a
-// `dist < bestDist` scan (see k_window_topk).  trunc(i): the list of query i was cut.
-struct CandLists {
-    const int* cnt = nullptr; const int* idx = nullptr; const int* dist = nullptr; int stride = 0;
-    const unsigned int* keys = nullptr;                                 // dist << 20 | keypoint index, in (distance, visiting order) rank
-    int count(int i) const { return keys ? std::min(cnt[i], (int)WT_K) : std::min(cnt[i], stride); }   // (never beyond a row: window_pass has checked)
-    bool trunc(int i) const { return keys && cnt[i] > WT_K; }
-    int index(int i, int c) const { return keys ? (int)(keys[(size_t)i * WT_K + c] & 0xFFFFFu) : idx[(size_t)i * stride + c]; }
-    int distance(int i, int c) const { return keys ? (int)(keys[(size_t)i * WT_K + c] >> 20) : dist[(size_t)i * stride + c]; }
-};
-
 // M4 body.  cur: the frame's view (host arrays, or the resident frame's host-side copy of what the replay reads); df: resident frame or NULL
 static int search_by_projection_frame_impl(orbm_t* m, const orbm_frame_t* cur, const orbm_dframe* df, const uint8_t* cur_blocked, const float* sf,
                                            int nq, const uint8_t* valid, const float* u, const float* v, const float* invzc,
                                            const int32_t* octave, const float* angle, const uint8_t* qdesc, const uint8_t* mp_obs,
                                            float th, int bForward, int bBackward, float mbf, int check_ori, int32_t* match) {
     // windows exactly as ORBmatcher.cc:2543-2549; invalid queries get an empty window (r < 0)
-    std::vector<float> qr(nq), qur(nq), qer(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
+    std::vector<float> qur(nq), qer(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; qur[i] = 0; qer[i] = -1.f; continue; }
+        if (!valid[i]) { W.skip(i); qur[i] = 0; qer[i] = -1.f; continue; }
         const int o = octave[i];
         const float radius = th * sf[o];
-        qr[i] = radius;
-        if (bForward) { minl[i] = o; maxl[i] = -1; }
-        else if (bBackward) { minl[i] = 0; maxl[i] = o; }
-        else { minl[i] = o - 1; maxl[i] = o + 1; }
+        if (bForward) W.set(i, radius, o, -1);
+        else if (bBackward) W.set(i, radius, 0, o);
+        else W.set(i, radius, o - 1, o + 1);
         qur[i] = u[i] - mbf * invzc[i];                                    // :2571
         qer[i] = cur->uright ? radius : -1.f;
     }
@@ -574,13 +704,7 @@ static int search_by_projection_frame_impl(orbm_t* m, const orbm_frame_t* cur, c
         for (int i = 0; i < nq; ++i) {
             const int nc = valid[i] ? Lc.count(i) : 0;
             if (nc == 0) continue;
-            int bestDist = 256, bestIdx2 = -1;
-            for (int c = 0; c < nc; ++c) {
-                const int i2 = Lc.index(i, c);
-                if (blocked[i2]) continue;
-                const int d = Lc.distance(i, c);
-                if (d < bestDist) { bestDist = d; bestIdx2 = i2; }
-            }
+            const auto [bestDist, bestIdx2] = best_unblocked(Lc, i, blocked.data());
             if (bestIdx2 < 0 && Lc.trunc(i)) return false;
             if (bestDist <= ORBM_TH_HIGH) {
                 match[bestIdx2] = i;
@@ -589,36 +713,10 @@ static int search_by_projection_frame_impl(orbm_t* m, const orbm_frame_t* cur, c
                 if (check_ori) rh.add(angle[i], cur->kps[bestIdx2].angle, factor, bestIdx2);
             }
         }
-        if (check_ori) {
-            int ind[3];
-            rh.maxima(ind);
-            for (int b = 0; b < ORBM_HISTO_LENGTH; ++b)
-                if (b != ind[0] && b != ind[1] && b != ind[2])
-                    for (int k : rh.bins[b]) { match[k] = ORBM_MATCH_PRUNED; nmatches--; }
-        }
+        if (check_ori) rh.cull([&](int k) { match[k] = ORBM_MATCH_PRUNED; nmatches--; });
         return true;
     };
-    std::vector<int> cnt, idx, dist;
-    if (df) {
-        const int* kc = nullptr; const unsigned int* kk = nullptr;
-        static const bool prof = getenv("ORBM_PROFILE") != nullptr;
-        auto T = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double t0 = prof ? T() : 0;
-        int rc = window_topk_pass(m, df, cur->uright != nullptr, nq, u, v, qr.data(), minl.data(), maxl.data(), qur.data(), qer.data(), qdesc, &kc, &kk);
-        if (rc) return rc;
-        const double t1 = prof ? T() : 0;
-        CandLists Lk; Lk.cnt = kc; Lk.keys = kk;
-        const bool done = !kc || replay(Lk);
-        if (!kc) { for (int i = 0; i < cur->n; ++i) match[i] = -1; nmatches = 0; }
-        if (prof) fprintf(stderr, "orbm profile: top-K pass %.1f us, replay %.1f us%s\n", t1 - t0, T() - t1, done ? "" : " (fallback)");
-        if (done) return nmatches;
-    }
-    int cap = std::max(1, std::min(cur->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    int rc = window_pass(m, cur, nq, u, v, qr.data(), minl.data(), maxl.data(), qur.data(), qer.data(), qdesc, cap, cnt, idx, dist, false, df);
-    if (rc) return rc;
-    CandLists Lf; Lf.cnt = cnt.data(); Lf.idx = idx.data(); Lf.dist = dist.data(); Lf.stride = cap;
-    replay(Lf);
-    return nmatches;
+    return search_lists(m, cur, df, W.query(u, v, qur.data(), qer.data(), qdesc), true, match, nmatches, replay);
 }
 
 int orbm_search_by_projection_frame(orbm_t* m, const orbm_frame_t* cur, const uint8_t* cur_blocked, const float* sf,
@@ -635,16 +733,16 @@ static int search_by_projection_points_impl(orbm_t* m, const orbm_frame_t* f, co
                                             const float* view_cos, const int32_t* level, const uint8_t* qdesc, const uint8_t* mp_obs,
                                             float th, float nnratio, int32_t* match) {
     const bool bFactor = th != 1.0;
-    std::vector<float> qr(nq), qer(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
+    std::vector<float> qer(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!in_view[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; qer[i] = -1.f; continue; }
+        if (!in_view[i]) { W.skip(i); qer[i] = -1.f; continue; }
         float r = view_cos[i] > 0.998 ? 2.5f : 4.0f;                       // RadiusByViewingCos (:242-249)
         if (bFactor) r *= th;
-        qr[i] = r * sf[level[i]];
-        minl[i] = level[i] - 1; maxl[i] = level[i];
+        W.set(i, r * sf[level[i]], level[i] - 1, level[i]);
         qer[i] = f->uright ? r * sf[level[i]] : -1.f;                      // :107-117
     }
+    // replay of ORBmatcher.cc:119-166; false = a cut list held fewer than two unblocked candidates
     int nmatches = 0;
     auto replay = [&](const CandLists& Lc) -> bool {
         nmatches = 0;
@@ -653,42 +751,20 @@ static int search_by_projection_points_impl(orbm_t* m, const orbm_frame_t* f, co
         for (int iMP = 0; iMP < nq; ++iMP) {
             const int nc = in_view[iMP] ? Lc.count(iMP) : 0;
             if (nc == 0) continue;
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1, seen = 0;
-            for (int c = 0; c < nc; ++c) {
-                const int k = Lc.index(iMP, c);
-                if (blocked[k]) continue;
-                ++seen;
-                const int d = Lc.distance(iMP, c);
-                if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = f->kps[k].octave; bestIdx = k; }
-                else if (d < bestDist2) { bestLevel2 = f->kps[k].octave; bestDist2 = d; }
-            }
-            if (seen < 2 && Lc.trunc(iMP)) return false;                    // best AND second must come from the unblocked candidates
-            if (bestDist <= ORBM_TH_HIGH) {
-                if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-                if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                    match[bestIdx] = iMP;
-                    if (mp_obs[iMP]) blocked[bestIdx] = 1;
+            const BestTwo b = best_two_levels(Lc, iMP, blocked.data(), f->kps);
+            if (b.seen < 2 && Lc.trunc(iMP)) return false;                  // best AND second must come from the unblocked candidates
+            if (b.bestDist <= ORBM_TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;
+                if (b.bestLevel != b.bestLevel2 || b.bestDist <= nnratio * b.bestDist2) {
+                    match[b.bestIdx] = iMP;
+                    if (mp_obs[iMP]) blocked[b.bestIdx] = 1;
                     nmatches++;
                 }
             }
         }
         return true;
     };
-    std::vector<int> cnt, idx, dist;
-    if (df) {
-        const int* kc = nullptr; const unsigned int* kk = nullptr;
-        int rc = window_topk_pass(m, df, f->uright != nullptr, nq, px, py, qr.data(), minl.data(), maxl.data(), pxr, qer.data(), qdesc, &kc, &kk);
-        if (rc) return rc;
-        if (!kc) { for (int i = 0; i < f->n; ++i) match[i] = -1; return 0; }
-        CandLists Lk; Lk.cnt = kc; Lk.keys = kk;
-        if (replay(Lk)) return nmatches;
-    }
-    int cap = std::max(1, std::min(f->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    int rc = window_pass(m, f, nq, px, py, qr.data(), minl.data(), maxl.data(), pxr, qer.data(), qdesc, cap, cnt, idx, dist, false, df);
-    if (rc) return rc;
-    CandLists Lf; Lf.cnt = cnt.data(); Lf.idx = idx.data(); Lf.dist = dist.data(); Lf.stride = cap;
-    replay(Lf);
-    return nmatches;
+    return search_lists(m, f, df, W.query(px, py, pxr, qer.data(), qdesc), false, match, nmatches, replay);
 }
 
 int orbm_search_by_projection_points(orbm_t* m, const orbm_frame_t* f, const uint8_t* blocked_in, const float* sf,
@@ -789,17 +865,16 @@ int orbm_search_for_initialization(orbm_t* m, const orbm_frame_t* F1, const orbm
                                    float nnratio, int check_ori, int32_t* vnMatches12) {
     if (!m || !F1 || !F2) return ORBM_E_INVALID;
     const int n1 = F1->n;
-    std::vector<float> qx(n1), qy(n1), qr(n1);
-    std::vector<int> minl(n1), maxl(n1);
+    std::vector<float> qx(n1), qy(n1);
+    WindowTables W(n1);
     for (int i = 0; i < n1; ++i) {
         const int l1 = F1->kps[i].octave;
         qx[i] = prev[2 * i]; qy[i] = prev[2 * i + 1];
-        if (l1 > 0) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; }           // :825
-        else { qr[i] = (float)windowSize; minl[i] = l1; maxl[i] = l1; }
+        if (l1 > 0) W.skip(i);                                             // :825
+        else W.set(i, (float)windowSize, l1, l1);
     }
-    int cap = std::max(1, std::min(F2->n, 4096));      // becomes the row stride of idx / dist after window_pass
-    std::vector<int> cnt, idx, dist;
-    int rc = window_pass(m, F2, n1, qx.data(), qy.data(), qr.data(), minl.data(), maxl.data(), nullptr, nullptr, F1->desc, cap, cnt, idx, dist);
+    CandLists L;
+    int rc = window_lists(m, F2, false, W.query(qx.data(), qy.data(), nullptr, nullptr, F1->desc), 4096, L);   // (the 100-px window is dense)
     if (rc) return rc;
     int nmatches = 0;
     for (int i = 0; i < n1; ++i) vnMatches12[i] = -1;
@@ -807,10 +882,10 @@ int orbm_search_for_initialization(orbm_t* m, const orbm_frame_t* F1, const orbm
     const float factor = ORBM_HISTO_LENGTH / 360.0f;
     std::vector<int> vMatchedDistance(F2->n, INT_MAX), vnMatches21(F2->n, -1);
     for (int i1 = 0; i1 < n1; ++i1) {
-        if (F1->kps[i1].octave > 0 || cnt[i1] == 0) continue;
+        if (F1->kps[i1].octave > 0 || L.count(i1) == 0) continue;
         int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
-        for (int c = 0; c < cnt[i1]; ++c) {
-            const int i2 = idx[(size_t)i1 * cap + c], d = dist[(size_t)i1 * cap + c];
+        for (int c = 0, nc = L.count(i1); c < nc; ++c) {
+            const int i2 = L.index(i1, c), d = L.distance(i1, c);
             if (vMatchedDistance[i2] <= d) continue;
             if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestIdx2 = i2; }
             else if (d < bestDist2) bestDist2 = d;
@@ -822,32 +897,10 @@ int orbm_search_for_initialization(orbm_t* m, const orbm_frame_t* F1, const orbm
             if (check_ori) rh.add(F1->kps[i1].angle, F2->kps[bestIdx2].angle, factor, i1);
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            if (b == ind[0] || b == ind[1] || b == ind[2]) continue;
-            for (int i1 : rh.bins[b]) if (vnMatches12[i1] >= 0) { vnMatches12[i1] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) rh.cull([&](int i1) { if (vnMatches12[i1] >= 0) { vnMatches12[i1] = -1; nmatches--; } });   // only entries still matched (:926)
     for (int i1 = 0; i1 < n1; ++i1)
         if (vnMatches12[i1] >= 0) { prev[2 * i1] = F2->kps[vnMatches12[i1]].x; prev[2 * i1 + 1] = F2->kps[vnMatches12[i1]].y; }
     return nmatches;
-}
-
-static void join_nodes(int nn1, const int32_t* nodes1, const int32_t* start1, const int32_t* idx1, int nn2, const int32_t* nodes2,
-                       const int32_t* start2, JoinJobs& J) {
-    int a = 0, b = 0;                                                       // lower_bound jumps == this linear merge on sorted keys
-    while (a < nn1 && b < nn2) {
-        if (nodes1[a] == nodes2[b]) {
-            const int len = start2[b + 1] - start2[b];
-            for (int i = start1[a]; i < start1[a + 1]; ++i) {
-                J.q.push_back(idx1[i]); J.l2.push_back(start2[b]); J.len.push_back(len); J.off.push_back(J.total); J.node_b.push_back(b);
-                J.total += len;
-            }
-            ++a; ++b;
-        } else if (nodes1[a] < nodes2[b]) ++a; else ++b;
-    }
 }
 
 static int triangulation_impl(orbm_t* m, bool legacy, int n1, const orbm_kp_t* kps1, const uint8_t* desc1, const uint8_t* has_mp1, const float* uright1,
@@ -859,28 +912,25 @@ static int triangulation_impl(orbm_t* m, bool legacy, int n1, const orbm_kp_t* k
                                   orbm_pair_gate_fn gate = nullptr, void* gate_user = nullptr) {
     if (!m || n1 < 0 || n2 < 0) return ORBM_E_INVALID;
     std::vector<uint8_t> vbMatched2(n2, 0);                                 // only maintained by the legacy overload (:1319)
-    JoinJobs J;
-    join_nodes(nn1, nodes1, start1, idx1, nn2, nodes2, start2, J);
-    std::vector<int> dist;
-    int rc = bucket_pass(m, desc1, n1, desc2, n2, idx2, start2[nn2], J, dist);
+    BucketJobs B;
+    int rc = bucket_jobs(m, desc1, n1, nn1, nodes1, start1, idx1, desc2, n2, nn2, nodes2, start2, idx2, vMatches12, n1, B);
     if (rc) return rc;
-    for (int i = 0; i < n1; ++i) vMatches12[i] = -1;
     int nmatches = 0;
     RotHist rh;
     const float factor = legacy ? ORBM_HISTO_LENGTH / 360.0f : 1.0f / ORBM_HISTO_LENGTH;   // :1166 vs :1441 (sic)
-    for (size_t j = 0; j < J.q.size(); ++j) {
-        const int i1 = J.q[j];
+    for (size_t j = 0; j < B.size(); ++j) {
+        const int i1 = B.query(j);
         if (has_mp1[i1]) continue;
         const bool bStereo1 = uright1 && uright1[i1] >= 0;
         if (bOnlyStereo && !bStereo1) continue;
         const orbm_kp_t& kp1 = kps1[i1];
         int bestDist = ORBM_TH_LOW, bestIdx2 = -1;
-        for (int c = 0; c < J.len[j]; ++c) {
-            const int i2 = idx2[J.l2[j] + c];
+        for (int c = 0; c < B.count(j); ++c) {
+            const int i2 = B.index(j, c);
             if (vbMatched2[i2] || has_mp2[i2]) continue;
             const bool bStereo2 = uright2 && uright2[i2] >= 0;
             if (bOnlyStereo && !bStereo2) continue;
-            const int d = dist[J.off[j] + c];
+            const int d = B.distance(j, c);
             if (d > ORBM_TH_LOW || d > bestDist) continue;
             const orbm_kp_t& kp2 = kps2[i2];
             if (!bStereo1 && !bStereo2 && sf2) {                            // sf2 == NULL: pKF1->mpCamera2 set (:1517) / M12, which has no such gate
@@ -906,14 +956,7 @@ static int triangulation_impl(orbm_t* m, bool legacy, int n1, const orbm_kp_t* k
             if (check_ori) rh.add(kp1.angle, kps2[bestIdx2].angle, factor, i1);
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            if (b == ind[0] || b == ind[1] || b == ind[2]) continue;
-            for (int i : rh.bins[b]) { if (legacy) vbMatched2[vMatches12[i]] = 0; vMatches12[i] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) rh.cull([&](int i) { if (legacy) vbMatched2[vMatches12[i]] = 0; vMatches12[i] = -1; nmatches--; });
     return nmatches;
 }
 
@@ -951,16 +994,13 @@ int orbm_search_by_projection_kf(orbm_t* m, const orbm_frame_t* cur, const uint8
                                  int nq, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
                                  const float* angle, const uint8_t* qdesc, float th, int ORBdist, int check_ori, int32_t* match) {
     if (!m || !cur || nq < 0) return ORBM_E_INVALID;
-    std::vector<float> qr(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; continue; }
-        qr[i] = th * sf[level[i]]; minl[i] = level[i] - 1; maxl[i] = level[i] + 1;      // :2775-2778
+        if (!valid[i]) { W.skip(i); continue; }
+        W.set(i, th * sf[level[i]], level[i] - 1, level[i] + 1);            // :2775-2778
     }
-    int cap = std::max(1, std::min(cur->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    std::vector<int> cnt, idx, dist;
-    orbm_frame_t f = *cur; f.uright = nullptr;                              // this overload has no stereo gate
-    int rc = window_pass(m, &f, nq, u, v, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, cap, cnt, idx, dist);
+    CandLists L;
+    int rc = window_lists(m, cur, false, W.query(u, v, nullptr, nullptr, qdesc), 2048, L);   // this overload has no stereo gate
     if (rc) return rc;
     int nmatches = 0;
     RotHist rh;
@@ -968,27 +1008,15 @@ int orbm_search_by_projection_kf(orbm_t* m, const orbm_frame_t* cur, const uint8
     std::vector<uint8_t> taken(blocked_in, blocked_in + cur->n);
     for (int i = 0; i < cur->n; ++i) match[i] = -1;
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i] || cnt[i] == 0) continue;
-        int bestDist = 256, bestIdx2 = -1;
-        for (int c = 0; c < cnt[i]; ++c) {
-            const int i2 = idx[(size_t)i * cap + c];
-            if (taken[i2]) continue;                                        // :2793
-            const int d = dist[(size_t)i * cap + c];
-            if (d < bestDist) { bestDist = d; bestIdx2 = i2; }
-        }
+        if (!valid[i] || L.count(i) == 0) continue;
+        const auto [bestDist, bestIdx2] = best_unblocked(L, i, taken.data());   // :2793
         if (bestDist <= ORBdist) {
             match[bestIdx2] = i; taken[bestIdx2] = 1;
             nmatches++;
             if (check_ori) rh.add(angle[i], cur->kps[bestIdx2].angle, factor, bestIdx2);
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b)
-            if (b != ind[0] && b != ind[1] && b != ind[2])
-                for (int k : rh.bins[b]) { match[k] = ORBM_MATCH_PRUNED; nmatches--; }
-    }
+    if (check_ori) rh.cull([&](int k) { match[k] = ORBM_MATCH_PRUNED; nmatches--; });
     return nmatches;
 }
 
@@ -996,29 +1024,20 @@ int orbm_search_by_projection_sim3(orbm_t* m, const orbm_frame_t* kf, const uint
                                    int nq, const uint8_t* valid, const float* u, const float* v, const int32_t* level,
                                    const uint8_t* qdesc, int th, float ratioHamming, int32_t* match) {
     if (!m || !kf || nq < 0) return ORBM_E_INVALID;
-    std::vector<float> qr(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; continue; }
-        qr[i] = th * sf[level[i]]; minl[i] = level[i] - 1; maxl[i] = level[i];          // :600-601, :625-627
+        if (!valid[i]) { W.skip(i); continue; }
+        W.set(i, th * sf[level[i]], level[i] - 1, level[i]);                // :600-601, :625-627
     }
-    int cap = std::max(1, std::min(kf->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    std::vector<int> cnt, idx, dist;
-    orbm_frame_t f = *kf; f.uright = nullptr;
-    int rc = window_pass(m, &f, nq, u, v, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, cap, cnt, idx, dist);
+    CandLists L;
+    int rc = window_lists(m, kf, false, W.query(u, v, nullptr, nullptr, qdesc), 2048, L);
     if (rc) return rc;
     int nmatches = 0;
     std::vector<uint8_t> matched(matched_in, matched_in + kf->n);
     for (int i = 0; i < kf->n; ++i) match[i] = -1;
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i] || cnt[i] == 0) continue;
-        int bestDist = 256, bestIdx = -1;
-        for (int c = 0; c < cnt[i]; ++c) {
-            const int k = idx[(size_t)i * cap + c];
-            if (matched[k]) continue;                                        // :621-622
-            const int d = dist[(size_t)i * cap + c];
-            if (d < bestDist) { bestDist = d; bestIdx = k; }
-        }
+        if (!valid[i] || L.count(i) == 0) continue;
+        const auto [bestDist, bestIdx] = best_unblocked(L, i, matched.data());   // :621-622
         if (bestDist <= ORBM_TH_LOW * ratioHamming) { match[bestIdx] = i; matched[bestIdx] = 1; nmatches++; }
     }
     return nmatches;
@@ -1028,24 +1047,21 @@ int orbm_fuse(orbm_t* m, const orbm_frame_t* kf, const float* sf, const float* i
               int nq, const uint8_t* valid, const float* u, const float* v, const float* ur, const int32_t* level,
               const uint8_t* qdesc, float th, int chi2_gate, int32_t* best_idx) {
     if (!m || !kf || nq < 0) return ORBM_E_INVALID;
-    std::vector<float> qr(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; continue; }
-        qr[i] = th * sf[level[i]]; minl[i] = level[i] - 1; maxl[i] = level[i];
+        if (!valid[i]) { W.skip(i); continue; }
+        W.set(i, th * sf[level[i]], level[i] - 1, level[i]);
     }
-    int cap = std::max(1, std::min(kf->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    std::vector<int> cnt, idx, dist;
-    orbm_frame_t f = *kf; f.uright = nullptr;                               // the chi2 gate below is not a window gate
-    int rc = window_pass(m, &f, nq, u, v, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, cap, cnt, idx, dist);
+    CandLists L;
+    int rc = window_lists(m, kf, false, W.query(u, v, nullptr, nullptr, qdesc), 2048, L);   // the chi2 gate below is not a window gate
     if (rc) return rc;
     int nFused = 0;
     for (int i = 0; i < nq; ++i) {
         best_idx[i] = -1;
-        if (!valid[i] || cnt[i] == 0) continue;
+        if (!valid[i] || L.count(i) == 0) continue;
         int bestDist = chi2_gate ? 256 : INT_MAX, bestIdx = -1;
-        for (int c = 0; c < cnt[i]; ++c) {
-            const int k = idx[(size_t)i * cap + c];
+        for (int c = 0, nc = L.count(i); c < nc; ++c) {
+            const int k = L.index(i, c);
             if (chi2_gate) {                                                 // :1925-1949
                 const orbm_kp_t& kp = kf->kps[k];
                 if (kf->uright && kf->uright[k] >= 0) {
@@ -1058,7 +1074,7 @@ int orbm_fuse(orbm_t* m, const orbm_frame_t* kf, const float* sf, const float* i
                     if (e2 * inv_sigma2[kp.octave] > 5.99) continue;
                 }
             }
-            const int d = dist[(size_t)i * cap + c];
+            const int d = L.distance(i, c);
             if (d < bestDist) { bestDist = d; bestIdx = k; }
         }
         if (bestDist <= ORBM_TH_LOW) { best_idx[i] = bestIdx; nFused++; }
@@ -1070,23 +1086,20 @@ static int sim3_one_way(orbm* m, const orbm_frame_t* src, const orbm_frame_t* ds
                         const float* u, const float* v, const int32_t* level, const uint8_t* qdesc, float th, std::vector<int>& vnMatch) {
     const int nq = src->n;
     vnMatch.assign(nq, -1);
-    std::vector<float> qr(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; continue; }
-        qr[i] = th * sf_dst[level[i]]; minl[i] = level[i] - 1; maxl[i] = level[i];
+        if (!valid[i]) { W.skip(i); continue; }
+        W.set(i, th * sf_dst[level[i]], level[i] - 1, level[i]);
     }
-    int cap = std::max(1, std::min(dst->n, 2048));      // becomes the row stride of idx / dist after window_pass
-    std::vector<int> cnt, idx, dist;
-    orbm_frame_t f = *dst; f.uright = nullptr;
-    int rc = window_pass(m, &f, nq, u, v, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, cap, cnt, idx, dist);
+    CandLists L;
+    int rc = window_lists(m, dst, false, W.query(u, v, nullptr, nullptr, qdesc), 2048, L);
     if (rc) return rc;
     for (int i = 0; i < nq; ++i) {
         if (!valid[i]) continue;
         int bestDist = INT_MAX, bestIdx = -1;
-        for (int c = 0; c < cnt[i]; ++c) {
-            const int d = dist[(size_t)i * cap + c];
-            if (d < bestDist) { bestDist = d; bestIdx = idx[(size_t)i * cap + c]; }
+        for (int c = 0, nc = L.count(i); c < nc; ++c) {
+            const int d = L.distance(i, c);
+            if (d < bestDist) { bestDist = d; bestIdx = L.index(i, c); }
         }
         if (bestDist <= ORBM_TH_HIGH) vnMatch[i] = bestIdx;
     }
@@ -1756,64 +1769,40 @@ int orbm_search_by_projection_frame_fisheye(orbm_t* m, const orbm_frame_t* cur_l
                                             const int32_t* octave, const float* angle, const uint8_t* qdesc, const uint8_t* mp_obs,
                                             float th, int bForward, int bBackward, int check_ori, int32_t* match_l, int32_t* match_r) {
     if (!m || !cur_l || !cur_r || nq < 0) return ORBM_E_INVALID;
-    std::vector<float> qr(nq);
-    std::vector<int> minl(nq), maxl(nq);
+    WindowTables W(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i]) { qr[i] = -1.f; minl[i] = 0; maxl[i] = -1; continue; }
+        if (!valid[i]) { W.skip(i); continue; }
         const int o = octave[i];
-        qr[i] = th * sf[o];
-        if (bForward) { minl[i] = o; maxl[i] = -1; } else if (bBackward) { minl[i] = 0; maxl[i] = o; } else { minl[i] = o - 1; maxl[i] = o + 1; }
+        if (bForward) W.set(i, th * sf[o], o, -1); else if (bBackward) W.set(i, th * sf[o], 0, o); else W.set(i, th * sf[o], o - 1, o + 1);
     }
-    orbm_frame_t fl = *cur_l, fr = *cur_r; fl.uright = nullptr; fr.uright = nullptr;     // no stereo gate when Nleft != -1 (:2569)
-    int capL = std::max(1, std::min(fl.n, 2048)), capR = std::max(1, std::min(fr.n, 2048));      // row strides after window_pass
-    std::vector<int> cntL, idxL, distL, cntR, idxR, distR;
-    int rc = window_pass(m, &fl, nq, u, v, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, capL, cntL, idxL, distL);
+    CandLists Ll, Lr;                                                       // no stereo gate when Nleft != -1 (:2569)
+    int rc = window_lists(m, cur_l, false, W.query(u, v, nullptr, nullptr, qdesc), 2048, Ll);
     if (rc) return rc;
-    rc = window_pass(m, &fr, nq, ur, vr, qr.data(), minl.data(), maxl.data(), nullptr, nullptr, qdesc, capR, cntR, idxR, distR);
+    rc = window_lists(m, cur_r, false, W.query(ur, vr, nullptr, nullptr, qdesc), 2048, Lr);
     if (rc) return rc;
     int nmatches = 0;
-    const int Nleft = fl.n;
+    const int Nleft = cur_l->n;
     RotHist rh;
     const float factor = ORBM_HISTO_LENGTH / 360.0f;
-    std::vector<uint8_t> bl(blocked_l_in, blocked_l_in + fl.n), br(blocked_r_in, blocked_r_in + fr.n);
-    for (int i = 0; i < fl.n; ++i) match_l[i] = -1;
-    for (int i = 0; i < fr.n; ++i) match_r[i] = -1;
+    std::vector<uint8_t> bl(blocked_l_in, blocked_l_in + cur_l->n), br(blocked_r_in, blocked_r_in + cur_r->n);
+    for (int i = 0; i < cur_l->n; ++i) match_l[i] = -1;
+    for (int i = 0; i < cur_r->n; ++i) match_r[i] = -1;
+    // one camera's claim of query i (:2556-2613 left, :2637-2678 right); `first`: the camera's offset in the histogram's entries
+    auto claim = [&](const CandLists& L, const orbm_frame_t* f, std::vector<uint8_t>& blocked, int32_t* match, int first, int i) {
+        const auto [bestDist, bestIdx2] = best_unblocked(L, i, blocked.data());
+        if (bestDist <= ORBM_TH_HIGH) {
+            match[bestIdx2] = i;
+            if (mp_obs[i]) blocked[bestIdx2] = 1;
+            nmatches++;
+            if (check_ori) rh.add(angle[i], f->kps[bestIdx2].angle, factor, bestIdx2 + first);
+        }
+    };
     for (int i = 0; i < nq; ++i) {
-        if (!valid[i] || cntL[i] == 0) continue;                            // an empty left window skips the right block too (:2551)
-        int bestDist = 256, bestIdx2 = -1;
-        for (int c = 0; c < cntL[i]; ++c) {
-            const int i2 = idxL[(size_t)i * capL + c];
-            if (bl[i2]) continue;
-            const int d = distL[(size_t)i * capL + c];
-            if (d < bestDist) { bestDist = d; bestIdx2 = i2; }
-        }
-        if (bestDist <= ORBM_TH_HIGH) {
-            match_l[bestIdx2] = i;
-            if (mp_obs[i]) bl[bestIdx2] = 1;
-            nmatches++;
-            if (check_ori) rh.add(angle[i], fl.kps[bestIdx2].angle, factor, bestIdx2);
-        }
-        bestDist = 256; bestIdx2 = -1;
-        for (int c = 0; c < cntR[i]; ++c) {
-            const int i2 = idxR[(size_t)i * capR + c];
-            if (br[i2]) continue;
-            const int d = distR[(size_t)i * capR + c];
-            if (d < bestDist) { bestDist = d; bestIdx2 = i2; }
-        }
-        if (bestDist <= ORBM_TH_HIGH) {
-            match_r[bestIdx2] = i;
-            if (mp_obs[i]) br[bestIdx2] = 1;
-            nmatches++;
-            if (check_ori) rh.add(angle[i], fr.kps[bestIdx2].angle, factor, bestIdx2 + Nleft);
-        }
+        if (!valid[i] || Ll.count(i) == 0) continue;                        // an empty left window skips the right block too (:2551)
+        claim(Ll, cur_l, bl, match_l, 0, i);
+        claim(Lr, cur_r, br, match_r, Nleft, i);
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b)
-            if (b != ind[0] && b != ind[1] && b != ind[2])
-                for (int k : rh.bins[b]) { if (k < Nleft) match_l[k] = ORBM_MATCH_PRUNED; else match_r[k - Nleft] = ORBM_MATCH_PRUNED; nmatches--; }
-    }
+    if (check_ori) rh.cull([&](int k) { if (k < Nleft) match_l[k] = ORBM_MATCH_PRUNED; else match_r[k - Nleft] = ORBM_MATCH_PRUNED; nmatches--; });
     return nmatches;
 }
 
@@ -1825,68 +1814,51 @@ int orbm_search_by_projection_points_fisheye(orbm_t* m, const orbm_frame_t* f_l,
                                              const uint8_t* qdesc, const uint8_t* mp_obs, float th, float nnratio, int32_t* match_l, int32_t* match_r) {
     if (!m || !f_l || !f_r || nq < 0) return ORBM_E_INVALID;
     const bool bFactor = th != 1.0;
-    std::vector<float> qrl(nq), qrr(nq);
-    std::vector<int> minL(nq), maxL(nq), minR(nq), maxR(nq);
+    WindowTables Wl(nq), Wr(nq);
     for (int i = 0; i < nq; ++i) {
-        if (!in_view[i]) { qrl[i] = -1.f; minL[i] = 0; maxL[i] = -1; }
+        if (!in_view[i]) Wl.skip(i);
         else {
             float r = view_cos[i] > 0.998 ? 2.5f : 4.0f;
             if (bFactor) r *= th;
-            qrl[i] = r * sf[level[i]]; minL[i] = level[i] - 1; maxL[i] = level[i];
+            Wl.set(i, r * sf[level[i]], level[i] - 1, level[i]);
         }
-        if (!in_view_r[i] || level_r[i] == -1) { qrr[i] = -1.f; minR[i] = 0; maxR[i] = -1; }
+        if (!in_view_r[i] || level_r[i] == -1) Wr.skip(i);
         else {
             const float r = view_cos_r[i] > 0.998 ? 2.5f : 4.0f;             // the right block applies no th factor (:174)
-            qrr[i] = r * sf[level_r[i]]; minR[i] = level_r[i] - 1; maxR[i] = level_r[i];
+            Wr.set(i, r * sf[level_r[i]], level_r[i] - 1, level_r[i]);
         }
     }
-    orbm_frame_t fl = *f_l, fr = *f_r; fl.uright = nullptr; fr.uright = nullptr;
-    int capL = std::max(1, std::min(fl.n, 2048)), capR = std::max(1, std::min(fr.n, 2048));      // row strides after window_pass
-    std::vector<int> cntL, idxL, distL, cntR, idxR, distR;
-    int rc = window_pass(m, &fl, nq, px, py, qrl.data(), minL.data(), maxL.data(), nullptr, nullptr, qdesc, capL, cntL, idxL, distL);
+    CandLists Ll, Lr;
+    int rc = window_lists(m, f_l, false, Wl.query(px, py, nullptr, nullptr, qdesc), 2048, Ll);
     if (rc) return rc;
-    rc = window_pass(m, &fr, nq, pxr, pyr, qrr.data(), minR.data(), maxR.data(), nullptr, nullptr, qdesc, capR, cntR, idxR, distR);
+    rc = window_lists(m, f_r, false, Wr.query(pxr, pyr, nullptr, nullptr, qdesc), 2048, Lr);
     if (rc) return rc;
     int nmatches = 0;
-    std::vector<uint8_t> bl(blocked_l_in, blocked_l_in + fl.n), br(blocked_r_in, blocked_r_in + fr.n);
-    for (int i = 0; i < fl.n; ++i) match_l[i] = -1;
-    for (int i = 0; i < fr.n; ++i) match_r[i] = -1;
+    std::vector<uint8_t> bl(blocked_l_in, blocked_l_in + f_l->n), br(blocked_r_in, blocked_r_in + f_r->n);
+    for (int i = 0; i < f_l->n; ++i) match_l[i] = -1;
+    for (int i = 0; i < f_r->n; ++i) match_r[i] = -1;
     for (int iMP = 0; iMP < nq; ++iMP) {
         if (!in_view[iMP] && !in_view_r[iMP]) continue;
-        if (in_view[iMP] && cntL[iMP] > 0) {
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-            for (int c = 0; c < cntL[iMP]; ++c) {
-                const int k = idxL[(size_t)iMP * capL + c];
-                if (bl[k]) continue;
-                const int d = distL[(size_t)iMP * capL + c];
-                if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = fl.kps[k].octave; bestIdx = k; }
-                else if (d < bestDist2) { bestLevel2 = fl.kps[k].octave; bestDist2 = d; }
-            }
-            if (bestDist <= ORBM_TH_HIGH) {
-                if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;          // :148-149 (skips the right block)
-                if (bestLevel != bestLevel2 || bestDist <= nnratio * bestDist2) {
-                    match_l[bestIdx] = iMP;
-                    if (mp_obs[iMP]) bl[bestIdx] = 1;
-                    if (l2r[bestIdx] != -1) { match_r[l2r[bestIdx]] = iMP; if (mp_obs[iMP]) br[l2r[bestIdx]] = 1; nmatches++; }
+        if (in_view[iMP] && Ll.count(iMP) > 0) {
+            const BestTwo b = best_two_levels(Ll, iMP, bl.data(), f_l->kps);
+            if (b.bestDist <= ORBM_TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;          // :151-152 (skips the right block)
+                if (b.bestLevel != b.bestLevel2 || b.bestDist <= nnratio * b.bestDist2) {
+                    match_l[b.bestIdx] = iMP;
+                    if (mp_obs[iMP]) bl[b.bestIdx] = 1;
+                    if (l2r[b.bestIdx] != -1) { match_r[l2r[b.bestIdx]] = iMP; if (mp_obs[iMP]) br[l2r[b.bestIdx]] = 1; nmatches++; }
                     nmatches++;
                 }
             }
         }
         if (in_view_r[iMP] && level_r[iMP] != -1) {
-            if (cntR[iMP] == 0) continue;
-            int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-            for (int c = 0; c < cntR[iMP]; ++c) {
-                const int k = idxR[(size_t)iMP * capR + c];
-                if (br[k]) continue;
-                const int d = distR[(size_t)iMP * capR + c];
-                if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = fr.kps[k].octave; bestIdx = k; }
-                else if (d < bestDist2) { bestLevel2 = fr.kps[k].octave; bestDist2 = d; }
-            }
-            if (bestDist <= ORBM_TH_HIGH) {
-                if (bestLevel == bestLevel2 && bestDist > nnratio * bestDist2) continue;
-                if (r2l[bestIdx] != -1) { match_l[r2l[bestIdx]] = iMP; if (mp_obs[iMP]) bl[r2l[bestIdx]] = 1; nmatches++; }
-                match_r[bestIdx] = iMP;
-                if (mp_obs[iMP]) br[bestIdx] = 1;
+            if (Lr.count(iMP) == 0) continue;
+            const BestTwo b = best_two_levels(Lr, iMP, br.data(), f_r->kps);
+            if (b.bestDist <= ORBM_TH_HIGH) {
+                if (b.bestLevel == b.bestLevel2 && b.bestDist > nnratio * b.bestDist2) continue;
+                if (r2l[b.bestIdx] != -1) { match_l[r2l[b.bestIdx]] = iMP; if (mp_obs[iMP]) bl[r2l[b.bestIdx]] = 1; nmatches++; }
+                match_r[b.bestIdx] = iMP;
+                if (mp_obs[iMP]) br[b.bestIdx] = 1;
                 nmatches++;
             }
         }
@@ -1900,23 +1872,20 @@ int orbm_search_by_bow_fisheye(orbm_t* m, int nkf, const orbm_kp_t* kps_kf, cons
                                int nnf, const int32_t* nodes_f, const int32_t* start_f, const int32_t* idx_f,
                                float nnratio, int check_ori, int32_t* f_match) {
     if (!m || nkf < 0 || nf < 0) return ORBM_E_INVALID;
-    JoinJobs J;
-    join_nodes(nnk, nodes_k, start_k, idx_k, nnf, nodes_f, start_f, J);
-    std::vector<int> dist;
-    int rc = bucket_pass(m, desc_kf, nkf, desc_f, nf, idx_f, start_f[nnf], J, dist);
+    BucketJobs B;
+    int rc = bucket_jobs(m, desc_kf, nkf, nnk, nodes_k, start_k, idx_k, desc_f, nf, nnf, nodes_f, start_f, idx_f, f_match, nf, B);
     if (rc) return rc;
-    for (int i = 0; i < nf; ++i) f_match[i] = -1;
     int nmatches = 0;
     RotHist rh;
     const float factor = ORBM_HISTO_LENGTH / 360.0f;
-    for (size_t j = 0; j < J.q.size(); ++j) {
-        const int iKF = J.q[j];
+    for (size_t j = 0; j < B.size(); ++j) {
+        const int iKF = B.query(j);
         if (!kf_good[iKF]) continue;
         int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256, bestDist1R = 256, bestIdxFR = -1, bestDist2R = 256;
-        for (int c = 0; c < J.len[j]; ++c) {
-            const int iF = idx_f[J.l2[j] + c];
+        for (int c = 0; c < B.count(j); ++c) {
+            const int iF = B.index(j, c);
             if (f_match[iF] >= 0) continue;
-            const int d = dist[J.off[j] + c];
+            const int d = B.distance(j, c);
             if (iF < nleft && d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdxF = iF; }
             else if (iF < nleft && d < bestDist2) bestDist2 = d;
             if (iF >= nleft && d < bestDist1R) { bestDist2R = bestDist1R; bestDist1R = d; bestIdxFR = iF; }
@@ -1935,14 +1904,7 @@ int orbm_search_by_bow_fisheye(orbm_t* m, int nkf, const orbm_kp_t* kps_kf, cons
             }
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            if (b == ind[0] || b == ind[1] || b == ind[2]) continue;
-            for (int i : rh.bins[b]) { f_match[i] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) rh.cull([&](int i) { f_match[i] = -1; nmatches--; });
     return nmatches;
 }
 
@@ -1952,24 +1914,21 @@ int orbm_search_by_bow_kf(orbm_t* m, int n1, const orbm_kp_t* kps1, const uint8_
                           int nn2, const int32_t* nodes2, const int32_t* start2, const int32_t* idx2,
                           float nnratio, int check_ori, int32_t* vpMatches12) {
     if (!m || n1 < 0 || n2 < 0) return ORBM_E_INVALID;
-    JoinJobs J;
-    join_nodes(nn1, nodes1, start1, idx1, nn2, nodes2, start2, J);
-    std::vector<int> dist;
-    int rc = bucket_pass(m, desc1, n1, desc2, n2, idx2, start2[nn2], J, dist);
+    BucketJobs B;
+    int rc = bucket_jobs(m, desc1, n1, nn1, nodes1, start1, idx1, desc2, n2, nn2, nodes2, start2, idx2, vpMatches12, n1, B);
     if (rc) return rc;
-    for (int i = 0; i < n1; ++i) vpMatches12[i] = -1;
     std::vector<uint8_t> vbMatched2(n2, 0);
     int nmatches = 0;
     RotHist rh;
     const float factor = ORBM_HISTO_LENGTH / 360.0f;                        // :978
-    for (size_t j = 0; j < J.q.size(); ++j) {
-        const int i1 = J.q[j];
+    for (size_t j = 0; j < B.size(); ++j) {
+        const int i1 = B.query(j);
         if (!good1[i1]) continue;
         int bestDist1 = 256, bestIdx2 = -1, bestDist2 = 256;
-        for (int c = 0; c < J.len[j]; ++c) {
-            const int i2 = idx2[J.l2[j] + c];
+        for (int c = 0; c < B.count(j); ++c) {
+            const int i2 = B.index(j, c);
             if (vbMatched2[i2] || !good2[i2]) continue;
-            const int d = dist[J.off[j] + c];
+            const int d = B.distance(j, c);
             if (d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdx2 = i2; }
             else if (d < bestDist2) bestDist2 = d;
         }
@@ -1980,14 +1939,7 @@ int orbm_search_by_bow_kf(orbm_t* m, int n1, const orbm_kp_t* kps1, const uint8_
             nmatches++;
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            if (b == ind[0] || b == ind[1] || b == ind[2]) continue;
-            for (int i : rh.bins[b]) { vpMatches12[i] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) rh.cull([&](int i) { vpMatches12[i] = -1; nmatches--; });
     return nmatches;
 }
 
@@ -1997,23 +1949,20 @@ int orbm_search_by_bow(orbm_t* m, int nkf, const orbm_kp_t* kps_kf, const uint8_
                        int nnf, const int32_t* nodes_f, const int32_t* start_f, const int32_t* idx_f,
                        float nnratio, int check_ori, int32_t* f_match) {
     if (!m || nkf < 0 || nf < 0) return ORBM_E_INVALID;
-    JoinJobs J;
-    join_nodes(nnk, nodes_k, start_k, idx_k, nnf, nodes_f, start_f, J);
-    std::vector<int> dist;
-    int rc = bucket_pass(m, desc_kf, nkf, desc_f, nf, idx_f, start_f[nnf], J, dist);
+    BucketJobs B;
+    int rc = bucket_jobs(m, desc_kf, nkf, nnk, nodes_k, start_k, idx_k, desc_f, nf, nnf, nodes_f, start_f, idx_f, f_match, nf, B);
     if (rc) return rc;
-    for (int i = 0; i < nf; ++i) f_match[i] = -1;
     int nmatches = 0;
     RotHist rh;
     const float factor = ORBM_HISTO_LENGTH / 360.0f;                        // :334
-    for (size_t j = 0; j < J.q.size(); ++j) {                              // jobs are in the reference's (node, iKF) order
-        const int iKF = J.q[j];
+    for (size_t j = 0; j < B.size(); ++j) {                                // jobs are in the reference's (node, iKF) order
+        const int iKF = B.query(j);
         if (!kf_good[iKF]) continue;
         int bestDist1 = 256, bestIdxF = -1, bestDist2 = 256;
-        for (int c = 0; c < J.len[j]; ++c) {
-            const int iF = idx_f[J.l2[j] + c];
+        for (int c = 0; c < B.count(j); ++c) {
+            const int iF = B.index(j, c);
             if (f_match[iF] >= 0) continue;                                 // :385 -- order-dependent gate
-            const int d = dist[J.off[j] + c];
+            const int d = B.distance(j, c);
             if (d < bestDist1) { bestDist2 = bestDist1; bestDist1 = d; bestIdxF = iF; }
             else if (d < bestDist2) bestDist2 = d;
         }
@@ -2023,14 +1972,7 @@ int orbm_search_by_bow(orbm_t* m, int nkf, const orbm_kp_t* kps_kf, const uint8_
             nmatches++;
         }
     }
-    if (check_ori) {
-        int ind[3];
-        rh.maxima(ind);
-        for (int b = 0; b < ORBM_HISTO_LENGTH; ++b) {
-            if (b == ind[0] || b == ind[1] || b == ind[2]) continue;
-            for (int i : rh.bins[b]) { f_match[i] = -1; nmatches--; }
-        }
-    }
+    if (check_ori) rh.cull([&](int i) { f_match[i] = -1; nmatches--; });
     return nmatches;
 }
 
