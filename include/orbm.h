@@ -958,6 +958,68 @@ int orbm_update_normal_and_depth_batch_async(orbm_t*, int nmp, int nkf_rows, int
                                              const float* pw, const int32_t* ref_row, const int32_t* ref_slot, const float* scale_factors_host, int nlevels,
                                              float* normal, float* min_dist, float* max_dist, uint8_t* updated);
 
+/* ---- KeyFrameDatabase queries: which KeyFrames go into the batched searches.  KeyFrameDatabase::DetectRelocalizationCandidates
+ * (KeyFrameDatabase.cc:869-981, caller Tracking.cc:4163) and DetectNBestCandidates (:660-866, caller LoopClosing.cc:592) up to and
+ * including the scores; the covisibility accumulation over the three result rows is facade/KeyFrameDatabase.h.
+ *
+ * orbm_bow_vector_batch_async: mBowVec rows on the device.  word_id / weight [nrows][cap] are the rows orbm_bow_transform_batch_async
+ * writes; counts [nrows], min(counts[r], cap) features per row (a negative count is 0).  Semantics: TemplatedVocabulary::transform for the
+ * header `0 0` (TemplatedVocabulary.h:1145-1161, :1193) with BowVector::addWeight and normalize (BowVector.cpp:34-46, :62-84): a feature
+ * with !(w > 0) is left out (zero, negative, NaN; :1157) -- so is one with a negative word id, which no transform writes --; the weights
+ * of one word are added in feature order; norm is the double sum of fabs in ascending word id; every value is divided by norm only if
+ * norm > 0.0.  Both sums are serial chains (double addition is not associative): one lane per word, one chain per row, nothing is
+ * reassociated, so the rows equal the host's orbm_bow_vectors bit for bit.  Outputs bow_word [nrows][cap] ascending and unique, bow_val
+ * [nrows][cap], nbow [nrows]; slots at or beyond nbow[r] keep the caller's bytes.  bow_val must not overlap weight.  Enqueue-only; no
+ * work buffer, every value is recomputed per launch and nothing accumulates across graph replays; capturable (orbx_capture_begin) after
+ * one eager call on the handle (the first call raises the kernel's LDS limit).  ORBM_E_INVALID: a NULL array, nrows or cap < 1.
+ * ORBM_E_CAPACITY: cap > ORBM_BOWVEC_MAX_CAP = 16384 (a row's 64-bit keys word << 32 | slot are sorted in LDS), nrows > 65535.  All
+ * checks run before anything is enqueued.
+ *
+ * orbm_kfdb_query (host pointers, synchronous) / orbm_kfdb_query_batch_async (device pointers, enqueue-only): one parameter list.
+ * The database is a pool of BowVector rows in the layout above: db_word / db_val [ndb_rows][db_cap], db_n [ndb_rows]; the row index is
+ * the order of the KeyFrameDatabase::add calls (:40-47).  db_active [ndb_rows] is 0 for a KeyFrame removed by erase / clearMap (:50-70,
+ * :79-103); NULL = all active.  Queries are rows q_row[q], q < nq, of a second pool q_word / q_val [nq_rows][q_cap], q_n [nq_rows], which
+ * may be the same arrays.  exclude [nq][ndb_rows] is spConnectedKF.count(pKFi) of DetectNBestCandidates (:692); NULL = none, the
+ * relocalization form.  Row lengths are clamped with min(n, cap) (negative = 0); rows must ascend as orbm_bow_vector_batch_async writes
+ * them.  Per query q and row r, with S = the words present in both vectors:
+ *   common [nq][ndb_rows]      |S| (mnRelocWords :890 / mnPlaceRecognitionWords :701); 0 for inactive or excluded rows
+ *   first_word [nq][ndb_rows]  the smallest word of S, -1 when common is 0
+ *   max_common [nq]            the maximum of common over the rows (:898-903, :717-722)
+ *   min_common [nq]            (int)((float)max_common * 0.8f): a float multiply with no contraction, then truncation (:905, :724)
+ *   nsharing [nq]              rows with common > 0 = lKFsSharingWords.size()
+ *   scored [nq][ndb_rows]      common > min_common, strict (:916, :739);  nscored [nq] = rows with scored set
+ *   score [nq][ndb_rows]       where scored: (float)(-s / 2.0), s = L1Scoring::score's double sum of fabs(vi - wi) - fabs(vi) - fabs(wi)
+ *                              over S in ascending word order (ScoringObject.cpp:23-68), vi from the query and wi from the row;
+ *                              0.0f where scored is 0
+ * With nsharing == 0 every output of that query is 0 / -1 (:894, :712).
+ * List order.  The reference's lKFsSharingWords is exactly the rows with common > 0 sorted by (first_word, r): the inverted-file walk
+ * visits the query's words in ascending order and each word's list in add order (:877-891, :675-709), and a KeyFrame enters the list at
+ * the first word it shares, its first_word; KeyFrames that enter at one word do so in that word's list order, which is add order = row
+ * order.  So a stable sort of the sharing rows by first_word rebuilds the list, and with it the order of lScoreAndMatch.
+ * The intersection is parallel (a wave per (query, row), binary search in the query's words); the sum is one serial chain per scored
+ * row in word order.  max_common, nsharing and nscored are reduced across rows with integer atomics and are zeroed by memsets inside
+ * the enqueued work, so a replayed graph starts clean; no scratch.  Capturable at once.  ORBM_E_INVALID: a NULL required array
+ * (db_active and exclude may be NULL); nq, nq_rows, q_cap, ndb_rows or db_cap < 1; in the host form a q_row entry outside [0, nq_rows).
+ * In the device form such a query writes the empty result (all 0 / -1).  ORBM_E_CAPACITY: q_cap or db_cap > 65535, ndb_rows >
+ * ORBM_KFDB_MAX_ROWS, nq > ORBM_KFDB_MAX_QUERIES.  All checks run before anything is enqueued and leave the outputs untouched.  Nothing
+ * reads out of bounds.  No CPU fallback: ORBM_E_HIP without a device.  Both return ORBM_OK. */
+enum { ORBM_BOWVEC_MAX_CAP = 16384 };
+enum { ORBM_KFDB_MAX_ROWS = 1 << 20, ORBM_KFDB_MAX_QUERIES = 65535 };
+int orbm_bow_vector_batch_async(orbm_t*, const int32_t* word_id, const double* weight, const int32_t* counts, int nrows, int cap,
+                                int32_t* bow_word, double* bow_val, int32_t* nbow);
+int orbm_kfdb_query(orbm_t*, int nq, const int32_t* q_row,
+                    int nq_rows, int q_cap, const int32_t* q_word, const double* q_val, const int32_t* q_n,
+                    int ndb_rows, int db_cap, const int32_t* db_word, const double* db_val, const int32_t* db_n,
+                    const uint8_t* db_active, const uint8_t* exclude,
+                    int32_t* common, int32_t* first_word, float* score, uint8_t* scored,
+                    int32_t* max_common, int32_t* min_common, int32_t* nsharing, int32_t* nscored);
+int orbm_kfdb_query_batch_async(orbm_t*, int nq, const int32_t* q_row,
+                                int nq_rows, int q_cap, const int32_t* q_word, const double* q_val, const int32_t* q_n,
+                                int ndb_rows, int db_cap, const int32_t* db_word, const double* db_val, const int32_t* db_n,
+                                const uint8_t* db_active, const uint8_t* exclude,
+                                int32_t* common, int32_t* first_word, float* score, uint8_t* scored,
+                                int32_t* max_common, int32_t* min_common, int32_t* nsharing, int32_t* nscored);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -22,6 +22,8 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4
 HOST, DEVICE = 0, 1
 DEPTH_U16, DEPTH_F32 = 0, 1                          # include/orbm.h: ORBM_DEPTH_*
 DEPTH_SELECT_MAX_CAP = 16384                         # include/orbm.h: ORBM_DEPTH_SELECT_MAX_CAP
+BOWVEC_MAX_CAP = 16384                               # include/orbm.h: ORBM_BOWVEC_MAX_CAP
+KFDB_MAX_ROWS, KFDB_MAX_QUERIES = 1 << 20, 65535     # include/orbm.h: ORBM_KFDB_MAX_ROWS, ORBM_KFDB_MAX_QUERIES
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -921,6 +923,13 @@ def _install_search():
                                      ci, vp, vp, vp, vp, vp,                       # nobs, obs_off, obs_row, obs_slot, obs_flags, valid
                                      vp, vp, vp, vp, ci,                           # pw, ref_row, ref_slot, scale factors (host), nlevels
                                      vp, vp, vp, vp]                               # normal, min_dist, max_dist, updated
+    L.orbm_bow_vector_batch_async.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp]           # word_id, weight, counts, nrows, cap, outputs
+    for name in ("orbm_kfdb_query", "orbm_kfdb_query_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, vp,                                   # nq, q_row
+                                     ci, ci, vp, vp, vp,                           # nq_rows, q_cap, q_word, q_val, q_n
+                                     ci, ci, vp, vp, vp,                           # ndb_rows, db_cap, db_word, db_val, db_n
+                                     vp, vp,                                       # db_active, exclude
+                                     vp, vp, vp, vp, vp, vp, vp, vp]               # common, first_word, score, scored, max / min_common, nsharing, nscored
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -1047,6 +1056,48 @@ def _install_search():
                                                                     obs_slot, obs_flags, valid, pw, ref_row, ref_slot, _p(sf), len(sf),
                                                                     normal, min_dist, max_dist, updated), "orbm_update_normal_and_depth_batch_async")
 
+    def bow_vector_batch_async(self, word_id, weight, counts, nrows, cap, bow_word, bow_val, nbow):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_bow_vector_batch_async)."""
+        return _chk(self.L.orbm_bow_vector_batch_async(self.h, word_id, weight, counts, nrows, cap, bow_word, bow_val, nbow),
+                    "orbm_bow_vector_batch_async")
+
+    def kfdb_query(self, q_row, q_word, q_val, q_n, db_word, db_val, db_n, db_active=None, exclude=None):
+        """The inverted-file walk, the 0.8 rule and the L1 scores of KeyFrameDatabase::DetectRelocalizationCandidates / DetectNBestCandidates
+        (KeyFrameDatabase.cc:869-926, :660-752) for the queries q_row of the pool q_word / q_val [nq_rows][q_cap], q_n against the pool
+        db_word / db_val [ndb_rows][db_cap], db_n -> dict of common, first_word, score, scored [nq][ndb_rows] and max_common, min_common,
+        nsharing, nscored [nq] (include/orbm.h: orbm_kfdb_query)."""
+        qr = np.ascontiguousarray(q_row, np.int32); nq = len(qr)
+        qw = np.ascontiguousarray(q_word, np.int32); qv = np.ascontiguousarray(q_val, np.float64); qn = np.ascontiguousarray(q_n, np.int32)
+        same = q_word is db_word and q_val is db_val and q_n is db_n
+        dw, dv, dn = (qw, qv, qn) if same else (np.ascontiguousarray(db_word, np.int32), np.ascontiguousarray(db_val, np.float64),
+                                                np.ascontiguousarray(db_n, np.int32))
+        if qw.ndim != 2 or dw.ndim != 2 or qv.shape != qw.shape or dv.shape != dw.shape or len(qn) != len(qw) or len(dn) != len(dw):
+            raise OrbError("a pool is word [rows][cap], val [rows][cap] and n [rows]")
+        ndb = len(dw)
+        act = None if db_active is None else np.ascontiguousarray(db_active, np.uint8)
+        exc = None if exclude is None else np.ascontiguousarray(exclude, np.uint8)
+        if (act is not None and act.shape != (ndb,)) or (exc is not None and exc.shape != (nq, ndb)):
+            raise OrbError("db_active holds one flag per database row and exclude one per (query, row)")
+        shape = (max(nq, 1), max(ndb, 1))
+        out = {"common": np.zeros(shape, np.int32), "first_word": np.zeros(shape, np.int32), "score": np.zeros(shape, np.float32),
+               "scored": np.zeros(shape, np.uint8), "max_common": np.zeros(shape[0], np.int32), "min_common": np.zeros(shape[0], np.int32),
+               "nsharing": np.zeros(shape[0], np.int32), "nscored": np.zeros(shape[0], np.int32)}
+        _chk(self.L.orbm_kfdb_query(self.h, nq, _p(qr), len(qw), qw.shape[1], _p(qw), _p(qv), _p(qn), ndb, dw.shape[1], _p(dw), _p(dv), _p(dn),
+                                    None if act is None else _p(act), None if exc is None else _p(exc),
+                                    *[_p(out[k]) for k in ("common", "first_word", "score", "scored", "max_common", "min_common", "nsharing", "nscored")]),
+             "orbm_kfdb_query")
+        return {k: v[:nq] for k, v in out.items()}
+
+    def kfdb_query_batch_async(self, nq, q_row, nq_rows, q_cap, q_word, q_val, q_n, ndb_rows, db_cap, db_word, db_val, db_n, db_active, exclude,
+                               common, first_word, score, scored, max_common, min_common, nsharing, nscored):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_kfdb_query_batch_async)."""
+        return _chk(self.L.orbm_kfdb_query_batch_async(self.h, nq, q_row, nq_rows, q_cap, q_word, q_val, q_n, ndb_rows, db_cap, db_word, db_val, db_n,
+                                                       db_active, exclude, common, first_word, score, scored, max_common, min_common, nsharing,
+                                                       nscored), "orbm_kfdb_query_batch_async")
+
+    ORBmatcher.BowVectorBatchAsync = bow_vector_batch_async
+    ORBmatcher.KfdbQuery = kfdb_query
+    ORBmatcher.KfdbQueryBatchAsync = kfdb_query_batch_async
     ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
     ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
     ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
@@ -1137,6 +1188,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_select_depth_points", "orbm_select_depth_points_batch_async", "orbm_adopt_new_points_batch_async",
             "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async",
             "orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async",
+            "orbm_bow_vector_batch_async", "orbm_kfdb_query", "orbm_kfdb_query_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

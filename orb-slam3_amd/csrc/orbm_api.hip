@@ -38,6 +38,7 @@ struct orbm {
     hipEvent_t e0 = nullptr, e1 = nullptr, e2 = nullptr;
     bool timed = false, gridFirst = false;
     bool dselLds = false;                                      // k_depth_select's dynamic LDS limit has been raised (orbm_select_depth_points*)
+    bool bowvLds = false;                                      // k_bow_vector's dynamic LDS limit has been raised (orbm_bow_vector_batch_async)
     bool initLds = false;                                      // k_init_search's dynamic LDS limit has been raised (orbm_search_for_initialization_batch_async)
     // Scratch arena of the single-frame entry points: ONE device block and a pinned host mirror of the same size.  Uploads are
     // staged in the mirror and sent with one asynchronous copy before the kernel, results come back with one copy after it
@@ -2768,6 +2769,115 @@ int orbm_update_normal_and_depth(orbm_t* m, int nmp, int nkf_rows, int cap, cons
     int cnt = 0;
     for (int i = 0; i < nmp; ++i) cnt += updated[i] ? 1 : 0;
     return cnt;
+}
+
+// ---- KeyFrameDatabase queries: BowVector rows on the device, then DetectRelocalizationCandidates / DetectNBestCandidates up to the scores ----
+int orbm_bow_vector_batch_async(orbm_t* m, const int32_t* word_id, const double* weight, const int32_t* counts, int nrows, int cap,
+                                int32_t* bow_word, double* bow_val, int32_t* nbow) {
+    if (!m || !word_id || !weight || !counts || !bow_word || !bow_val || !nbow) { set_merr("BowVector batch: a required array is NULL"); return ORBM_E_INVALID; }
+    if (nrows < 1 || cap < 1) { set_merr("BowVector batch: nrows and cap must be >= 1"); return ORBM_E_INVALID; }
+    if (cap > ORBM_BOWVEC_MAX_CAP) {
+        set_merr("BowVector batch: cap %d above %d (the row's 64-bit keys are sorted in LDS)", cap, (int)ORBM_BOWVEC_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (nrows > 65535) { set_merr("BowVector batch: %d rows in one call (at most 65535)", nrows); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    if (!m->bowvLds) {                                                       // once per handle, on its first (eager) call: the largest legal size
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(m->stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive) {
+            set_merr("BowVector batch: inside a capture, run the call once eagerly first");
+            return ORBM_E_HIP;
+        }
+        MHIPCHK(hipFuncSetAttribute((const void*)k_bow_vector, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    (int)(ORBM_BOWVEC_MAX_CAP * sizeof(unsigned long long))));
+        m->bowvLds = true;
+    }
+    int n2 = 1;
+    while (n2 < cap) n2 <<= 1;
+    const int threads = std::min(1024, std::max(64, n2 / 2));                // one thread per pair of the bitonic network, whole waves
+    hipLaunchKernelGGL(k_bow_vector, dim3(nrows), dim3(threads), (size_t)n2 * sizeof(unsigned long long), m->stream, word_id, weight, counts, cap, n2,
+                       bow_word, bow_val, nbow);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+// the argument tests the host and the device form share
+static int kfdb_args(const char* who, orbm_t* m, int nq, const int32_t* q_row, int nq_rows, int q_cap, const int32_t* q_word, const double* q_val,
+                     const int32_t* q_n, int ndb_rows, int db_cap, const int32_t* db_word, const double* db_val, const int32_t* db_n,
+                     int32_t* common, int32_t* first_word, float* score, uint8_t* scored, int32_t* max_common, int32_t* min_common,
+                     int32_t* nsharing, int32_t* nscored) {
+    if (!m || !q_row || !q_word || !q_val || !q_n || !db_word || !db_val || !db_n || !common || !first_word || !score || !scored || !max_common ||
+        !min_common || !nsharing || !nscored) {
+        set_merr("%s: a required array is NULL", who);
+        return ORBM_E_INVALID;
+    }
+    if (nq < 1 || nq_rows < 1 || q_cap < 1 || ndb_rows < 1 || db_cap < 1) {
+        set_merr("%s: nq, nq_rows, q_cap, ndb_rows and db_cap must be >= 1", who);
+        return ORBM_E_INVALID;
+    }
+    if (q_cap > 65535 || db_cap > 65535) { set_merr("%s: q_cap %d / db_cap %d above 65535", who, q_cap, db_cap); return ORBM_E_CAPACITY; }
+    if (ndb_rows > ORBM_KFDB_MAX_ROWS) { set_merr("%s: %d database rows (at most %d)", who, ndb_rows, (int)ORBM_KFDB_MAX_ROWS); return ORBM_E_CAPACITY; }
+    if (nq > ORBM_KFDB_MAX_QUERIES) { set_merr("%s: %d queries in one call (at most %d)", who, nq, (int)ORBM_KFDB_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    return ORBM_OK;
+}
+
+int orbm_kfdb_query_batch_async(orbm_t* m, int nq, const int32_t* q_row, int nq_rows, int q_cap, const int32_t* q_word, const double* q_val,
+                                const int32_t* q_n, int ndb_rows, int db_cap, const int32_t* db_word, const double* db_val, const int32_t* db_n,
+                                const uint8_t* db_active, const uint8_t* exclude, int32_t* common, int32_t* first_word, float* score,
+                                uint8_t* scored, int32_t* max_common, int32_t* min_common, int32_t* nsharing, int32_t* nscored) {
+    const int rc = kfdb_args("KeyFrameDatabase query batch", m, nq, q_row, nq_rows, q_cap, q_word, q_val, q_n, ndb_rows, db_cap, db_word, db_val, db_n,
+                             common, first_word, score, scored, max_common, min_common, nsharing, nscored);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const KfdbParams P{nq, nq_rows, q_cap, ndb_rows, db_cap, q_row, q_word, q_val, q_n, db_word, db_val, db_n, db_active, exclude};
+    // the three reduced rows start from zero inside the enqueued work: a replayed graph replays the memsets
+    MHIPCHK(hipMemsetAsync(max_common, 0, sizeof(int32_t) * nq, m->stream));
+    MHIPCHK(hipMemsetAsync(nsharing, 0, sizeof(int32_t) * nq, m->stream));
+    MHIPCHK(hipMemsetAsync(nscored, 0, sizeof(int32_t) * nq, m->stream));
+    const dim3 grid((ndb_rows + 3) / 4, nq);
+    hipLaunchKernelGGL(k_kfdb_common, grid, dim3(256), 0, m->stream, P, common, first_word, max_common, nsharing);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_kfdb_score, grid, dim3(256), 0, m->stream, P, common, max_common, score, scored, min_common, nscored);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_kfdb_query(orbm_t* m, int nq, const int32_t* q_row, int nq_rows, int q_cap, const int32_t* q_word, const double* q_val,
+                    const int32_t* q_n, int ndb_rows, int db_cap, const int32_t* db_word, const double* db_val, const int32_t* db_n,
+                    const uint8_t* db_active, const uint8_t* exclude, int32_t* common, int32_t* first_word, float* score,
+                    uint8_t* scored, int32_t* max_common, int32_t* min_common, int32_t* nsharing, int32_t* nscored) {
+    int rc = kfdb_args("KeyFrameDatabase query", m, nq, q_row, nq_rows, q_cap, q_word, q_val, q_n, ndb_rows, db_cap, db_word, db_val, db_n,
+                       common, first_word, score, scored, max_common, min_common, nsharing, nscored);
+    if (rc) return rc;
+    for (int q = 0; q < nq; ++q)
+        if (q_row[q] < 0 || q_row[q] >= nq_rows) { set_merr("KeyFrameDatabase query: q_row[%d] = %d outside [0, %d)", q, q_row[q], nq_rows); return ORBM_E_INVALID; }
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t nqs = (size_t)nq_rows * q_cap, nds = (size_t)ndb_rows * db_cap, nout = (size_t)nq * ndb_rows;
+    const bool same = q_word == db_word && q_val == db_val && q_n == db_n && nq_rows == ndb_rows && q_cap == db_cap;   // one pool: one upload
+    DevBuf dqr, dqw, dqv, dqn, dw, dv, dn, da, dx, dcnt, dcom, dfw, dsc, dsd;
+    arena_reset(m);
+    UP(dqr, q_row, sizeof(int32_t) * nq);
+    UP(dw, db_word, sizeof(int32_t) * nds); UP(dv, db_val, sizeof(double) * nds); UP(dn, db_n, sizeof(int32_t) * ndb_rows);
+    if (!same) { UP(dqw, q_word, sizeof(int32_t) * nqs); UP(dqv, q_val, sizeof(double) * nqs); UP(dqn, q_n, sizeof(int32_t) * nq_rows); }
+    if (db_active) UP(da, db_active, ndb_rows);
+    if (exclude) UP(dx, exclude, nout);
+    AL(dcnt, sizeof(int32_t) * 4 * nq); AL(dcom, sizeof(int32_t) * nout); AL(dfw, sizeof(int32_t) * nout); AL(dsc, sizeof(float) * nout); AL(dsd, nout);
+    ARENA_FLUSH(m);
+    int32_t* cnt = dcnt.as<int32_t>();
+    rc = orbm_kfdb_query_batch_async(m, nq, dqr.as<int32_t>(), nq_rows, q_cap, same ? dw.as<int32_t>() : dqw.as<int32_t>(),
+                                     same ? dv.as<double>() : dqv.as<double>(), same ? dn.as<int32_t>() : dqn.as<int32_t>(), ndb_rows, db_cap,
+                                     dw.as<int32_t>(), dv.as<double>(), dn.as<int32_t>(), db_active ? da.as<uint8_t>() : nullptr,
+                                     exclude ? dx.as<uint8_t>() : nullptr, dcom.as<int32_t>(), dfw.as<int32_t>(), dsc.as<float>(), dsd.as<uint8_t>(),
+                                     cnt, cnt + nq, cnt + 2 * (size_t)nq, cnt + 3 * (size_t)nq);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(common, dcom.host(), sizeof(int32_t) * nout); memcpy(first_word, dfw.host(), sizeof(int32_t) * nout);
+    memcpy(score, dsc.host(), sizeof(float) * nout); memcpy(scored, dsd.host(), nout);
+    const int32_t* hc = (const int32_t*)dcnt.host();
+    memcpy(max_common, hc, sizeof(int32_t) * nq); memcpy(min_common, hc + nq, sizeof(int32_t) * nq);
+    memcpy(nsharing, hc + 2 * (size_t)nq, sizeof(int32_t) * nq); memcpy(nscored, hc + 3 * (size_t)nq, sizeof(int32_t) * nq);
+    return ORBM_OK;
 }
 
 }  // extern "C"

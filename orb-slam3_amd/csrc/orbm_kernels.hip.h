@@ -4549,6 +4549,212 @@ __global__ __launch_bounds__(256) void k_mp_normal_depth(const KpIn* __restrict_
     updated[mp] = ok;
 }
 
+// ------------------------------------------------------------------------------------------------
+// k_bow_vector: the BowVector of one row of (word, weight) features -- TemplatedVocabulary::transform for the header `0 0`
+// (TemplatedVocabulary.h:1145-1161, :1193) with BowVector::addWeight and BowVector::normalize(L1) (BowVector.cpp:34-46, :62-84).
+// One workgroup per row.
+//   keys    one 64-bit key per feature i < n with weight > 0 and word >= 0: word << 32 | i; every other slot and the padding to
+//           n2 = a power of two hold all ones.  k_depth_select's bitonic network sorts them in LDS, so that the features of one word are
+//           neighbours in feature order and the words ascend: std::map's order.
+//   sums    the lane at the head of a run adds the run's weights one after the other in feature order (v = w0; v = v + w1; ...):
+//           double addition is not associative and nothing is reassociated.  The head's output position is the number of heads before
+//           it (ballot prefix inside the wave, wave totals through LDS).  bow_word / bow_val receive the word and the raw sum.
+//   norm    wave 0 reads the raw sums back 64 at a time and adds fabs of lane 0, 1, 2, ... into one wave-uniform double: ONE serial
+//           chain in ascending word id.  Every value is then divided by it, only if norm > 0.0.
+// Only positions below nbow[r] are written; every value is recomputed per launch, so nothing accumulates across graph replays.
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void k_bow_vector(const int* __restrict__ word_id, const double* __restrict__ weight,
+                                                     const int* __restrict__ counts, int cap, int n2, int* __restrict__ bow_word,
+                                                     double* __restrict__ bow_val, int* __restrict__ nbow) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long bv_keys[];
+    __shared__ int sCnt[16];
+    __shared__ double sNorm;
+    const int r = blockIdx.x, tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wave = tid >> 6, nwaves = T >> 6;
+    const size_t o0 = (size_t)r * cap;
+    const int n = min(max(counts[r], 0), cap);
+    const int* wid = word_id + o0;
+    const double* wgt = weight + o0;
+    for (int i = tid; i < n2; i += T) {
+        unsigned long long key = ~0ull;
+        if (i < n) {
+            const int w = wid[i];
+            if (wgt[i] > 0 && w >= 0) key = ((unsigned long long)(unsigned)w << 32) | (unsigned)i;     // !(w > 0) is left out (:1157)
+        }
+        bv_keys[i] = key;
+    }
+    __syncthreads();
+    const int half = n2 >> 1;
+    for (int k = 2; k <= n2; k <<= 1) {                                      // k_depth_select's network, step for step
+        int j = k >> 1;
+        for (; j > 64; j >>= 1) {
+            for (int p = tid; p < half; p += T) {
+                const int i = 2 * p - (p & (j - 1)), q = i | j;
+                const unsigned long long a = bv_keys[i], b = bv_keys[q];
+                if ((a > b) == ((i & k) == 0)) { bv_keys[i] = b; bv_keys[q] = a; }
+            }
+            __syncthreads();
+        }
+        for (int p0 = tid & ~63; p0 < half; p0 += T) {
+            const int p = p0 + lane;
+            for (int jj = j; jj > 0; jj >>= 1) {
+                if (p < half) {
+                    const int i = 2 * p - (p & (jj - 1)), q = i | jj;
+                    const unsigned long long a = bv_keys[i], b = bv_keys[q];
+                    if ((a > b) == ((i & k) == 0)) { bv_keys[i] = b; bv_keys[q] = a; }
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                __builtin_amdgcn_wave_barrier();
+            }
+        }
+        __syncthreads();
+    }
+    int* ow = bow_word + o0;
+    double* ov = bow_val + o0;
+    int base = 0;                                                            // heads before this chunk of T positions
+    for (int p0 = 0; p0 < n2; p0 += T) {                                     // uniform trip count: every lane reaches the barriers
+        const int p = p0 + tid;
+        const unsigned long long key = p < n2 ? bv_keys[p] : ~0ull;
+        const int w = (int)(key >> 32);
+        const bool head = key != ~0ull && (p == 0 || (int)(bv_keys[p - 1] >> 32) != w);
+        const u64 bal = __ballot(head);
+        if (lane == 0) sCnt[wave] = __popcll(bal);
+        __syncthreads();
+        int before = base, total = 0;
+        for (int v = 0; v < nwaves; ++v) { const int c = sCnt[v]; total += c; if (v < wave) before += c; }
+        if (head) {
+            double v = wgt[(unsigned)key];
+            for (int e = p + 1; e < n2; ++e) {
+                const unsigned long long ke = bv_keys[e];
+                if (ke == ~0ull || (int)(ke >> 32) != w) break;
+                v = v + wgt[(unsigned)ke];
+            }
+            const int jo = before + __popcll(bal & ((1ull << lane) - 1));
+            ow[jo] = w; ov[jo] = v;
+        }
+        base += total;
+        __syncthreads();                                                     // sCnt is free for the next chunk
+    }
+    const int nb = base;
+    if (wave == 0) {
+        double norm = 0.0;
+        for (int c0 = 0; c0 < nb; c0 += 64) {
+            const int cnt = min(64, nb - c0);
+            const double mine = lane < cnt ? ov[c0 + lane] : 0.0;
+            for (int l = 0; l < cnt; ++l) norm = norm + fabs(__shfl(mine, l));
+        }
+        if (lane == 0) { sNorm = norm; nbow[r] = nb; }
+    }
+    __syncthreads();
+    const double norm = sNorm;
+    if (norm > 0.0)
+        for (int jo = tid; jo < nb; jo += T) ov[jo] = ov[jo] / norm;
+}
+
+// ------------------------------------------------------------------------------------------------
+// KeyFrameDatabase queries: DetectRelocalizationCandidates (KeyFrameDatabase.cc:869-981) and DetectNBestCandidates (:660-866) as far as
+// the inverted file, the 0.8 rule and L1Scoring::score go.  ONE wave per (query q, database row r), four per workgroup; lanes over the
+// row's entries in chunks of 64, each lane looking its word up in the query's ascending words by binary search.
+// k_kfdb_common: common = sum of the ballot popcounts, first_word = the word of the first hit (the row ascends); one atomicMax and one
+//   atomicAdd per sharing row into max_common / nsharing, which a memset ahead of the kernel in the same stream zeroes: integer maximum
+//   and sum do not depend on their order, and a replayed graph starts from the memset.
+// k_kfdb_score: min_common = (int)((float)max_common * 0.8f), scored = common > min_common; a scored row repeats the lookup and adds
+//   fabs(vi - wi) - fabs(vi) - fabs(wi) (ScoringObject.cpp:41) for the set bits of each chunk's ballot in ascending lane = ascending
+//   word, every term broadcast from its lane into one wave-uniform double: L1Scoring::score's chain, in its order, without LDS.
+// Row lengths are min(max(n, 0), cap); a q_row outside [0, nq_rows) is an empty query.  Nothing is read out of bounds.
+// ------------------------------------------------------------------------------------------------
+struct KfdbParams {
+    int nq, nq_rows, q_cap, ndb_rows, db_cap;
+    const int* q_row; const int* q_word; const double* q_val; const int* q_n;
+    const int* db_word; const double* db_val; const int* db_n; const uint8_t* db_active; const uint8_t* exclude;
+};
+
+// the query's row: its length (0 for a q_row out of range) and the start of its arrays
+__device__ __forceinline__ int kfdb_query(const KfdbParams& P, int q, size_t& qo) {
+    const int qr = P.q_row[q];
+    qo = 0;
+    if ((unsigned)qr >= (unsigned)P.nq_rows) return 0;
+    qo = (size_t)qr * P.q_cap;
+    return min(max(P.q_n[qr], 0), P.q_cap);
+}
+// the database row's length as this query sees it: 0 when the row is inactive or excluded
+__device__ __forceinline__ int kfdb_row(const KfdbParams& P, int q, int r) {
+    if (P.db_active && !P.db_active[r]) return 0;
+    if (P.exclude && P.exclude[(size_t)q * P.ndb_rows + r]) return 0;
+    return min(max(P.db_n[r], 0), P.db_cap);
+}
+// position of word w in qw[0, nq), or -1
+__device__ __forceinline__ int kfdb_find(const int* __restrict__ qw, int nq, int w) {
+    int lo = 0, hi = nq;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (qw[mid] < w) lo = mid + 1; else hi = mid;
+    }
+    return (lo < nq && qw[lo] == w) ? lo : -1;
+}
+
+__global__ __launch_bounds__(256) void k_kfdb_common(KfdbParams P, int* __restrict__ common, int* __restrict__ first_word,
+                                                     int* __restrict__ max_common, int* __restrict__ nsharing) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), q = blockIdx.y;
+    if (r >= P.ndb_rows) return;                                             // wave-uniform
+    size_t qo;
+    const int nqw = kfdb_query(P, q, qo);
+    const int nr = nqw > 0 ? kfdb_row(P, q, r) : 0;
+    const int* qw = P.q_word + qo;
+    const int* rw = P.db_word + (size_t)r * P.db_cap;
+    int cnt = 0, first = -1;
+    for (int c0 = 0; c0 < nr; c0 += 64) {
+        const int i = c0 + lane;
+        const int w = i < nr ? rw[i] : 0;
+        const bool hit = i < nr && kfdb_find(qw, nqw, w) >= 0;
+        const u64 bal = __ballot(hit);
+        if (bal && first < 0) first = __shfl(w, __builtin_ctzll(bal));
+        cnt += __popcll(bal);
+    }
+    if (lane == 0) {
+        const size_t o = (size_t)q * P.ndb_rows + r;
+        common[o] = cnt; first_word[o] = first;
+        if (cnt > 0) { atomicMax(&max_common[q], cnt); atomicAdd(&nsharing[q], 1); }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_kfdb_score(KfdbParams P, const int* __restrict__ common, const int* __restrict__ max_common,
+                                                    float* __restrict__ score, uint8_t* __restrict__ scored,
+                                                    int* __restrict__ min_common, int* __restrict__ nscored) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6), q = blockIdx.y;
+    if (r >= P.ndb_rows) return;
+    const int minc = (int)__fmul_rn((float)max_common[q], 0.8f);             // KeyFrameDatabase.cc:905: a float product, truncated
+    if (r == 0 && lane == 0) min_common[q] = minc;
+    const size_t o = (size_t)q * P.ndb_rows + r;
+    const bool sc = common[o] > minc;                                        // strict (:916); common is 0 wherever the row is not searched
+    double s = 0.0;
+    if (sc) {
+        size_t qo;
+        const int nqw = kfdb_query(P, q, qo);
+        const int nr = kfdb_row(P, q, r);
+        const int* qw = P.q_word + qo;
+        const double* qv = P.q_val + qo;
+        const int* rw = P.db_word + (size_t)r * P.db_cap;
+        const double* rv = P.db_val + (size_t)r * P.db_cap;
+        for (int c0 = 0; c0 < nr; c0 += 64) {
+            const int i = c0 + lane;
+            const int pos = i < nr ? kfdb_find(qw, nqw, rw[i]) : -1;
+            double term = 0.0;
+            if (pos >= 0) {
+                const double vi = qv[pos], wi = rv[i];
+                term = fabs(vi - wi) - fabs(vi) - fabs(wi);
+            }
+            for (u64 m = __ballot(pos >= 0); m; m &= m - 1) s = s + __shfl(term, __builtin_ctzll(m));
+        }
+    }
+    if (lane == 0) {
+        score[o] = sc ? (float)(-s / 2.0) : 0.0f;
+        scored[o] = sc ? 1 : 0;
+        if (sc) atomicAdd(&nscored[q], 1);
+    }
+}
+
 // k_gather_rows: packs the used prefix of every row of the two [nq][cap] candidate arrays into [nq][maxc] (one contiguous
 // device-to-host copy instead of nq*cap entries or a strided copy).
 __global__ __launch_bounds__(256) void k_gather_rows(const int* __restrict__ idx, const int* __restrict__ dist, int nq, int cap, int maxc,
