@@ -1052,6 +1052,39 @@ int orbm_is_in_frustum(orbm_t*, int space, int n, const float* pw, const float* 
                        const float* rcw, const float* tcw, const float* ow, const float* k, const float* bounds,
                        float bf, float viewing_cos_limit, float log_scale_factor, int n_scale_levels,
                        uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr, float* depth, int32_t* level, float* view_cos);
+/* orbm_is_in_frustum_batch_async: the loop of Tracking::SearchLocalPoints (Tracking.cc:3808-3862) over Frame::isInFrustum for `nframes`
+ * frames in ONE launch, with everything that changes from frame to frame read from device rows: the producer of the query rows of
+ * orbm_search_by_projection_points_batch_async, written in place.  Frame f's pose is tcw [nframes][12], the row-major 3x4 [Rcw | tcw]
+ * (mRcwx, mtcwx; the layout of orbm_search_by_projection_kf_batch_async and orbm_fuse_batch_async), and ow [nframes][3] (mOwx); its point
+ * count is nq[f], used as min(max(nq[f], 0), q_stride).  The MapPoint rows pw / normal [..][q_stride][3] and min_dist / max_dist
+ * [..][q_stride] are [nframes] rows, or ONE row for every frame -- the same local map -- when q_shared != 0.  k_host = (fx, fy, cx, cy)
+ * and bounds_host = (minX, maxX, minY, maxY) are host pointers and, like bf, viewing_cos_limit, log_scale_factor and n_scale_levels, hold
+ * for every frame of the call.  Arithmetic, order of the gates and level rule are those of orbm_is_in_frustum: both forms run one device
+ * function and give the same bits.
+ * Skip rule: skip [nframes][q_stride] (always per frame; NULL = none) is step 1 of SearchLocalPoints, set by the caller to
+ * `pMP->mnLastFrameSeen == frame.mnId || pMP->isBad()`: a point already matched in the frame (:3844) or bad (:3847).  An entry with
+ * skip != 0 gets in_view = 0 and NOTHING ELSE of it is written -- the reference sets mbTrackInView = false (:3828) and leaves mTrackProjX/Y alone, and
+ * it never searches a bad point whatever its stale flag (ORBmatcher.cc:45-80).
+ * Tail rule: entries nq[f] <= i < q_stride get in_view = 0 and their other six fields are not written.
+ * Outputs, rows [nframes][q_stride] of the seven arrays orbm_search_by_projection_points_batch_async takes (depth is its th_far row): for a
+ * point that is neither skipped nor in the tail in_view is written always; proj_x / proj_y are -1 unless the point passed the image-bounds
+ * test and stay set when a later gate rejects it; proj_xr, depth, level and view_cos are written only where in_view == 1 -- a rejected
+ * point keeps the caller's bytes there.
+ * Count: n_in_view [nframes] (NULL = not wanted) = the number of entries of row f with in_view == 1, the reference's nToMatch (:3856).  It
+ * is summed with integer atomics into a row that a memset inside the enqueued work zeroes first: exact, and the same on every replay.
+ * All pointers are device pointers except k_host and bounds_host.  Enqueue-only, no scratch and no work buffer: the call can be captured
+ * (orbx_capture_begin) from the first call, and a replayed graph follows new poses, counts and skip flags in the rows.  The fisheye
+ * isInFrustum (Nleft != -1, KannalaBrandt8::project) stays with the caller.  ORBM_E_INVALID: a NULL required array (skip and n_in_view
+ * may be NULL); nframes, q_stride or n_scale_levels < 1; a viewing_cos_limit or log_scale_factor that is not finite.  ORBM_E_CAPACITY:
+ * nframes > 65535; q_stride > ORBM_LP_MAX_QUERIES.  Nothing is enqueued on either error and orbm_last_error names the argument.  A NULL
+ * handle is ORBM_E_HIP where there is no device (no CPU fallback) and ORBM_E_INVALID otherwise.  Returns ORBM_OK. */
+int orbm_is_in_frustum_batch_async(orbm_t*, int nframes, const float* tcw, const float* ow,
+                                   const int32_t* nq, int q_stride, const uint8_t* skip,
+                                   const float* pw, const float* normal, const float* min_dist, const float* max_dist, int q_shared,
+                                   const float* k_host, const float* bounds_host, float bf, float viewing_cos_limit,
+                                   float log_scale_factor, int n_scale_levels,
+                                   uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr, float* depth, int32_t* level, float* view_cos,
+                                   int32_t* n_in_view);
 
 #ifdef __cplusplus
 }

@@ -930,6 +930,10 @@ def _install_search():
                                      ci, ci, vp, vp, vp,                           # ndb_rows, db_cap, db_word, db_val, db_n
                                      vp, vp,                                       # db_active, exclude
                                      vp, vp, vp, vp, vp, vp, vp, vp]               # common, first_word, score, scored, max / min_common, nsharing, nscored
+    L.orbm_is_in_frustum_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp,                 # nframes, tcw, ow, nq, q_stride, skip
+                                                 vp, vp, vp, vp, ci,                         # pw, normal, min_dist, max_dist, q_shared
+                                                 vp, vp, cf, cf, cf, ci,                     # k, bounds (host), bf, cos limit, log scale factor, levels
+                                                 vp, vp, vp, vp, vp, vp, vp, vp]             # the seven rows, n_in_view
     L.orbm_vocab_load_text.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_char_p]
     L.orbm_vocab_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.orbm_vocab_destroy.argtypes = [C.c_void_p]
@@ -1095,6 +1099,17 @@ def _install_search():
                                                        db_active, exclude, common, first_word, score, scored, max_common, min_common, nsharing,
                                                        nscored), "orbm_kfdb_query_batch_async")
 
+    def is_in_frustum_batch(self, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, q_shared, K, bounds, bf, viewing_cos_limit,
+                            log_scale_factor, n_levels, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view=None):
+        """Frame::isInFrustum for every frame of a batch in one launch, enqueue only: every array argument is a device pointer except K =
+        (fx, fy, cx, cy) and bounds, which are host arrays (include/orbm.h: orbm_is_in_frustum_batch_async)."""
+        K = np.ascontiguousarray(K, np.float32); B = np.ascontiguousarray(bounds, np.float32)
+        return _chk(self.L.orbm_is_in_frustum_batch_async(self.h, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, int(q_shared),
+                                                          _p(K), _p(B), float(bf), float(viewing_cos_limit), float(log_scale_factor), int(n_levels),
+                                                          in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view),
+                    "orbm_is_in_frustum_batch_async")
+
+    ORBmatcher.isInFrustumBatch = is_in_frustum_batch
     ORBmatcher.BowVectorBatchAsync = bow_vector_batch_async
     ORBmatcher.KfdbQuery = kfdb_query
     ORBmatcher.KfdbQueryBatchAsync = kfdb_query_batch_async
@@ -1170,7 +1185,7 @@ def _frame_geometry_methods(prefix):
     return {"UndistortKeyPoints": UndistortKeyPoints, "ComputeImageBounds": ComputeImageBounds, "isInFrustum": isInFrustum}
 
 
-EXPORTS += ["orbm_undistort_keypoints", "orbm_image_bounds", "orbm_is_in_frustum"]
+EXPORTS += ["orbm_undistort_keypoints", "orbm_image_bounds", "orbm_is_in_frustum", "orbm_is_in_frustum_batch_async"]
 EXPORTS += ["orbm_frame_create", "orbm_frame_destroy", "orbm_frame_size", "orbm_search_by_projection_frame_resident", "orbm_search_by_projection_points_resident"]
 EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_projection_frame", "orbm_search_by_projection_points",
             "orbm_search_for_initialization", "orbm_search_for_triangulation", "orbm_search_by_bow", "orbm_stereo_matches",

@@ -2421,6 +2421,45 @@ int orbm_is_in_frustum(orbm_t* m, int space, int n, const float* pw, const float
     return cnt;
 }
 
+// Frame::isInFrustum for every frame of a batch in one launch: poses, counts and skip flags from device rows, the rows M3 reads written in place
+int orbm_is_in_frustum_batch_async(orbm_t* m, int nframes, const float* tcw, const float* ow, const int32_t* nq, int q_stride, const uint8_t* skip,
+                                   const float* pw, const float* normal, const float* min_dist, const float* max_dist, int q_shared,
+                                   const float* k_host, const float* bounds_host, float bf, float viewing_cos_limit, float log_scale_factor,
+                                   int n_scale_levels, uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr, float* depth, int32_t* level,
+                                   float* view_cos, int32_t* n_in_view) {
+    const char* who = "isInFrustum batch";
+    if (!m) {                                                                // no handle: orbm_create has refused, for want of a device or of a call
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_merr("%s: no HIP device: the MI355X matcher has no CPU fallback", who); return ORBM_E_HIP; }
+        set_merr("%s: the handle is NULL", who);
+        return ORBM_E_INVALID;
+    }
+    const struct { const void* p; const char* name; } req[] = {
+        {tcw, "tcw"}, {ow, "ow"}, {nq, "nq"}, {pw, "pw"}, {normal, "normal"}, {min_dist, "min_dist"}, {max_dist, "max_dist"}, {k_host, "k_host"},
+        {bounds_host, "bounds_host"}, {in_view, "in_view"}, {proj_x, "proj_x"}, {proj_y, "proj_y"}, {proj_xr, "proj_xr"}, {depth, "depth"},
+        {level, "level"}, {view_cos, "view_cos"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (nframes < 1) { set_merr("%s: nframes %d must be >= 1", who, nframes); return ORBM_E_INVALID; }
+    if (q_stride < 1) { set_merr("%s: q_stride %d must be >= 1", who, q_stride); return ORBM_E_INVALID; }
+    if (n_scale_levels < 1) { set_merr("%s: n_scale_levels %d must be >= 1", who, n_scale_levels); return ORBM_E_INVALID; }
+    if (!std::isfinite(viewing_cos_limit)) { set_merr("%s: viewing_cos_limit is not finite", who); return ORBM_E_INVALID; }
+    if (!std::isfinite(log_scale_factor)) { set_merr("%s: log_scale_factor is not finite", who); return ORBM_E_INVALID; }
+    if (nframes > 65535) { set_merr("%s: nframes %d above 65535", who, nframes); return ORBM_E_CAPACITY; }
+    if (q_stride > ORBM_LP_MAX_QUERIES) { set_merr("%s: q_stride %d above %d", who, q_stride, (int)ORBM_LP_MAX_QUERIES); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    FrustumParams C;
+    memset(&C, 0, sizeof(C));                                                // the pose fields come from the device rows
+    memcpy(C.k, k_host, sizeof(C.k)); memcpy(C.bounds, bounds_host, sizeof(C.bounds));
+    C.bf = bf; C.cosLimit = viewing_cos_limit; C.logSF = log_scale_factor; C.nLevels = n_scale_levels;
+    // the counts start from zero inside the enqueued work: a replayed graph replays the memset
+    if (n_in_view) MHIPCHK(hipMemsetAsync(n_in_view, 0, sizeof(int32_t) * nframes, m->stream));
+    hipLaunchKernelGGL(k_frustum_batch, dim3((q_stride + 255) / 256, nframes), dim3(256), 0, m->stream, tcw, ow, nq, q_stride, skip, pw, normal,
+                       min_dist, max_dist, q_shared ? 1 : 0, C, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
 // ---- RGB-D frames: Frame::ComputeStereoFromRGBD and Frame::UnprojectStereo ----------------------------------
 // the argument tests the host and the device form share; fills the kernel's parameter block
 static int rgbd_params(const char* who, int first, int cap, int depth_type, int w, int h, int stride_bytes, float depth_factor, float mbf, RgbdParams& P) {

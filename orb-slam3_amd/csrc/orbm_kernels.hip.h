@@ -4008,18 +4008,18 @@ __global__ __launch_bounds__(256) void k_undistort(const KpIn* __restrict__ in, 
 // k_frustum: Frame::isInFrustum (Nleft == -1, Frame.cc:603-671) + MapPoint::PredictScale (MapPoint.cc:725-740), one
 // thread per map point.  Float expressions in the reference's order (Matx products accumulate from 0 in float, cv::norm
 // accumulates in double); log(ratio) is evaluated in double and rounded to float (the host libm's logf is within 1 ulp of
-// that; the predicted level can differ only when log(ratio)/logScaleFactor is within an ulp of an integer).
+// that; the predicted level can differ only when log(ratio)/logScaleFactor is within an ulp of an integer).  The per-point body is
+// frustum_point, shared with k_frustum_batch: both forms give the same bits.
 // ------------------------------------------------------------------------------------------------
 struct FrustumParams { float rcw[9], tcw[3], ow[3], k[4], bounds[4], bf, cosLimit, logSF; int nLevels; };
 
-__global__ __launch_bounds__(256) void k_frustum(int n, const float* __restrict__ pw, const float* __restrict__ normal,
-                                                 const float* __restrict__ minDist, const float* __restrict__ maxDist, FrustumParams F,
-                                                 uint8_t* inView, float* projX, float* projY, float* projXR, float* depth, int* level,
-                                                 float* viewCos) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    inView[i] = 0; projX[i] = -1.f; projY[i] = -1.f;
-    const float P0 = pw[3 * i], P1 = pw[3 * i + 1], P2 = pw[3 * i + 2];
+// One map point: reads entry q of the MapPoint rows, writes entry o of the seven output rows; true where the point is in view.
+__device__ __forceinline__ bool frustum_point(const FrustumParams& F, const float* __restrict__ pw, const float* __restrict__ normal,
+                                              const float* __restrict__ minDist, const float* __restrict__ maxDist, size_t q, size_t o,
+                                              uint8_t* inView, float* projX, float* projY, float* projXR, float* depth, int* level,
+                                              float* viewCos) {
+    inView[o] = 0; projX[o] = -1.f; projY[o] = -1.f;
+    const float P0 = pw[3 * q], P1 = pw[3 * q + 1], P2 = pw[3 * q + 2];
     float Pc[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -4032,26 +4032,68 @@ __global__ __launch_bounds__(256) void k_frustum(int n, const float* __restrict_
     const float PcDist = (float)sqrt(n2);
     const float PcZ = Pc[2];
     const float invz = 1.0f / PcZ;
-    if (PcZ < 0.0f) return;
+    if (PcZ < 0.0f) return false;
     const float u = F.k[0] * Pc[0] / Pc[2] + F.k[2], v = F.k[1] * Pc[1] / Pc[2] + F.k[3];
-    if (u < F.bounds[0] || u > F.bounds[1]) return;
-    if (v < F.bounds[2] || v > F.bounds[3]) return;
-    projX[i] = u; projY[i] = v;
-    const float maxD = 1.2f * maxDist[i], minD = 0.8f * minDist[i];
+    if (u < F.bounds[0] || u > F.bounds[1]) return false;
+    if (v < F.bounds[2] || v > F.bounds[3]) return false;
+    projX[o] = u; projY[o] = v;
+    const float maxD = 1.2f * maxDist[q], minD = 0.8f * minDist[q];
     const float O0 = P0 - F.ow[0], O1 = P1 - F.ow[1], O2 = P2 - F.ow[2];
     double d2 = 0.0;
     d2 += (double)O0 * (double)O0; d2 += (double)O1 * (double)O1; d2 += (double)O2 * (double)O2;
     const float dist = (float)sqrt(d2);
-    if (dist < minD || dist > maxD) return;
+    if (dist < minD || dist > maxD) return false;
     float dot = 0.f;
-    dot += O0 * normal[3 * i]; dot += O1 * normal[3 * i + 1]; dot += O2 * normal[3 * i + 2];
+    dot += O0 * normal[3 * q]; dot += O1 * normal[3 * q + 1]; dot += O2 * normal[3 * q + 2];
     const float vc = dot / dist;
-    if (vc < F.cosLimit) return;
-    const float ratio = maxDist[i] / dist;
+    if (vc < F.cosLimit) return false;
+    const float ratio = maxDist[q] / dist;
     const float lg = (float)log((double)ratio);
     int ns = (int)ceilf(lg / F.logSF);
     if (ns < 0) ns = 0; else if (ns >= F.nLevels) ns = F.nLevels - 1;
-    inView[i] = 1; projXR[i] = u - F.bf * invz; depth[i] = PcDist; level[i] = ns; viewCos[i] = vc;
+    inView[o] = 1; projXR[o] = u - F.bf * invz; depth[o] = PcDist; level[o] = ns; viewCos[o] = vc;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_frustum(int n, const float* __restrict__ pw, const float* __restrict__ normal,
+                                                 const float* __restrict__ minDist, const float* __restrict__ maxDist, FrustumParams F,
+                                                 uint8_t* inView, float* projX, float* projY, float* projXR, float* depth, int* level,
+                                                 float* viewCos) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    frustum_point(F, pw, normal, minDist, maxDist, (size_t)i, (size_t)i, inView, projX, projY, projXR, depth, level, viewCos);
+}
+
+// k_frustum_batch: frustum_point for every (frame, point) of a batch in one launch, grid = (point blocks, frames).  Frame f's pose comes
+// from device rows -- tcw [nframes][12] row-major 3x4 [Rcw | tcw], ow [nframes][3]; f is blockIdx.y, so the fifteen loads are uniform --
+// and its count from nq[f], clamped to [0, qStride]: a replayed graph follows the rows.  C carries k, bounds, bf, cosLimit, logSF and
+// nLevels; its pose fields are not read.  The MapPoint rows are [nframes][qStride], or one row for all frames when qShared.  Entry i of
+// row f: i >= n or skip[f][i] != 0 -> inView = 0 and nothing else written; otherwise exactly what k_frustum writes.  nInView[f] (NULL =
+// not counted) += the popcount of each wave's in-view ballot: an integer sum into a row the caller's memset zeroes ahead of the launch
+// in the same stream, so it is exact, independent of the order and the same on every replay.  No LDS; every lane reaches the ballot.
+__global__ __launch_bounds__(256) void k_frustum_batch(const float* __restrict__ tcw, const float* __restrict__ ow, const int* __restrict__ nq,
+                                                       int qStride, const uint8_t* __restrict__ skip, const float* __restrict__ pw,
+                                                       const float* __restrict__ normal, const float* __restrict__ minDist,
+                                                       const float* __restrict__ maxDist, int qShared, FrustumParams C, uint8_t* inView,
+                                                       float* projX, float* projY, float* projXR, float* depth, int* level, float* viewCos,
+                                                       int* nInView) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(max(nq[f], 0), qStride);
+    FrustumParams F = C;
+    const float* T = tcw + 12 * (size_t)f;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        F.rcw[3 * r] = T[4 * r]; F.rcw[3 * r + 1] = T[4 * r + 1]; F.rcw[3 * r + 2] = T[4 * r + 2]; F.tcw[r] = T[4 * r + 3];
+        F.ow[r] = ow[3 * (size_t)f + r];
+    }
+    const size_t o = (size_t)f * qStride + i, q = qShared ? (size_t)i : o;
+    bool iv = false;
+    if (i < qStride) {
+        if (i >= n || (skip && skip[o])) inView[o] = 0;
+        else iv = frustum_point(F, pw, normal, minDist, maxDist, q, o, inView, projX, projY, projXR, depth, level, viewCos);
+    }
+    const u64 bal = __ballot(iv);
+    if (nInView && bal && (threadIdx.x & 63) == 0) atomicAdd(&nInView[f], __popcll(bal));
 }
 
 // ------------------------------------------------------------------------------------------------

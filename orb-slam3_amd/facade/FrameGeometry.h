@@ -2,6 +2,7 @@
 //   Frame::UndistortKeyPoints   (src/Frame.cc:924-970)   -> UndistortKeyPoints()
 //   Frame::ComputeImageBounds   (src/Frame.cc:977-1021)  -> ComputeImageBounds()
 //   Frame::isInFrustum for all local map points (src/Frame.cc:603-671, src/Tracking.cc:3808-3862) -> IsInFrustumBatch()
+//   the pose rows of the batched device form orbm_is_in_frustum_batch_async (mRcwx, mtcwx, mOwx) -> FrustumPoseRow()
 //   cvtColor(..., COLOR_*2GRAY) (src/Tracking.cc:1264-1290) -> see orbx_gray_from_color in include/orbx.h
 //   Frame::ComputeStereoFromRGBD (src/Frame.cc:1279-1309) + the depth conversion of GrabImageRGBD (src/Tracking.cc:1353-1354) -> ComputeStereoFromRGBD()
 //   Frame::UnprojectStereo for every keypoint (src/Frame.cc:1312-1326) -> UnprojectStereoAll()
@@ -57,6 +58,21 @@ inline int IsInFrustumBatch(orbm_t* m, const std::vector<float>& Pw3, const std:
                                       out.projXR.data(), out.depth.data(), out.level.data(), out.viewCos.data());
     if (rc < 0) throw std::runtime_error(std::string("orbm_is_in_frustum: ") + orbm_last_error());
     return rc;
+}
+
+// One frame's row of the pose arrays orbm_is_in_frustum_batch_async reads, from the members Frame::isInFrustum uses (Frame.cc:621, :651):
+// tcwRow[12] = the row-major 3x4 [mRcwx | mtcwx], owRow[3] = mOwx -- the very floats IsInFrustumBatch hands over as Rcw, tcw and Ow.
+// Upload row f to tcw + 12 * f and ow + 3 * f; a captured step then follows the frame's pose.  Pinhole frames (Nleft == -1) only: the
+// fisheye isInFrustum (KannalaBrandt8::project) stays with the caller.
+inline void FrustumPoseRow(const cv::Matx33f& Rcw, const cv::Matx31f& tcw, const cv::Matx31f& Ow, float tcwRow[12], float owRow[3]) {
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) tcwRow[4 * r + c] = Rcw(r, c);
+        tcwRow[4 * r + 3] = tcw(r);
+        owRow[r] = Ow(r);
+    }
+}
+template <class FrameT> inline void FrustumPoseRow(const FrameT& F, float tcwRow[12], float owRow[3]) {
+    FrustumPoseRow(F.mRcwx, F.mtcwx, F.mOwx, tcwRow, owRow);
 }
 
 // mvuRight, mvDepth of an RGB-D frame from the UNCONVERTED depth image and mDepthMapFactor: the caller drops its own
