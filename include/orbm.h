@@ -1020,6 +1020,71 @@ int orbm_kfdb_query_batch_async(orbm_t*, int nq, const int32_t* q_row,
                                 int32_t* common, int32_t* first_word, float* score, uint8_t* scored,
                                 int32_t* max_common, int32_t* min_common, int32_t* nsharing, int32_t* nscored);
 
+/* ---- KeyFrameCulling: the redundancy counts of LocalMapping::KeyFrameCulling (LocalMapping.cc:1218-1400) for every covisible KeyFrame
+ * of the new one in ONE call, over the arrays the MapPoint refresh already keeps resident.
+ * orbm_keyframe_culling (host pointers, synchronous) / orbm_keyframe_culling_batch_async (device pointers, enqueue-only): one parameter
+ * list.
+ * Inputs.  The KeyFrame pool kps_kf [nkf_rows][cap], counts_kf [nkf_rows] and the observation CSR obs_off [nmp + 1] / obs_row / obs_slot
+ * / obs_flags [nobs] follow the MapPoint refresh convention exactly: a two-camera KeyFrame is one stacked row, an entry is skipped when
+ * obs_row lies outside [0, nkf_rows) or obs_slot outside [0, min(counts_kf[row], cap)), a non-increasing obs_off pair, a pair that leaves
+ * [0, nobs] and a list of more than ORBM_MP_MAX_OBS entries are an empty list.  cand_row [ncand] = the pool rows of the candidates in the
+ * order of GetVectorCovisibleKeyFrames(); the caller leaves out the KeyFrames the reference skips (mnId == GetInitKFid() || isBad(),
+ * :1272).  kf_mp [ncand][cap] = per candidate slot the index of GetMapPointMatches()[i] in the call's MapPoint list; an index outside
+ * [0, nmp) means NULL.  depth [ncand][cap] = mvDepth; NULL means mbMonocular, no gate.  mp_valid [nmp] = !isBad(); NULL = all valid.
+ * mp_nobs [nmp] = Observations().  erased [nkf_rows] marks erased KeyFrames; NULL = none.  th_obs is 3; redundant_th is 0.9f or 0.5f
+ * (:1238-1245).
+ * Entry flags.  Bit 2 of obs_flags: the entry weighs 2 in nObs (!pKF->mpCamera2 && mvuRight[leftIndex] >= 0, MapPoint.cc:212, :232);
+ * otherwise it weighs 1.  The two refresh calls ignore bit 2.  Bit 1 (the KeyFrame isBad()) is ignored here: the reference does not test
+ * it.  Bit 0 = a right-camera observation, as before.
+ * Semantics.  Candidate k has r = cand_row[k] and walks the slots i < min(counts_kf[r], cap); a candidate with r out of range or
+ * erased[r] set gives zeros.  In this order:
+ *   1. j = kf_mp[k][i]; j NULL or mp_valid[j] == 0: the slot is not counted.
+ *   2. Over the live entries of MapPoint j (after the skip rules) E is the set of entries whose row is erased; nobs_eff = mp_nobs[j] -
+ *      the sum of the weights of E.  If E is not empty and nobs_eff <= 2 the MapPoint is bad by erasure and the slot is not counted
+ *      (MapPoint::EraseObservation, MapPoint.cc:220-257; MapPoint::SetBadFlag, :280-305).  nObs only falls, so testing the final value
+ *      equals the reference's test after each erase.
+ *   3. depth != NULL and (depth[k][i] > th_depth || depth[k][i] < 0), the reference's expression as written (:1295): not counted.  A
+ *      NaN depth is counted, -0.0 is counted, depth == th_depth is counted.
+ *   4. n_mps[k]++.
+ *   5. If nobs_eff > th_obs: L = kps_kf[r][i].octave, and the observing KeyFrames are counted.  An entry takes part if its row is not
+ *      erased and is not r; it passes if its keypoint's octave <= L + 1.  A right entry (bit 0) directly preceded in the list by a left
+ *      entry of the same row, both of them live, forms one KeyFrame with it, which counts once if either entry passes (the scaleLeveli
+ *      minimum of :1316-1328).  Any other arrangement counts per entry: this is defined here, not by the reference.  If the count is >
+ *      th_obs, n_redundant[k]++.  The reference's break at :1335 does not change the answer.
+ *   6. cull[k] = (float)n_redundant > redundant_th * (float)n_mps: one float multiply and one compare, with no contraction (:1349).
+ *      With 0.9f, 9 of 10 is not culled and 10 of 11 is.  first_cull (optional, NULL = not written) = the least k with cull[k] set, or -1.
+ *   7. slot_state [ncand][cap] (optional, NULL = not written): 0 = not counted, 1 = counted, 2 = redundant.  Every slot below cap is
+ *      written; 0 at and beyond the row's count.
+ * Deviation.  For a two-camera candidate the reference reads mvKeysRight[i].octave with the stacked index i (:1303-1305): past the end
+ * or the wrong feature.  The library reads slot i of the stacked row.
+ * The sequential rule.  A KeyFrame that is voted out is erased at once (KeyFrame::SetBadFlag, KeyFrame.cc:746-887), so a later
+ * candidate is counted on a changed map.  The results are exact for candidates 0 .. first_cull.  The caller then decides what to do
+ * with candidate first_cull -- in inertial mode the mPrevKF / mNextKF / time tests (:1352-1387) stay with the caller --; if the KeyFrame
+ * was really erased (isBad() afterwards; mbNotErase leaves it alive) the caller sets erased[row] = 1 and calls again for the remaining
+ * candidates.  No CSR, pool or kf_mp row is rebuilt.  Only while erased is all zero or NULL does a single call equal the reference for
+ * every candidate.  The rule assumes the map invariant that an observation entry of KeyFrame X exists exactly where X's mvpMapPoints
+ * holds that MapPoint.
+ * Outputs n_mps, n_redundant [ncand], cull [ncand], slot_state, first_cull [1].  The host form returns the number of candidates with
+ * cull set; the device form returns ORBM_OK.  The device form uses no scratch that survives a call: the counts are summed with integer
+ * atomics into n_mps / n_redundant, which memsets inside the enqueued work zero first, every output is recomputed per launch and nothing
+ * accumulates across graph replays; it is capturable (orbx_capture_begin) from the first call, and a replay follows rewritten erased,
+ * kf_mp, mp_valid, mp_nobs and cand_row rows.  With erased == NULL a list is left as soon as its count has passed th_obs; with an erased
+ * row every list is walked to its end; the outputs are the same.  Nothing reads out of bounds whatever the indices hold.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL required array (depth, mp_valid, erased, slot_state and first_cull may be NULL); ncand,
+ * nkf_rows, cap or nmp < 1; nobs < 0; th_obs < 0.  ORBM_E_CAPACITY: ncand > ORBM_KFCULL_MAX_CAND, cap > ORBM_KFCULL_MAX_CAP, nmp >
+ * ORBM_MP_MAX_BATCH, nkf_rows * cap > 2^31 - 1.  No CPU fallback: ORBM_E_HIP without a device. */
+enum { ORBM_KFCULL_MAX_CAND = 65535, ORBM_KFCULL_MAX_CAP = 65535 };
+int orbm_keyframe_culling(orbm_t*, int ncand, const int32_t* cand_row, int nkf_rows, int cap,
+                          const orbm_kp_t* kps_kf, const int32_t* counts_kf, const int32_t* kf_mp, const float* depth, float th_depth,
+                          int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot, const uint8_t* obs_flags,
+                          const uint8_t* mp_valid, const int32_t* mp_nobs, const uint8_t* erased, int th_obs, float redundant_th,
+                          int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, uint8_t* slot_state, int32_t* first_cull);
+int orbm_keyframe_culling_batch_async(orbm_t*, int ncand, const int32_t* cand_row, int nkf_rows, int cap,
+                                      const orbm_kp_t* kps_kf, const int32_t* counts_kf, const int32_t* kf_mp, const float* depth, float th_depth,
+                                      int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot, const uint8_t* obs_flags,
+                                      const uint8_t* mp_valid, const int32_t* mp_nobs, const uint8_t* erased, int th_obs, float redundant_th,
+                                      int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, uint8_t* slot_state, int32_t* first_cull);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -24,6 +24,7 @@ DEPTH_U16, DEPTH_F32 = 0, 1                          # include/orbm.h: ORBM_DEPT
 DEPTH_SELECT_MAX_CAP = 16384                         # include/orbm.h: ORBM_DEPTH_SELECT_MAX_CAP
 BOWVEC_MAX_CAP = 16384                               # include/orbm.h: ORBM_BOWVEC_MAX_CAP
 KFDB_MAX_ROWS, KFDB_MAX_QUERIES = 1 << 20, 65535     # include/orbm.h: ORBM_KFDB_MAX_ROWS, ORBM_KFDB_MAX_QUERIES
+KFCULL_MAX_CAND, KFCULL_MAX_CAP = 65535, 65535       # include/orbm.h: ORBM_KFCULL_MAX_CAND, ORBM_KFCULL_MAX_CAP
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -930,6 +931,12 @@ def _install_search():
                                      ci, ci, vp, vp, vp,                           # ndb_rows, db_cap, db_word, db_val, db_n
                                      vp, vp,                                       # db_active, exclude
                                      vp, vp, vp, vp, vp, vp, vp, vp]               # common, first_word, score, scored, max / min_common, nsharing, nscored
+    for name in ("orbm_keyframe_culling", "orbm_keyframe_culling_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, vp, ci, ci,                           # ncand, cand_row, nkf_rows, cap
+                                     vp, vp, vp, vp, cf,                           # kps_kf, counts_kf, kf_mp, depth, th_depth
+                                     ci, ci, vp, vp, vp, vp,                       # nmp, nobs, obs_off, obs_row, obs_slot, obs_flags
+                                     vp, vp, vp, ci, cf,                           # mp_valid, mp_nobs, erased, th_obs, redundant_th
+                                     vp, vp, vp, vp, vp]                           # n_mps, n_redundant, cull, slot_state, first_cull
     L.orbm_is_in_frustum_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp,                 # nframes, tcw, ow, nq, q_stride, skip
                                                  vp, vp, vp, vp, ci,                         # pw, normal, min_dist, max_dist, q_shared
                                                  vp, vp, cf, cf, cf, ci,                     # k, bounds (host), bf, cos limit, log scale factor, levels
@@ -1099,6 +1106,41 @@ def _install_search():
                                                        db_active, exclude, common, first_word, score, scored, max_common, min_common, nsharing,
                                                        nscored), "orbm_kfdb_query_batch_async")
 
+    def keyframe_culling(self, cand_row, kps_kf, counts_kf, kf_mp, depth, th_depth, obs_off, obs_row, obs_slot, obs_flags, mp_valid, mp_nobs,
+                         erased=None, th_obs=3, redundant_th=0.9, slot_state=True):
+        """The redundancy counts of LocalMapping::KeyFrameCulling (LocalMapping.cc:1218-1400) for the candidates cand_row of the KeyFrame
+        pool kps_kf [nkf_rows][cap] -> dict of n_mps, n_redundant, cull [ncand], slot_state [ncand][cap] (None when not asked for),
+        first_cull and ncull.  depth / mp_valid / erased may be None (include/orbm.h: orbm_keyframe_culling)."""
+        cr = np.ascontiguousarray(cand_row, np.int32); nc = len(cr)
+        k = np.ascontiguousarray(kps_kf, KP_DTYPE); nrows, cap = k.shape[0], k.shape[1]
+        cnt = np.ascontiguousarray(counts_kf, np.int32); km = np.ascontiguousarray(kf_mp, np.int32)
+        dp = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        no = np.ascontiguousarray(mp_nobs, np.int32); nmp = len(no)
+        off, row, slot, fl, v, nobs = _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, mp_valid, nmp)
+        er = None if erased is None else np.ascontiguousarray(erased, np.uint8)
+        if km.shape != (nc, cap) or (dp is not None and dp.shape != (nc, cap)) or len(cnt) != nrows or (er is not None and er.shape != (nrows,)):
+            raise OrbError("kf_mp / depth hold one row of cap slots per candidate; counts_kf and erased one entry per pool row")
+        out = {"n_mps": np.zeros(max(nc, 1), np.int32), "n_redundant": np.zeros(max(nc, 1), np.int32), "cull": np.zeros(max(nc, 1), np.uint8)}
+        ss = np.zeros((max(nc, 1), cap), np.uint8) if slot_state else None
+        fc = np.zeros(1, np.int32)
+        rc = _chk(self.L.orbm_keyframe_culling(self.h, nc, _p(cr), nrows, cap, _p(k), _p(cnt), _p(km), None if dp is None else _p(dp), float(th_depth),
+                                               nmp, nobs, _p(off), _p(row), _p(slot), _p(fl), None if v is None else _p(v), _p(no),
+                                               None if er is None else _p(er), int(th_obs), float(redundant_th),
+                                               _p(out["n_mps"]), _p(out["n_redundant"]), _p(out["cull"]), None if ss is None else _p(ss), _p(fc)),
+                  "orbm_keyframe_culling")
+        out = {key: a[:nc] for key, a in out.items()}
+        out.update(slot_state=None if ss is None else ss[:nc], first_cull=int(fc[0]), ncull=rc)
+        return out
+
+    def keyframe_culling_batch_async(self, ncand, cand_row, nkf_rows, cap, kps_kf, counts_kf, kf_mp, depth, th_depth, nmp, nobs, obs_off, obs_row,
+                                     obs_slot, obs_flags, mp_valid, mp_nobs, erased, th_obs, redundant_th, n_mps, n_redundant, cull,
+                                     slot_state=None, first_cull=None):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_keyframe_culling_batch_async)."""
+        return _chk(self.L.orbm_keyframe_culling_batch_async(self.h, ncand, cand_row, nkf_rows, cap, kps_kf, counts_kf, kf_mp, depth, float(th_depth),
+                                                             nmp, nobs, obs_off, obs_row, obs_slot, obs_flags, mp_valid, mp_nobs, erased, int(th_obs),
+                                                             float(redundant_th), n_mps, n_redundant, cull, slot_state, first_cull),
+                    "orbm_keyframe_culling_batch_async")
+
     def is_in_frustum_batch(self, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, q_shared, K, bounds, bf, viewing_cos_limit,
                             log_scale_factor, n_levels, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view=None):
         """Frame::isInFrustum for every frame of a batch in one launch, enqueue only: every array argument is a device pointer except K =
@@ -1113,6 +1155,8 @@ def _install_search():
     ORBmatcher.BowVectorBatchAsync = bow_vector_batch_async
     ORBmatcher.KfdbQuery = kfdb_query
     ORBmatcher.KfdbQueryBatchAsync = kfdb_query_batch_async
+    ORBmatcher.KeyframeCulling = keyframe_culling
+    ORBmatcher.KeyframeCullingBatchAsync = keyframe_culling_batch_async
     ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
     ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
     ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
@@ -1204,6 +1248,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_distinctive_descriptors", "orbm_distinctive_descriptors_batch_async",
             "orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async",
             "orbm_bow_vector_batch_async", "orbm_kfdb_query", "orbm_kfdb_query_batch_async",
+            "orbm_keyframe_culling", "orbm_keyframe_culling_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

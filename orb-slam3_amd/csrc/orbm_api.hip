@@ -2919,4 +2919,93 @@ int orbm_kfdb_query(orbm_t* m, int nq, const int32_t* q_row, int nq_rows, int q_
     return ORBM_OK;
 }
 
+// ---- KeyFrameCulling: LocalMapping::KeyFrameCulling's redundancy counts over the pool and the CSR of the MapPoint refresh ----
+// the argument tests the host and the device form share; fills the observation block of the kernel
+static int kfcull_args(const char* who, orbm_t* m, int ncand, const int32_t* cand_row, int nkf_rows, int cap, const orbm_kp_t* kps_kf,
+                       const int32_t* counts_kf, const int32_t* kf_mp, int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row,
+                       const int32_t* obs_slot, const uint8_t* obs_flags, const uint8_t* mp_valid, const int32_t* mp_nobs, int th_obs,
+                       int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, MpObs& O) {
+    if (!m) {                                                                // no handle: orbm_create has refused, for want of a device or of a call
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_merr("%s: no HIP device: the MI355X matcher has no CPU fallback", who); return ORBM_E_HIP; }
+        set_merr("%s: the handle is NULL", who);
+        return ORBM_E_INVALID;
+    }
+    const struct { const void* p; const char* name; } req[] = {
+        {cand_row, "cand_row"}, {kps_kf, "kps_kf"}, {counts_kf, "counts_kf"}, {kf_mp, "kf_mp"}, {obs_off, "obs_off"}, {obs_row, "obs_row"},
+        {obs_slot, "obs_slot"}, {obs_flags, "obs_flags"}, {mp_nobs, "mp_nobs"}, {n_mps, "n_mps"}, {n_redundant, "n_redundant"}, {cull, "cull"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (ncand < 1) { set_merr("%s: ncand %d must be >= 1", who, ncand); return ORBM_E_INVALID; }
+    if (th_obs < 0) { set_merr("%s: th_obs %d must be >= 0", who, th_obs); return ORBM_E_INVALID; }
+    if (nmp < 1 || nkf_rows < 1 || cap < 1 || nobs < 0) { set_merr("%s: nmp, nkf_rows and cap must be >= 1 and nobs >= 0", who); return ORBM_E_INVALID; }
+    if (ncand > ORBM_KFCULL_MAX_CAND) { set_merr("%s: %d candidates in one call (at most %d)", who, ncand, (int)ORBM_KFCULL_MAX_CAND); return ORBM_E_CAPACITY; }
+    if (cap > ORBM_KFCULL_MAX_CAP) { set_merr("%s: cap %d above %d", who, cap, (int)ORBM_KFCULL_MAX_CAP); return ORBM_E_CAPACITY; }
+    return mp_obs_args(who, nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, mp_valid, O);
+}
+
+int orbm_keyframe_culling_batch_async(orbm_t* m, int ncand, const int32_t* cand_row, int nkf_rows, int cap, const orbm_kp_t* kps_kf,
+                                      const int32_t* counts_kf, const int32_t* kf_mp, const float* depth, float th_depth, int nmp, int nobs,
+                                      const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot, const uint8_t* obs_flags,
+                                      const uint8_t* mp_valid, const int32_t* mp_nobs, const uint8_t* erased, int th_obs, float redundant_th,
+                                      int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, uint8_t* slot_state, int32_t* first_cull) {
+    MpObs O;
+    const int rc = kfcull_args("KeyFrameCulling batch", m, ncand, cand_row, nkf_rows, cap, kps_kf, counts_kf, kf_mp, nmp, nobs, obs_off, obs_row,
+                               obs_slot, obs_flags, mp_valid, mp_nobs, th_obs, n_mps, n_redundant, cull, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const KfcullParams P{ncand, th_obs, th_depth, cand_row, (const KpIn*)kps_kf, counts_kf, kf_mp, depth, mp_nobs, erased};
+    // the two count rows start from zero inside the enqueued work: a replayed graph replays the memsets
+    MHIPCHK(hipMemsetAsync(n_mps, 0, sizeof(int32_t) * ncand, m->stream));
+    MHIPCHK(hipMemsetAsync(n_redundant, 0, sizeof(int32_t) * ncand, m->stream));
+    hipLaunchKernelGGL(k_kfcull, dim3((cap + 15) / 16, ncand), dim3(256), 0, m->stream, P, O, n_mps, n_redundant, slot_state);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_kfcull_finish, dim3(1), dim3(1024), 0, m->stream, ncand, n_mps, n_redundant, redundant_th, cull, first_cull);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_keyframe_culling(orbm_t* m, int ncand, const int32_t* cand_row, int nkf_rows, int cap, const orbm_kp_t* kps_kf,
+                          const int32_t* counts_kf, const int32_t* kf_mp, const float* depth, float th_depth, int nmp, int nobs,
+                          const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot, const uint8_t* obs_flags,
+                          const uint8_t* mp_valid, const int32_t* mp_nobs, const uint8_t* erased, int th_obs, float redundant_th,
+                          int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, uint8_t* slot_state, int32_t* first_cull) {
+    MpObs O;
+    int rc = kfcull_args("KeyFrameCulling", m, ncand, cand_row, nkf_rows, cap, kps_kf, counts_kf, kf_mp, nmp, nobs, obs_off, obs_row, obs_slot,
+                         obs_flags, mp_valid, mp_nobs, th_obs, n_mps, n_redundant, cull, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t ne = (size_t)std::max(nobs, 1), nslots = (size_t)nkf_rows * cap, ncs = (size_t)ncand * cap;
+    DevBuf dcr, dk, dc, dkm, dd, doff, drow, dslot, dfl, dv, dno, de, dcnt, dcu, dss;
+    arena_reset(m);
+    UP(dcr, cand_row, sizeof(int32_t) * ncand); UP(dk, kps_kf, sizeof(KpIn) * nslots); UP(dc, counts_kf, sizeof(int32_t) * nkf_rows);
+    UP(dkm, kf_mp, sizeof(int32_t) * ncs);
+    if (depth) UP(dd, depth, sizeof(float) * ncs);
+    UP(doff, obs_off, sizeof(int32_t) * ((size_t)nmp + 1));
+    UP(drow, obs_row, sizeof(int32_t) * ne * (nobs > 0)); UP(dslot, obs_slot, sizeof(int32_t) * ne * (nobs > 0)); UP(dfl, obs_flags, ne * (nobs > 0));
+    if (mp_valid) UP(dv, mp_valid, nmp);
+    UP(dno, mp_nobs, sizeof(int32_t) * nmp);
+    if (erased) UP(de, erased, nkf_rows);
+    AL(dcnt, sizeof(int32_t) * (2 * (size_t)ncand + 1)); AL(dcu, ncand);
+    if (slot_state) AL(dss, ncs);
+    ARENA_FLUSH(m);
+    int32_t* cnt = dcnt.as<int32_t>();
+    rc = orbm_keyframe_culling_batch_async(m, ncand, dcr.as<int32_t>(), nkf_rows, cap, (const orbm_kp_t*)dk.as<KpIn>(), dc.as<int32_t>(), dkm.as<int32_t>(),
+                                           depth ? dd.as<float>() : nullptr, th_depth, nmp, nobs, doff.as<int32_t>(), drow.as<int32_t>(),
+                                           dslot.as<int32_t>(), dfl.as<uint8_t>(), mp_valid ? dv.as<uint8_t>() : nullptr, dno.as<int32_t>(),
+                                           erased ? de.as<uint8_t>() : nullptr, th_obs, redundant_th, cnt, cnt + ncand, dcu.as<uint8_t>(),
+                                           slot_state ? dss.as<uint8_t>() : nullptr, cnt + 2 * (size_t)ncand);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    const int32_t* hc = (const int32_t*)dcnt.host();
+    memcpy(n_mps, hc, sizeof(int32_t) * ncand); memcpy(n_redundant, hc + ncand, sizeof(int32_t) * ncand);
+    memcpy(cull, dcu.host(), ncand);
+    if (slot_state) memcpy(slot_state, dss.host(), ncs);
+    if (first_cull) *first_cull = hc[2 * (size_t)ncand];
+    int n = 0;
+    for (int k = 0; k < ncand; ++k) n += cull[k] ? 1 : 0;
+    return n;
+}
+
 }  // extern "C"

@@ -4808,4 +4808,137 @@ __global__ __launch_bounds__(256) void k_gather_rows(const int* __restrict__ idx
     odist[i] = dist[(size_t)q * cap + k];
 }
 
+// ------------------------------------------------------------------------------------------------
+// KeyFrameCulling: LocalMapping::KeyFrameCulling's redundancy counts (LocalMapping.cc:1218-1400) for every candidate KeyFrame of a call,
+// over the KeyFrame pool and the observation CSR of the MapPoint refresh (MpObs, mp_obs_range, mp_obs_slot: the same skip rules).
+// k_kfcull, grid = (ceil(cap / 16), ncand), 256 threads:
+//   Work split.  The unit is one (candidate, slot) item with a ragged entry list; per entry the work is one 4-byte octave out of a
+//   28-byte keypoint at a scattered pool address (a pool of 100 rows x 1000 slots is 2.8 MB: it stays in one XCD's 4 MiB L2).  One
+//   thread per slot would walk lists of 3..30 entries in divergent loops with one gather in flight per lane.  Instead a group of 16
+//   lanes takes a slot -- four slots per wave, sixteen per workgroup -- and walks the list 16 entries at a time: the typical list is
+//   one or two rounds, every round is 16 independent gathers, and the group's sums are popcounts of wave ballots masked to the group
+//   (no shuffles, no LDS).  A list of more than 64 entries is left out of the group rounds and taken afterwards by the WHOLE wave, 64
+//   entries a round, so the longest legal list (65535) costs its own wave 1024 rounds and the other three waves of the workgroup
+//   nothing.  16 rather than 8 lanes: at a mean of 8 entries half of the lists are longer than 8 and would need a second round.
+//   Early exit.  With erased == NULL nobs_eff is mp_nobs[j]: a slot with mp_nobs <= th_obs is not walked at all and a walk stops after
+//   the round in which its count passed th_obs (the reference's break, :1335; counts only grow, so the answer is the same).  With an
+//   erased row every list is walked to its end, because nobs_eff needs all of it.
+//   Pairs.  A right entry that passes re-reads its predecessor: when that is a live left entry of the same row which passes too, the
+//   KeyFrame was counted there (the scaleLeveli minimum of :1316-1328).  No state crosses a round.
+//   Counts.  Per workgroup two LDS counters take the wave ballots' popcounts, then one integer atomicAdd each into n_mps[k] /
+//   n_redundant[k], rows that a memset in the same stream has zeroed: exact, and the same on every replay.
+// k_kfcull_finish, one workgroup behind it in the stream: cull[k] = (float)n_redundant > redundant_th * (float)n_mps (one float
+// multiply, one compare, :1349) and first_cull by a minimum over the workgroup, with plain stores: nothing to reset between replays.
+// Nothing reads out of bounds whatever cand_row, kf_mp and the CSR hold.
+// ------------------------------------------------------------------------------------------------
+struct KfcullParams {
+    int ncand, th_obs;
+    float th_depth;
+    const int* cand_row; const KpIn* kps_kf; const int* counts_kf; const int* kf_mp; const float* depth; const int* mp_nobs; const uint8_t* erased;
+};
+
+// entry a of the CSR against candidate row r at level L: er = a live entry of an erased row (w = its weight in nObs), ps = it adds one
+// to the count of observing KeyFrames
+__device__ __forceinline__ void kfc_entry(const KfcullParams& P, const MpObs& O, int r, int L, int a, bool first, bool& er, int& w, bool& ps) {
+    er = false; ps = false; w = 0;
+    const long long p = mp_obs_slot(O, P.counts_kf, a);
+    if (p < 0) return;                                                      // skipped: neither erased nor observing
+    const int row = O.row[a];
+    const unsigned fl = O.flags[a];
+    if (P.erased && P.erased[row]) { er = true; w = (fl & 4) ? 2 : 1; return; }
+    if (row == r) return;                                                   // pKFi == pKF (:1312)
+    const long long top = (long long)L + 1;
+    if ((long long)P.kps_kf[p].octave > top) return;
+    ps = true;
+    if ((fl & 1) && !first && O.row[a - 1] == row && !(O.flags[a - 1] & 1)) {   // the right entry of a pair: counted at the left entry if that passes
+        const long long q = mp_obs_slot(O, P.counts_kf, a - 1);
+        if (q >= 0 && (long long)P.kps_kf[q].octave <= top) ps = false;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_kfcull(KfcullParams P, MpObs O, int* __restrict__ n_mps, int* __restrict__ n_redundant,
+                                                uint8_t* __restrict__ slot_state) {
+    __shared__ int sCnt[2];
+    const int k = blockIdx.y, lane = threadIdx.x & 63, l = lane & 15;
+    const int i = blockIdx.x * 16 + (threadIdx.x >> 4);                     // the group's slot
+    const u64 gm = 0xFFFFull << (lane & 48);                                // the group's lanes in a wave ballot
+    if (threadIdx.x < 2) sCnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int r = P.cand_row[k];
+    const bool full = P.erased != nullptr;
+    int n = 0;
+    if ((unsigned)r < (unsigned)O.nkf_rows && !(full && P.erased[r])) n = min(P.counts_kf[r], O.cap);
+    bool counted = false;
+    long long nobs = 0;
+    int L = 0, o0 = 0, E = 0;
+    if (i < n) {
+        const size_t at = (size_t)k * O.cap + i;
+        const int j = P.kf_mp[at];
+        if ((unsigned)j < (unsigned)O.nmp && !(O.valid && !O.valid[j])) {
+            bool inDepth = true;
+            if (P.depth) { const float d = P.depth[at]; inDepth = !(d > P.th_depth || d < 0); }   // :1295 as written: NaN and -0.0 pass
+            if (inDepth) {
+                counted = true;
+                nobs = P.mp_nobs[j];
+                E = mp_obs_range(O, j, o0);
+                L = P.kps_kf[(size_t)r * O.cap + i].octave;
+            }
+        }
+    }
+    const bool walk = counted && E > 0 && (full || nobs > P.th_obs);
+    int cnt = 0, wsum = 0;
+    bool anyE = false;
+    // lists of at most 64 entries: the group's 16 lanes, 16 entries a round
+    const int Es = (walk && E <= 64) ? E : 0;
+    for (int base = 0; __any(base < Es && (full || cnt <= P.th_obs)); base += 16) {
+        bool er = false, ps = false;
+        int w = 0;
+        const int e = base + l;
+        if (e < Es && (full || cnt <= P.th_obs)) kfc_entry(P, O, r, L, o0 + e, e == 0, er, w, ps);
+        const u64 bp = __ballot(ps) & gm, be = __ballot(er) & gm, b2 = __ballot(er && w == 2) & gm;
+        cnt += __popcll(bp); wsum += __popcll(be) + __popcll(b2); anyE |= be != 0;
+    }
+    // longer lists: the whole wave, 64 entries a round, one list after the other
+    for (u64 m = __ballot(walk && E > 64 && l == 0); m; m &= m - 1) {
+        const int src = __ffsll((long long)m) - 1;                           // the first lane of the list's group
+        const int o0w = __shfl(o0, src), Ew = __shfl(E, src), Lw = __shfl(L, src);
+        int c = 0, ws = 0;
+        bool ae = false;
+        for (int base = 0; base < Ew && (full || c <= P.th_obs); base += 64) {
+            bool er = false, ps = false;
+            int w = 0;
+            const int e = base + lane;
+            if (e < Ew) kfc_entry(P, O, r, Lw, o0w + e, e == 0, er, w, ps);
+            const u64 be = __ballot(er);
+            c += __popcll(__ballot(ps)); ws += __popcll(be) + __popcll(__ballot(er && w == 2)); ae |= be != 0;
+        }
+        if ((lane & 48) == src) { cnt = c; wsum = ws; anyE = ae; }
+    }
+    const long long eff = nobs - wsum;                                       // nObs after every erase; it only falls (MapPoint.cc:231-250)
+    if (anyE && eff <= 2) counted = false;                                  // bad by erasure: gone from this KeyFrame too (:280-305)
+    const bool red = counted && eff > P.th_obs && cnt > P.th_obs;
+    if (slot_state && l == 0 && i < O.cap) slot_state[(size_t)k * O.cap + i] = counted ? (red ? 2 : 1) : 0;
+    const int nc = __popcll(__ballot(counted && l == 0)), nr = __popcll(__ballot(red && l == 0));
+    if (lane == 0) { if (nc) atomicAdd(&sCnt[0], nc); if (nr) atomicAdd(&sCnt[1], nr); }
+    __syncthreads();
+    if (threadIdx.x == 0) { if (sCnt[0]) atomicAdd(&n_mps[k], sCnt[0]); if (sCnt[1]) atomicAdd(&n_redundant[k], sCnt[1]); }
+}
+
+__global__ __launch_bounds__(1024) void k_kfcull_finish(int ncand, const int* __restrict__ n_mps, const int* __restrict__ n_redundant, float redundant_th,
+                                                        uint8_t* __restrict__ cull, int* __restrict__ first_cull) {
+    __shared__ int sFirst;
+    if (threadIdx.x == 0) sFirst = INT_MAX;
+    __syncthreads();
+    int mine = INT_MAX;
+    for (int k = threadIdx.x; k < ncand; k += 1024) {
+        const float bound = redundant_th * (float)n_mps[k];                 // -ffp-contract=off: one multiply, then one compare
+        const bool c = (float)n_redundant[k] > bound;
+        cull[k] = c ? 1 : 0;
+        if (c) mine = min(mine, k);
+    }
+    if (mine != INT_MAX) atomicMin(&sFirst, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && first_cull) *first_cull = sFirst == INT_MAX ? -1 : sFirst;
+}
+
 }  // namespace orbmk
