@@ -62,6 +62,7 @@ struct orbx {
 #ifdef ORBX_AB
     bool rzV2p = false;                                       // ORBX_RESIZE_V2P: A/B, k_resize2p (8-row tasks of one frame) instead of k_resize2
     RzTaskP* dRzTasksP = nullptr; size_t capRzTasksP = 0;
+    bool blurV3p = false;                                     // ORBX_BLUR_V3P: A/B, k_blur3p (pass 2 started from the constant, rows clamped in every tile) instead of k_blur3
 #endif
     bool qtV1 = false, odV1 = false, serial = false, blurV2 = false, blurEarly = true;
     int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
@@ -397,6 +398,7 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
 #ifdef ORBX_AB
     cfg.rzNoPack = ab_env("ORBX_RESIZE_NOPACK") != nullptr;
     o->rzV2p = ab_env("ORBX_RESIZE_V2P") != nullptr;
+    o->blurV3p = ab_env("ORBX_BLUR_V3P") != nullptr;
 #endif
     if (const char* e = ab_env("ORBX_QT_WIDE")) cfg.qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
@@ -646,6 +648,12 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
         const bool walk = blur_walks(o->plan, nimg, o->blurWalkForce);
         o->blurFormLast = walk ? 1 : 0;
         const size_t first = walk ? 0 : o->plan.nTiles3Walk, count = walk ? o->plan.nTiles3Walk : o->plan.tiles3.size() - o->plan.nTiles3Walk;
+#ifdef ORBX_AB
+        if (o->blurV3p)
+            hipLaunchKernelGGL(k_blur3p, dim3((unsigned)count, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
+                               o->dTiles3 + first, (const uint4*)o->dB3Th, (const uint4*)o->dB3Tv);
+        else
+#endif
         hipLaunchKernelGGL(k_blur3, dim3((unsigned)count, nimg), dim3(256), 0, s1, g, o->dL0Ptr, l0pitch, o->dPyr, o->dBlur,
                            o->dTiles3 + first, (const uint4*)o->dB3Th, (const uint4*)o->dB3Tv);
     }

@@ -2171,9 +2171,186 @@ typedef int b3_i32x16 __attribute__((ext_vector_type(16)));
 
 #define B3_OROW 144                                        // output staging row stride (128 B + 16 B pad)
 #define B3_LROW 176                                        // LDS row stride: 160 B of pixels + 16 B pad (b128 reads conflict-free)
-__global__ __launch_bounds__(256) void k_blur3(Geom g, const u8* const* l0, int l0pitch, const u8* pyr, u8* blr,
+// + 0x81 to each byte of a dword, modulo 256 and without a carry between bytes: the low seven bits take the + 1, bit 7 is flipped
+// unless that carried into it
+__device__ __forceinline__ u32 b3_add81(u32 x) {
+    return __builtin_amdgcn_bitop3_b32((x & 0x7f7f7f7fu) + 0x01010101u, x, 0x80808080u, 0xD2);   // a ^ (~b & c)
+}
+
+// At most 3 waves per SIMD (the registers would allow 6, the LDS 8): the kernel runs beside FAST, which the step waits for, and is
+// memory-bound alone at any of these occupancies.  Measured per 1024 frames, step / k_blur3 beside FAST: 2 waves 3.14 ms / 1.59 ms,
+// 3 waves 3.03 / 1.09, 4 waves 3.05 / 0.93, 5 waves 3.07 / -, 6 waves 3.13 / 0.71 (profiles/NOTES.md): the more of it is resident, the
+// more it takes from the level-0 and middle FAST launches, and below 3 it outlasts them.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 3))) void k_blur3(Geom g, const u8* const* l0, int l0pitch, const u8* pyr, u8* blr,
                                                const Blur3Task* __restrict__ tasks,
                                                const uint4* __restrict__ thTab, const uint4* __restrict__ tvTab) {
+#if __HIP_DEVICE_COMPILE__
+    __shared__ __attribute__((aligned(16))) u8 xs[2][32 * B3_LROW];
+    __shared__ __attribute__((aligned(16))) u8 ob[2][32 * B3_OROW];   // blurred tile of the workgroup, 32 rows x 128 px, every byte 0x81 short (below)
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int cb = __builtin_amdgcn_readfirstlane(tid >> 6);            // this wave's 32-px column block of the 128-px group
+    Blur3Task t = tasks[B3_XCD ? xcd_task(blockIdx.x, gridDim.x) : blockIdx.x];   // one task per workgroup: (level, 128-px group, tile chunk)
+    t.level = (short)__builtin_amdgcn_readfirstlane(t.level);
+    t.x0 = (short)__builtin_amdgcn_readfirstlane(t.x0);
+    t.t0 = (short)__builtin_amdgcn_readfirstlane(t.t0);
+    t.nt = (short)__builtin_amdgcn_readfirstlane(t.nt);
+    t.th = __builtin_amdgcn_readfirstlane(t.th);
+    t.tv = __builtin_amdgcn_readfirstlane(t.tv);
+    const int frame = blockIdx.y;
+    const LevelDesc& L = g.lv[t.level];
+    int sp;
+    const u8* im = level_ptr(g, l0, l0pitch, pyr, frame, t.level, &sp);
+    u8* dst = blr + (size_t)frame * g.blrFrameBytes + L.boff;
+    const int w = L.w, h = L.h, dp = L.pitch, btpr = L.btpr, xg = t.x0, x0 = xg + 32 * cb;
+    const bool live = x0 < w;                                           // wave-uniform: a block past the right edge only helps loading
+    const int r = lane & 31, hh = lane >> 5;
+    b3_i32x4 th[2];
+    {
+        const int e = live ? t.th + cb : t.th;
+        const uint4 u0 = thTab[(size_t)e * 128 + lane], u1 = thTab[(size_t)e * 128 + 64 + lane];
+        th[0][0] = (int)u0.x; th[0][1] = (int)u0.y; th[0][2] = (int)u0.z; th[0][3] = (int)u0.w;
+        th[1][0] = (int)u1.x; th[1][1] = (int)u1.y; th[1][2] = (int)u1.z; th[1][3] = (int)u1.w;
+    }
+    // staging: 32 source rows x 160 B (pixels xg - 16 .. xg + 143) per tile = 320 16-byte pieces; thread -> piece tid and
+    // piece min(256 + tid, 319) (only the first 64 threads park the second one).  Every load is unconditional on a clamped
+    // row / column -- a piece outside the image only ever meets zero weights, so any real pixels will do -- which keeps
+    // the loads themselves (and the compiler's conservative vmcnt waits) out of branches.
+    const int it1 = min(256 + tid, 319);
+    const int pr0 = tid / 10, ps0 = tid - pr0 * 10, pr1 = it1 / 10, ps1 = it1 - pr1 * 10;
+    const int px0 = xg - 16 + 16 * ps0, px1 = xg - 16 + 16 * ps1;
+    const int pxc0 = (px0 >= 0 && px0 < sp) ? px0 : 0, pxc1 = (px1 >= 0 && px1 < sp) ? px1 : 0;
+    const int ldsW0 = pr0 * B3_LROW + 16 * ps0, ldsW1 = pr1 * B3_LROW + 16 * ps1;
+    const int ldsR = r * B3_LROW + 32 * cb + 16 * hh;
+    // A tile's 32 source rows start at sb = 26 tile - 3.  Only a tile with sb < 0 or sb + 32 > h (the first of a level, and the last
+    // one or two) has rows to clamp, and that is known to the whole wave: every other tile takes the two piece offsets of the
+    // tile before it plus 26 rows.  (The first fetch of a task and the tile after a level's first start the offsets afresh.)
+    int sb = t.t0 * B3_ROWS - 3;
+    u32 fo0 = 0, fo1 = 0;
+    const u32 fstep = (u32)(B3_ROWS * sp);
+    u32 tvo = (u32)(t.tv * 1024 + lane * 16);
+    uint4 n0, n1;
+    auto fetch = [&](const bool first) __attribute__((always_inline)) {
+        if (first || sb < B3_ROWS || sb + 32 > h) {
+            fo0 = (u32)(__mul24(min(max(sb + pr0, 0), h - 1), sp) + pxc0);
+            fo1 = (u32)(__mul24(min(max(sb + pr1, 0), h - 1), sp) + pxc1);
+        } else {
+            fo0 += fstep; fo1 += fstep;
+        }
+        n0 = gload128u(im, fo0);
+        n1 = gload128u(im, fo1);
+        sb += B3_ROWS;
+        asm volatile("" : "+s"(sb));                                    // (no induction variables derived from it: they cost registers)
+    };
+    auto park = [&](const int buf) __attribute__((always_inline)) {
+        const u32 m = 0x80808080u;
+        *(uint4*)(xs[buf] + ldsW0) = make_uint4(n0.x ^ m, n0.y ^ m, n0.z ^ m, n0.w ^ m);
+        if (tid < 64) *(uint4*)(xs[buf] + ldsW1) = make_uint4(n1.x ^ m, n1.y ^ m, n1.z ^ m, n1.w ^ m);
+    };
+    // memory operations retire in order and the compiler cannot count this kernel's predicated stores: per tile the order is
+    // [next Tv, next pixels] ... park (waits for both, nothing younger outstanding) ... stores, so the only wait of the loop
+    // is the one before parking and it never includes a store of the same tile
+    uint4 tvA = gload128u(tvTab, tvo), tvB = tvA;                       // Tv of the even / odd tiles of the walk (below)
+    fetch(true);
+    park(0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);                                 // vmcnt(0): Th and Tv have landed too, the tiles start with nothing outstanding
+    __syncthreads();
+    // write-out: the workgroup's 26 x 128 px tile leaves as 16-byte pieces, 8 per row: full 128-byte lines per row
+    // (tiled output: 8 consecutive lanes take 8 consecutive rows of one 16-byte column = one tile's line when the rows are aligned)
+    const bool tiledOut = g.blurTiled != 0;
+    const int orow = tiledOut ? (tid & 7) + 8 * (tid >> 6) : tid >> 3, oseg = tiledOut ? (tid >> 3) & 7 : tid & 7;
+    const bool ocol = xg + 16 * oseg < w && orow < B3_ROWS;
+    const int obR = orow * B3_OROW + 16 * oseg;
+    // Tiled output (g.blurTiled): the blurred level is only ever read back as 37-row x 40-byte patches around keypoints
+    // (k_orient_desc2), and that gather is bound by the number of 128-byte lines it touches: as 16 x 8-px tiles of one line each
+    // a patch covers ~21 lines instead of ~48.  Piece (row y, 16-byte column c) lives at ((y >> 3) * btpr + c) * 128 + (y & 7) * 16;
+    // the 8 rows x 8 pieces a wave stores are still whole or half lines (L2 merges the halves of a tile written by two steps).
+    const bool tiled = tiledOut;
+    int y16 = (t.t0 * B3_ROWS + orow) * 16;                             // 16 x this thread's output row: (y >> 3) and (y & 7) << 4 are a shift and a mask of it
+    const int h16 = h * 16;                                             // y16 < h16: the row is inside the image
+    const int tcol = (xg >> 4) + oseg;
+    const int scol = xg + 16 * oseg;
+    // One tile is compute(), then finish().  buf is a constant at every call site, so the LDS addresses of a tile are a register plus
+    // an immediate.  tvq holds the tile's Tv fragment while prefetch() loads the next one's into the other register set: the walk
+    // below swaps the two sets from tile to tile, which takes the place of a copy (the set being loaded is still an MFMA operand).
+    auto prefetch = [&](uint4& tvn) __attribute__((always_inline)) {    // in flight while this tile is computed
+        tvo += 1024u;
+        tvn = gload128u(tvTab, tvo);
+        fetch(false);
+    };
+    auto compute = [&](const int buf, const uint4& tvq) __attribute__((always_inline)) {
+        if (live) {
+            const uint4 a0 = *(const uint4*)(xs[buf] + ldsR);
+            const uint4 a1 = *(const uint4*)(xs[buf] + ldsR + 32);
+            b3_i32x4 A0, A1;
+            A0[0] = (int)a0.x; A0[1] = (int)a0.y; A0[2] = (int)a0.z; A0[3] = (int)a0.w;
+            A1[0] = (int)a1.x; A1[1] = (int)a1.y; A1[2] = (int)a1.z; A1[3] = (int)a1.w;
+            b3_i32x16 acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A0, th[0], (b3_i32x16)(0), 0, 0, 0);   // H - 32768: signed 16-bit
+            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(A1, th[1], acc, 0, 0, 0);
+            // ---- H - 32768 (signed 16-bit, one column per lane, 16 rows in the registers) -> low / high byte fragments: the
+            // high byte is a signed int8 as it stands, the low byte becomes one by - 128
+            b3_i32x4 blo, bhi;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const u32 p01 = __builtin_amdgcn_perm((u32)acc[4 * e + 1], (u32)acc[4 * e], 0x05010400u);       // r0.b0 r1.b0 r0.b1 r1.b1
+                const u32 p23 = __builtin_amdgcn_perm((u32)acc[4 * e + 3], (u32)acc[4 * e + 2], 0x05010400u);
+                blo[e] = (int)(__builtin_amdgcn_perm(p23, p01, 0x05040100u) ^ 0x80808080u);
+                bhi[e] = (int)__builtin_amdgcn_perm(p23, p01, 0x07060302u);
+            }
+            b3_i32x4 tv;
+            tv[0] = (int)tvq.x; tv[1] = (int)tvq.y; tv[2] = (int)tvq.z; tv[3] = (int)tvq.w;
+            // Both products start from the inline zero.  What they leave out is the offsets of both passes and the rounding,
+            // 256 * 32768 + 32768 + 32768 = 0x810000: its low 16 bits are zero, so bits 16..23 of (aH << 8) + aL are the blurred byte
+            // minus 0x81 modulo 256, for every input.  b3_add81 puts it back where ob is read (finish(): the one place).  As the
+            // start value of aL it was 16 registers, copied in front of the MFMA in every tile: the destination is tied to C.
+            const b3_i32x16 aH = __builtin_amdgcn_mfma_i32_32x32x32_i8(tv, bhi, (b3_i32x16)(0), 0, 0, 0);
+            const b3_i32x16 aL = __builtin_amdgcn_mfma_i32_32x32x32_i8(tv, blo, (b3_i32x16)(0), 0, 0, 0);
+            // ---- lane = column x0 + r, register i = output row (i&3) + 8 (i>>2) + 4 hh of the tile, value in bits 16..23: one LDS
+            // byte write each into the workgroup's output tile (double-buffered; the barrier below is the loop's only one), which
+            // then leaves as full 128-byte rows.  (Global byte stores crawl at a lane per clock, dword stores straight from this
+            // layout write 32-byte runs: 0.55 ms; a 4x4 byte transpose across lane quads -- 3 v_perm + 2 DPP moves + 2 v_perm per
+            // four rows -- ahead of dword LDS writes costs 28 VALU per tile more than these 16 LDS writes and the pass is
+            // VALU-bound.)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const u32 R = (u32)((aH[i] << 8) + aL[i]);
+                ob[buf][((i & 3) + 8 * (i >> 2) + 4 * hh) * B3_OROW + 32 * cb + r] = (u8)(R >> 16);   // ds_write_b8_d16_hi
+            }
+        }
+    };
+    auto finish = [&](const int buf) __attribute__((always_inline)) {
+        // LDS-only barrier: __syncthreads() would also drain vmcnt, i.e. wait for the stores and the prefetch
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        if (ocol && y16 < h16) {
+            const uint4 v = *(const uint4*)(ob[buf] + obR);
+            const u32 sa = tiled ? (u32)((__mul24(y16 >> 7, btpr) + tcol) << 7) | (u32)(y16 & 0x70) : (u32)(__mul24(y16 >> 4, dp) + scol);
+            *(__attribute__((address_space(1))) uint4*)((__attribute__((address_space(1))) u8*)dst + sa) =
+                make_uint4(b3_add81(v.x), b3_add81(v.y), b3_add81(v.z), b3_add81(v.w));
+        }
+        y16 += 16 * B3_ROWS;
+        asm volatile("" : "+v"(y16));                                   // (likewise: one running row, not one per address form)
+    };
+    // The loop takes the tiles that have a successor two at a time and has no other way out, and the last one or two tiles follow
+    // it: a tile is then reached only through park(), whose wait covers the Tv fragment as well (requested before the pixels), so
+    // no tile waits for memory anywhere else.  The next tile's pixels go to LDS before this tile's stores are issued: the wait for
+    // them then never includes a store.
+    int k = 0;
+    for (; k + 2 < t.nt; k += 2) {
+        prefetch(tvB); compute(0, tvA); park(1); finish(0);
+        prefetch(tvA); compute(1, tvB); park(0); finish(1);
+    }
+    if (t.nt - k == 2) {
+        prefetch(tvB); compute(0, tvA); park(1); finish(0);
+        compute(1, tvB); finish(1);
+    } else if (t.nt - k == 1) {
+        compute(0, tvA); finish(0);
+    }
+#endif
+}
+
+#ifdef ORBX_AB   /* k_blur3p: A/B reference (pass 2 started from the constant, Tv copied, rows clamped in every tile), not in the product library */
+__global__ __launch_bounds__(256) void k_blur3p(Geom g, const u8* const* l0, int l0pitch, const u8* pyr, u8* blr,
+                                                const Blur3Task* __restrict__ tasks,
+                                                const uint4* __restrict__ thTab, const uint4* __restrict__ tvTab) {
 #if __HIP_DEVICE_COMPILE__
     __shared__ __attribute__((aligned(16))) u8 xs[2][32 * B3_LROW];
     __shared__ __attribute__((aligned(16))) u8 ob[2][32 * B3_OROW];   // blurred tile of the workgroup, 32 rows x 128 px
@@ -2308,6 +2485,7 @@ __global__ __launch_bounds__(256) void k_blur3(Geom g, const u8* const* l0, int 
     }
 #endif
 }
+#endif  /* ORBX_AB */
 
 // (BL_R, BlurTask, BlurSel: orbx_plan.h)
 
