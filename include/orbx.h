@@ -109,6 +109,11 @@ int orbx_blur_in_pass(const orbx_t*);
 /* workgroup size the quadtree of the most recent batch was enqueued with: 1024 or 256 (k_quadtree2 takes the wide form when some
  * level wants >= 512 nodes or frames * levels <= 512), 0 for the first-generation kernel of the A/B library, -1 before any batch. */
 int orbx_quadtree_threads(const orbx_t*);
+/* k_quadtree2 refines a level on path histograms of the candidates' first subdivisions ("table mode") and falls back to passes over
+ * the candidates when a node that deep still has to be split.  Returns how many (frame, level) workgroups have fallen back since
+ * orbx_create: cumulative, never reset, read after the extractor's stream has drained; a negative ORBX_E_* on failure.  Stays 0
+ * with the A/B library's other quadtree kernels. */
+long long orbx_quadtree_fallbacks(orbx_t*);
 /* form the Gaussian blur of the most recent batch was enqueued in: 0 = k_blur3 with one 26-row tile per workgroup (small batches,
  * the single-frame call), 1 = k_blur3 walking chunks of up to 8 tiles (frames * walk tasks >= 2048), 2 = k_blur2 (the VALU kernel
  * of the A/B library), -1 before any batch. */

@@ -32,7 +32,7 @@ EXPORTS = [
     "orbx_create", "orbx_destroy", "orbx_last_error", "orbx_max_keypoints", "orbx_extract", "orbx_extract_batch",
     "orbx_extract_batch_async", "orbx_sync", "orbx_result_device", "orbx_result_fetch", "orbx_result_fetch_all", "orbx_level_size",
     "orbx_level_image", "orbx_pyramid_fetch", "orbx_pyramid_map", "orbx_scale_tables", "orbx_features_per_level", "orbx_level_candidates",
-    "orbx_level_selected", "orbx_last_timings", "orbx_set_stage_timing", "orbx_mean_timings", "orbx_stream_wait_results", "orbx_stream_wait_other", "orbx_guard_results", "orbx_gray_from_color", "orbx_remap_linear", "orbx_clahe", "orbx_algorithmic_bytes", "orbx_blur_in_pass", "orbx_quadtree_threads", "orbx_blur_form", "orbx_orient_form", "orbx_stream", "orbx_dev_alloc",
+    "orbx_level_selected", "orbx_last_timings", "orbx_set_stage_timing", "orbx_mean_timings", "orbx_stream_wait_results", "orbx_stream_wait_other", "orbx_guard_results", "orbx_gray_from_color", "orbx_remap_linear", "orbx_clahe", "orbx_algorithmic_bytes", "orbx_blur_in_pass", "orbx_quadtree_threads", "orbx_quadtree_fallbacks", "orbx_blur_form", "orbx_orient_form", "orbx_stream", "orbx_dev_alloc",
     "orbx_dev_free", "orbx_memcpy_h2d", "orbx_memcpy_d2h", "orbx_device_count",
     "orbx_capture_begin", "orbx_capture_end", "orbx_graph_launch", "orbx_result_download_async", "orbx_result_block_layout", "orbx_block_attach", "orbx_block_detach_all", "orbx_download_sync",
     "orbx_host_alloc", "orbx_host_free", "orbx_set_result_block", "orbx_mark", "orbx_mark_elapsed_ms",
@@ -82,6 +82,8 @@ def lib():
         L.orbx_algorithmic_bytes.restype = C.c_int64
         L.orbx_blur_in_pass.argtypes = [vp]
         L.orbx_quadtree_threads.argtypes = [vp]
+        L.orbx_quadtree_fallbacks.argtypes = [vp]
+        L.orbx_quadtree_fallbacks.restype = C.c_longlong
         L.orbx_blur_form.argtypes = [vp]
         L.orbx_orient_form.argtypes = [vp]
         L.orbx_algorithmic_bytes.argtypes = [vp, C.POINTER(C.c_int64)]
@@ -431,6 +433,14 @@ class ORBextractor:
     def quadtree_threads(self):
         """Workgroup size of the last batch's quadtree: 1024 / 256, 0 = the A/B library's k_quadtree (include/orbx.h)."""
         return int(self.L.orbx_quadtree_threads(self.h))
+
+    def quadtree_fallbacks(self):
+        """(frame, level) quadtrees that left table mode for passes over their candidates, cumulative since the handle was made; waits
+        for the extractor's stream (include/orbx.h: orbx_quadtree_fallbacks)."""
+        n = int(self.L.orbx_quadtree_fallbacks(self.h))
+        if n < 0:
+            raise OrbError("orbx_quadtree_fallbacks: %d %s" % (n, self.L.orbx_last_error().decode()))
+        return n
 
     def blur_form(self):
         """Form of the last batch's blur: 0 one-tile k_blur3, 1 walking k_blur3, 2 = the A/B library's k_blur2, -1 before any batch (include/orbx.h)."""

@@ -63,6 +63,8 @@ struct orbx {
     bool rzV2p = false;                                       // ORBX_RESIZE_V2P: A/B, k_resize2p (8-row tasks of one frame) instead of k_resize2
     RzTaskP* dRzTasksP = nullptr; size_t capRzTasksP = 0;
     bool blurV3p = false;                                     // ORBX_BLUR_V3P: A/B, k_blur3p (pass 2 started from the constant, rows clamped in every tile) instead of k_blur3
+    bool qtV2p = false;                                       // ORBX_QT_V2P: A/B, k_quadtree2p (candidate passes in every iteration behind the fused ones) instead of k_quadtree2
+    int qtHistDMax = 99;                                      // ORBX_QT_HISTD: A/B, caps the depth of k_quadtree2's path histograms (never below qtFuseD)
 #endif
     bool qtV1 = false, odV1 = false, serial = false, blurV2 = false, blurEarly = true;
     int qtThreadsLast = -1;                                    // orbx_quadtree_threads: the form the last batch was enqueued with
@@ -125,6 +127,7 @@ struct orbx {
     u32 *dCandCnt = nullptr, *dCandEnt = nullptr, *dSel = nullptr, *dSelCnt = nullptr;
     u16* dKpNode = nullptr;
     u32* dDense = nullptr;
+    u32* dQtFallbacks = nullptr;                               // k_quadtree2: workgroups that left table mode, cumulative (orbx_quadtree_fallbacks)
     KpOut* dKps = nullptr; u8* dDesc = nullptr; KpWork* dWork = nullptr;
     int *dN = nullptr, *dMono = nullptr, *dLap = nullptr, *dErr = nullptr;
     bool stageTiming = true;                                   // record the stage-boundary events (orbx_set_stage_timing)
@@ -263,6 +266,8 @@ static int build_geometry(orbx* o, int w, int h) {
     if (ensure(&o->dOvfList, &o->capOvfList, (size_t)g.totalCells * B)) return ORBX_E_HIP;
 #ifdef ORBX_AB
     HIPCHK(hipFuncSetAttribute((const void*)k_quadtree, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qtLds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2p<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
+    HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2p<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
 #endif
     HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<256>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
     HIPCHK(hipFuncSetAttribute((const void*)k_quadtree2<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.qt2Lds));
@@ -399,6 +404,8 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
     cfg.rzNoPack = ab_env("ORBX_RESIZE_NOPACK") != nullptr;
     o->rzV2p = ab_env("ORBX_RESIZE_V2P") != nullptr;
     o->blurV3p = ab_env("ORBX_BLUR_V3P") != nullptr;
+    o->qtV2p = ab_env("ORBX_QT_V2P") != nullptr;
+    if (const char* e = ab_env("ORBX_QT_HISTD")) o->qtHistDMax = atoi(e);
 #endif
     if (const char* e = ab_env("ORBX_QT_WIDE")) cfg.qtWideForce = atoi(e) != 0 ? 1 : 0;
     o->blurEarly = !o->blurV2 && ab_env("ORBX_BLUR_LATE") == nullptr;
@@ -425,9 +432,11 @@ int orbx_create(orbx_t** out, int nfeatures, float scale_factor, int nlevels, in
         const size_t B = max_batch;
         if (hipMalloc((void**)&o->dL0Ptr, sizeof(u8*) * B) != hipSuccess || hipMalloc((void**)&o->dSelCnt, sizeof(u32) * 12 * B) != hipSuccess ||
             hipMalloc((void**)&o->dLap, sizeof(int) * 2 * B) != hipSuccess || hipMalloc((void**)&o->dErr, sizeof(int)) != hipSuccess ||
-            hipMalloc((void**)&o->dPattern, 1024) != hipSuccess || hipMalloc((void**)&o->dOdW, sizeof(u32) * OD_WTAB) != hipSuccess || hipMalloc((void**)&o->dOvf, 2 * sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMalloc failed"); break; }
+            hipMalloc((void**)&o->dPattern, 1024) != hipSuccess || hipMalloc((void**)&o->dOdW, sizeof(u32) * OD_WTAB) != hipSuccess || hipMalloc((void**)&o->dOvf, 2 * sizeof(u32)) != hipSuccess ||
+            hipMalloc((void**)&o->dQtFallbacks, sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMalloc failed"); break; }
         if (hipMemcpy(o->dOdW, o->tab.odW.data(), sizeof(u32) * OD_WTAB, hipMemcpyHostToDevice) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
-        if (hipMemcpy(o->dPattern, kPattern, 1024, hipMemcpyHostToDevice) != hipSuccess || hipMemset(o->dErr, 0, sizeof(int)) != hipSuccess || hipMemset(o->dOvf, 0, 2 * sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
+        if (hipMemcpy(o->dPattern, kPattern, 1024, hipMemcpyHostToDevice) != hipSuccess || hipMemset(o->dErr, 0, sizeof(int)) != hipSuccess || hipMemset(o->dOvf, 0, 2 * sizeof(u32)) != hipSuccess ||
+            hipMemset(o->dQtFallbacks, 0, sizeof(u32)) != hipSuccess) { rc = ORBX_E_HIP; set_err("hipMemcpy failed"); break; }
         o->hL0Ptr.resize(B); o->hLap.resize(2 * B);
         rc = build_geometry(o, max_w, max_h);
     } while (0);
@@ -452,7 +461,7 @@ void orbx_destroy(orbx_t* o) {
     for (auto& e : o->evBatchDone) if (e) (void)hipEventDestroy(e);
     if (o->stream3) (void)hipStreamDestroy(o->stream3);
     void* ptrs[] = {o->dPyr, o->dBlur, o->dL0, (void*)o->dL0Ptr, o->dCells, o->dTiles, o->dTiles3, o->dB3Th, o->dB3Tv, o->dStrips, o->dAux, o->dF4Items, o->dX4, o->dRzTasks, o->dXt, o->dYt, o->dCandCnt, o->dCandEnt,
-                    o->dSel, o->dSelCnt, o->dKpNode, o->dDense, o->rb[0].base, o->rb[1].base, o->rb[2].base, o->rb[3].base, o->rb[4].base, o->rb[5].base, o->rb[6].base, o->rb[7].base, o->dWork, o->dLap, o->dErr, o->dPattern, o->dOvf, o->dOvfList, o->dOdW, (void*)o->dStamps};
+                    o->dSel, o->dSelCnt, o->dKpNode, o->dDense, o->rb[0].base, o->rb[1].base, o->rb[2].base, o->rb[3].base, o->rb[4].base, o->rb[5].base, o->rb[6].base, o->rb[7].base, o->dWork, o->dLap, o->dErr, o->dPattern, o->dOvf, o->dOvfList, o->dOdW, (void*)o->dStamps, o->dQtFallbacks};
     for (void* p : ptrs) if (p) (void)hipFree(p);
 #ifdef ORBX_AB
     if (o->dRzTasksP) (void)hipFree(o->dRzTasksP);
@@ -666,12 +675,24 @@ static int extract_batch_async_impl(orbx_t* o, const uint8_t* const* imgs, int i
         Geom g2 = g; g2.nodeCap = o->plan.qt2Cap; g2.sortCap = o->plan.qt2Sort;
         const bool wide = qt_wide(o->plan, nimg, g.nlevels, o->cfg.qtWideForce);
         o->qtThreadsLast = wide ? 1024 : 256;
+        int histD = o->plan.qtHistD;
+#ifdef ORBX_AB
+        histD = std::max(o->plan.qtFuseD, std::min(histD, o->qtHistDMax));
+        if (o->qtV2p) {
+            if (wide)
+                hipLaunchKernelGGL(k_quadtree2p<1024>, dim3(nimg, g.nlevels), dim3(1024), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
+                                   o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
+            else
+                hipLaunchKernelGGL(k_quadtree2p<256>, dim3(nimg, g.nlevels), dim3(256), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
+                                   o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
+        } else
+#endif
         if (wide)
             hipLaunchKernelGGL(k_quadtree2<1024>, dim3(nimg, g.nlevels), dim3(1024), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
-                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
+                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD, histD, o->dQtFallbacks);
         else
             hipLaunchKernelGGL(k_quadtree2<256>, dim3(nimg, g.nlevels), dim3(256), o->plan.qt2Lds, st, g2, o->dCandCnt, o->dCandEnt,
-                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD);
+                               o->dDense, o->dKpNode, o->dSel, o->dSelCnt, o->dErr, o->plan.maxCells, o->plan.maxIni, o->plan.qtFuseD, histD, o->dQtFallbacks);
     }
     STAGE_EV(3, st);
     if (o->guardPending) {                                       // k_slots is the first writer of the result block (orbx_guard_results)
@@ -1311,6 +1332,14 @@ int orbx_mean_timings(orbx_t* o, float* ms8, int* nsamples) {
 
 int orbx_blur_in_pass(const orbx_t* o) { return o && o->blurEarly && !o->serial ? 1 : 0; }
 int orbx_quadtree_threads(const orbx_t* o) { return o ? o->qtThreadsLast : -1; }
+long long orbx_quadtree_fallbacks(orbx_t* o) {
+    if (!o) return ORBX_E_INVALID;
+    u32 n = 0;
+    HIPCHK(hipSetDevice(o->device));
+    HIPCHK(hipStreamSynchronize(o->stream));
+    HIPCHK(hipMemcpy(&n, o->dQtFallbacks, sizeof(u32), hipMemcpyDeviceToHost));
+    return (long long)n;
+}
 int orbx_blur_form(const orbx_t* o) { return o ? o->blurFormLast : -1; }
 int orbx_orient_form(const orbx_t* o) { return o ? o->orientFormLast : -1; }
 

@@ -3,7 +3,7 @@
 // Pipeline per batch (all kernels are launched over (work-item, frame) so a batch fills the chip):
 //   k_resize2     x(L-1)  level l-1 -> level l, OpenCV INTER_LINEAR fixed point  (ORBextractor.cc:1664-1717)   [k_resize: general fallback]
 //   k_fast3<P>    x3      per 35-px cell: FAST-9/16 score, 3x3 NMS, ini/min threshold   (:1038-1143)          [+ k_fast_fix; k_fast: A/B]
-//   k_quadtree2   x1      DistributeOctTree per (frame, level)                            (:688-1034)          [k_quadtree: A/B]
+//   k_quadtree2   x1      DistributeOctTree per (frame, level)                            (:688-1034)          [k_quadtree, k_quadtree2p: A/B]
 //   k_slots       x1      octave/size fix-up, level-0 scaling, lapping partition          (:1161-1176,1633-1655)
 //   k_blur3       x1      7x7 Gaussian, sigma 2, reflect-101, bit-exact fixed point, as two int8 Toeplitz products on the
 //                         matrix cores (v_mfma_i32_32x32x32_i8)                          (:1606-1614)         [k_blur2: VALU A/B]
@@ -1721,11 +1721,12 @@ __device__ __forceinline__ short4 qt_child_rect(short4 r, int q) {
                        (short)((q & 1) ? r.z : mx), (short)((q & 2) ? r.w : my));
 }
 
+#ifdef ORBX_AB   /* k_quadtree2p: k_quadtree2's previous body (candidate passes in every iteration behind the fused ones), A/B reference, not in the product library */
 // NT = workgroup size: NT for the usual few thousand candidates per level, 1024 when a level has tens of thousands (1080p
 // with 4000 features: the single workgroup per (frame, level) is the whole parallelism of this latency-bound kernel).
 template <int NT>
-__global__ __launch_bounds__(NT) void k_quadtree2(Geom g, const u32* __restrict__ candCnt, const u32* __restrict__ candEnt,
-                                                   u32* dense, u16* kpNode, u32* selOut, u32* selCnt, int* err, int maxCells, int maxIni, int fuseD) {
+__global__ __launch_bounds__(NT) void k_quadtree2p(Geom g, const u32* __restrict__ candCnt, const u32* __restrict__ candEnt,
+                                                    u32* dense, u16* kpNode, u32* selOut, u32* selCnt, int* err, int maxCells, int maxIni, int fuseD) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // grid = (frames, levels): consecutive workgroup ids go round-robin over the 8 XCDs, so the fastest-varying index must
     // be the frame -- with the level there and 8 levels, every level-0 (heaviest) workgroup would land on the same XCD
@@ -2061,6 +2062,339 @@ __global__ __launch_bounds__(NT) void k_quadtree2(Geom g, const u32* __restrict_
         else atomicExch(err, 3);
     }
     if (tid == 0) selCnt[frame * g.nlevels + level] = (u32)min(nsel, L.selCap);
+#undef QT_FOR_KP
+#undef QT_H
+}
+#endif  /* ORBX_AB */
+
+// words in front of the depth-d quadrant histogram of one root: 4 + 16 + ... + 4^(d-1)
+__device__ __forceinline__ int qt_hist_words(int d) { return ((1 << (2 * d)) - 4) / 3; }
+
+// The kernel makes TWO passes over a level's candidates in the common case: the gather and the final arg-max.  Every iteration in
+// between -- the ones far from N (state 0) and the final-phase ones (state 1) alike -- is node-level work on PATH HISTOGRAMS: the
+// gather pass walks each candidate through the first histD subdivisions and counts the deepest path; the coarser histograms are sums.
+// A node keeps its path and depth, and the four quadrant counts of a node at depth d are the depth-(d+1) entries under its path, so
+// while every splittable node is shallower than histD an iteration reads no candidate and relabels none ("table mode").  The first
+// iteration that meets a splittable node at depth histD leaves table mode for good: one relabel pass through the path table gives
+// every candidate its node id, and from there the iterations run on candidate passes (histogram + relabel, k_quadtree2p's).
+// At the end, table mode resolves path -> node inside the arg-max pass.
+// LDS is k_quadtree2p's: the histogram levels beyond fuseD overlay childPos / newPos (used only after table mode) and the path table
+// then overlays sortKey (dead between iterations); the planner picks histD so that both fit (orbx_plan.h).
+// NT = workgroup size: NT for the usual few thousand candidates per level, 1024 when a level has tens of thousands (1080p
+// with 4000 features: the single workgroup per (frame, level) is the whole parallelism of this latency-bound kernel).
+template <int NT>
+__global__ __launch_bounds__(NT, NT == 256 ? 7 : 4) void k_quadtree2(Geom g, const u32* __restrict__ candCnt, const u32* __restrict__ candEnt,
+                                                   u32* dense, u16* kpNode, u32* selOut, u32* selCnt, int* err, int maxCells, int maxIni, int fuseD,
+                                                   int histD, u32* fallbacks) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    // grid = (frames, levels): consecutive workgroup ids go round-robin over the 8 XCDs, so the fastest-varying index must
+    // be the frame -- with the level there and 8 levels, every level-0 (heaviest) workgroup would land on the same XCD
+    const int level = blockIdx.y, frame = blockIdx.x;
+    const LevelDesc& L = g.lv[level];
+    const int tid = threadIdx.x;
+    const int cap = g.nodeCap, n2cap = g.sortCap;
+    unsigned long long* sortKey = (unsigned long long*)smem;
+    QNode* tabA = (QNode*)(sortKey + n2cap);
+    QNode* tabB = tabA + cap;
+    u32* qc = (u32*)(tabB + cap);                           // [cap][4]; reused as best[] at the end
+    u32* s1 = qc + cap * 4;
+    u32* s2 = s1 + cap;
+    u32* cellOff = s2 + cap;                                // [maxCells + 1]
+    u16* childPos = (u16*)(cellOff + maxCells + 1);         // [cap][4]
+    u16* newPos = childPos + cap * 4;
+    u8* nch = (u8*)(newPos + cap);
+    u8* proc = nch + cap;
+    // quadrant histograms of the first histD subdivision depths, indexed by the path ((root * 4 + q1) * 4 + q2) ...; the depth-d
+    // histogram is [maxIni * 4^d].  Depths 1..fuseD lie behind proc, depths fuseD+1..histD on childPos / newPos
+    u32* Hb = (u32*)(smem + (((size_t)(proc + cap - smem) + 3) & ~(size_t)3));
+    u32* Hx = (u32*)childPos;
+#define QT_H(d) ((d) <= fuseD ? Hb + maxIni * qt_hist_words(d) : Hx + maxIni * (qt_hist_words(d) - qt_hist_words(fuseD + 1)))
+    u32* HD = QT_H(histD);
+    u16* TDb = (u16*)(Hb + maxIni * qt_hist_words(fuseD + 1));   // [maxIni * 4^fuseD]
+    u16* TD = histD == fuseD ? TDb : (u16*)sortKey;         // [maxIni * 4^histD] deepest path -> node position
+    u16* pathA = TDb + (maxIni << (2 * fuseD));             // [cap] per node: path | depth << 12
+    u16* pathB = pathA + cap;
+    __shared__ u32 wsum[2 * (NT / 64)];
+    __shared__ int s_size, s_state, s_seqBase, s_cnt, s_ncand, s_deep;
+    const u32* cnts = candCnt + (size_t)frame * g.totalCells + L.cellBase;
+    const u32* ents = candEnt + (size_t)frame * g.totalSlots + L.slotBase;
+    u32* de = dense + (size_t)frame * g.totalSlots + L.slotBase;     // candidates of this level, densely packed in
+    u16* kn = kpNode + (size_t)frame * g.totalSlots + L.slotBase;    // vToDistributeKeys order; their deepest path (table mode) / current node
+    const int N = L.N;
+
+    // ---- gather the per-cell slot arrays into one dense list (cells are stored in reference order)
+    const int nCells = L.nCells;
+    for (int c = tid; c < nCells; c += NT) cellOff[c] = min(cnts[c], (u32)L.slotCap);   // (never beyond a cell's slots, whatever the count word holds)
+    for (int i = tid; i < cap; i += NT) s1[i] = 0;
+    for (int i = tid; i < (maxIni << (2 * histD)); i += NT) HD[i] = 0;
+    __syncthreads();
+    const int nk = (int)block_scan_excl<NT>(cellOff, nCells, wsum, tid);
+    if (tid == 0) cellOff[nCells] = (u32)nk;
+    __syncthreads();
+    {   // four candidates per thread at a time: their (uniform-length, branch-free) searches for the last cell with cellOff <= i
+        // interleave, and so do the four loads of the entries
+        int top = 1;
+        while (top * 2 < nCells) top *= 2;                   // largest power of two < nCells (nCells >= 1)
+        for (int i0 = tid; i0 < nk; i0 += 4 * NT) {
+            int lo[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) lo[u] = 0;
+            for (int sft = top; sft > 0; sft >>= 1) {
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = min(i0 + u * NT, nk - 1), c = lo[u] + sft;
+                    if (c < nCells && (int)cellOff[c] <= i) lo[u] = c;
+                }
+            }
+            u32 e4[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) { const int i = min(i0 + u * NT, nk - 1); e4[u] = ents[lo[u] * L.slotCap + (i - (int)cellOff[lo[u]])]; }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int i = i0 + u * NT;
+                if (i < nk) {
+                    const u32 e = e4[u];
+                    de[i] = e;
+                    const int x = (int)(e & 0xFFF), y = (int)((e >> 12) & 0xFFF);
+                    const int root = (int)((float)x / L.hX);            // ORBextractor.cc:740
+                    atomicAdd(&s1[root], 1u);
+                    // the candidate's path through the first histD subdivisions, by the same rectangle arithmetic the iterations use
+                    short4 r = make_short4((short)(int)(L.hX * (float)root), 0, (short)(int)(L.hX * (float)(root + 1)), (short)L.qtH);
+                    int path = root;
+#pragma unroll
+                    for (int d = 0; d < 6; ++d)
+                        if (d < histD) { const int q = qt_quadrant(r, x, y); path = path * 4 + q; r = qt_child_rect(r, q); }
+                    kn[i] = (u16)path;
+                    atomicAdd(&HD[path], 1u);
+                }
+            }
+        }
+    }
+    __syncthreads();
+
+    // a pass over the level's candidates: the (entry, node) pairs of QT_U candidates per thread are requested together before any
+    // is processed -- a rolled loop pays one L2 round trip per candidate (the LDS atomics in the bodies keep the compiler from hoisting
+    // the next iteration's loads)
+#ifndef QT_U
+#define QT_U 4
+#endif
+#define QT_FOR_KP(BODY) for (int k0_ = tid; k0_ < nk; k0_ += QT_U * NT) {                                         \
+        u32 e4_[QT_U]; int n4_[QT_U];                                                                                \
+        _Pragma("unroll") for (int u_ = 0; u_ < QT_U; ++u_) { const int ki = k0_ + u_ * NT; const bool in_ = ki < nk;  \
+            e4_[u_] = in_ ? de[ki] : 0u; n4_[u_] = in_ ? (int)kn[ki] : 0; }                                          \
+        _Pragma("unroll") for (int u_ = 0; u_ < QT_U; ++u_) { const int ki = k0_ + u_ * NT;                          \
+            if (ki < nk) { const u32 e = e4_[u_]; const int nd = n4_[u_]; BODY } } }
+
+    // ---- roots (ORBextractor.cc:695-763)
+    if (tid == 0) {
+        int size = 0;
+        for (int i = 0; i < L.nIni; ++i) {
+            if (s1[i] == 0) continue;                            // empty roots are erased
+            QNode nd;
+            nd.r = make_short4((short)(int)(L.hX * (float)i), 0, (short)(int)(L.hX * (float)(i + 1)), (short)L.qtH);
+            nd.cnt = s1[i]; nd.seq = i;
+            tabA[size] = nd; pathA[size] = (u16)i; ++size;       // path = root index, depth 0
+        }
+        s_size = size; s_state = 0; s_seqBase = L.nIni; s_cnt = 0; s_ncand = 0; s_deep = 0;
+    }
+    for (int d = histD - 1; d >= 1; --d) {                    // coarser histograms by summation
+        u32* Hc = QT_H(d); const u32* Hf = QT_H(d + 1);
+        for (int i = tid; i < (L.nIni << (2 * d)); i += NT) Hc[i] = Hf[4 * i] + Hf[4 * i + 1] + Hf[4 * i + 2] + Hf[4 * i + 3];
+        __syncthreads();
+    }
+
+    QNode* A = tabA; QNode* B = tabB;
+    u16* PA = pathA; u16* PB = pathB;
+    bool table = true;                                        // (uniform) no splittable node at depth histD so far
+    // the four quadrant counts of node i: in table mode from the histogram one level below the node (and into qc, where the list
+    // surgery reads them), otherwise what the candidate pass counted
+#define QT_QC4(i) u32 q0, q1, q2, q3;                                                                               \
+        if (table) { const int v_ = PA[i]; const u32* Hn_ = QT_H((v_ >> 12) + 1) + (v_ & 0xFFF) * 4;                  \
+            q0 = Hn_[0]; q1 = Hn_[1]; q2 = Hn_[2]; q3 = Hn_[3];                                                      \
+            qc[(i) * 4] = q0; qc[(i) * 4 + 1] = q1; qc[(i) * 4 + 2] = q2; qc[(i) * 4 + 3] = q3; }                    \
+        else { q0 = qc[(i) * 4]; q1 = qc[(i) * 4 + 1]; q2 = qc[(i) * 4 + 2]; q3 = qc[(i) * 4 + 3]; }
+    // path table: every deepest path under node i's path -> i
+#define QT_FILL_TD(n) for (int i = tid; i < (n); i += NT) {                                                         \
+        const int v = PA[i], sh = 2 * (histD - (v >> 12)), p = v & 0xFFF;                                            \
+        for (int j = p << sh; j < (p + 1) << sh; ++j) TD[j] = (u16)i; }
+
+    for (int iter = 0;; ++iter) {
+        const int state = s_state, size = s_size;
+        if (state == 2) break;
+        if (iter > 4096) { if (tid == 0) atomicExch(err, 4); break; }
+        if (table && s_deep) {                                                // a splittable node at depth histD: its quadrants are in no histogram
+            // (conservative in the final phase: the walk may stop before it reaches that node, or never have it in its processed prefix --
+            // the candidate passes give the same list either way, and which nodes the prefix holds is known only after the sort)
+            if (tid == 0) atomicAdd(fallbacks, 1u);
+            QT_FILL_TD(size)
+            __syncthreads();
+            QT_FOR_KP({ (void)e; kn[ki] = TD[nd]; })
+            for (int i = tid; i < size * 4; i += NT) qc[i] = 0;
+            __syncthreads();
+            table = false;
+        }
+        // (1) quadrant histograms of every splittable node (qc, s_cnt, s_ncand were reset at the end of the previous iteration)
+        if (!table) {
+            QT_FOR_KP({ if (A[nd].cnt > 1) atomicAdd(&qc[nd * 4 + qt_quadrant(A[nd].r, e & 0xFFF, (e >> 12) & 0xFFF)], 1u); })
+            __syncthreads();
+        }
+        int totalCh = 0, newSize = 0;
+        if (state == 0) {                                                    // ORBextractor.cc:779-895
+            for (int i = tid; i < size; i += NT) {
+                int c = 0;
+                if (A[i].cnt > 1) { QT_QC4(i) c = (q0 > 0) + (q1 > 0) + (q2 > 0) + (q3 > 0); }
+                nch[i] = (u8)c; proc[i] = c > 0;
+                s1[i] = c; s2[i] = c > 0 ? 0 : 1;
+            }
+            __syncthreads();
+            u32 totCh_, totKeep_;
+            block_scan2_excl<NT>(s1, size, s2, size, wsum, tid, &totCh_, &totKeep_);
+            totalCh = (int)totCh_;
+            newSize = totalCh + (int)totKeep_;
+            for (int i = tid; i < size; i += NT) {
+                const int c = nch[i];
+                if (c > 0) {
+                    const int blockStart = totalCh - (int)s1[i] - c;
+                    const int v = table ? (int)PA[i] : 0, p4 = (v & 0xFFF) * 4, dn = (v >> 12) + 1;
+                    int fwd = 0;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const u32 qn = qc[i * 4 + q];
+                        if (qn > 0) {
+                            const int pos = blockStart + (c - 1 - fwd);
+                            QNode nd; nd.r = qt_child_rect(A[i].r, q); nd.cnt = qn; nd.seq = (u32)(s_seqBase + (int)s1[i] + fwd);
+                            B[pos] = nd;
+                            if (table) { PB[pos] = (u16)((p4 + q) | (dn << 12)); if (qn > 1 && dn >= histD) s_deep = 1; }
+                            else childPos[i * 4 + q] = (u16)pos;
+                            if (qn > 1) atomicAdd(&s_cnt, 1);
+                            ++fwd;
+                        }
+                    }
+                } else {
+                    const int pos = totalCh + (int)s2[i];
+                    B[pos] = A[i];
+                    if (table) PB[pos] = PA[i]; else newPos[i] = (u16)pos;
+                }
+            }
+        } else {                                                             // ORBextractor.cc:912-992
+            int n2 = 1;
+            while (n2 < size) n2 <<= 1;
+            for (int i = tid; i < n2; i += NT) {
+                unsigned long long key = 0;
+                if (i < size && A[i].cnt > 1) {
+                    key = ((unsigned long long)A[i].cnt << 40) | ((unsigned long long)A[i].seq << 16) | (unsigned)i;
+                    atomicAdd(&s_ncand, 1);
+                }
+                sortKey[i] = key;
+                if (i < size) {
+                    int c = 0;
+                    if (A[i].cnt > 1) { QT_QC4(i) c = (q0 > 0) + (q1 > 0) + (q2 > 0) + (q3 > 0); }
+                    nch[i] = (u8)c; proc[i] = 0;
+                }
+            }
+            __syncthreads();
+            for (int k = 2; k <= n2; k <<= 1)
+                for (int j = k >> 1; j > 0; j >>= 1) {
+                    for (int i = tid; i < n2; i += NT) {
+                        const int ixj = i ^ j;
+                        if (ixj > i) {
+                            const unsigned long long a = sortKey[i], b = sortKey[ixj];
+                            const bool up = (i & k) == 0;
+                            if ((a > b) == up) { sortKey[i] = b; sortKey[ixj] = a; }
+                        }
+                    }
+                    __syncthreads();
+                }
+            const int ncand = s_ncand;
+            // processing order k = 0.. : largest (count, seq) first = sortKey[n2-1-k]
+            for (int k = tid; k < ncand; k += NT) s1[k] = (u32)nch[(int)(sortKey[n2 - 1 - k] & 0xFFFF)] - 1u;
+            __syncthreads();
+            block_scan_excl<NT>(s1, ncand, wsum, tid);
+            // the reference stops right after the split that makes size >= N: count the splits that leave size < N
+            for (int k = tid; k < ncand; k += NT) {
+                const int gain = (int)nch[(int)(sortKey[n2 - 1 - k] & 0xFFFF)] - 1;
+                if (size + (int)s1[k] + gain < N) atomicAdd(&s_cnt, 1);
+            }
+            __syncthreads();
+            const int P = min(ncand, s_cnt + 1);
+            __syncthreads();
+            if (tid == 0) s_cnt = 0;
+            for (int k = tid; k < ncand; k += NT) {
+                const int id = (int)(sortKey[n2 - 1 - k] & 0xFFFF);
+                s1[k] = k < P ? (u32)nch[id] : 0u;
+                if (k < P) proc[id] = 1;
+            }
+            __syncthreads();
+            for (int i = tid; i < size; i += NT) s2[i] = proc[i] ? 0 : 1;
+            __syncthreads();
+            u32 totCh_, totKeep_;
+            block_scan2_excl<NT>(s1, ncand, s2, size, wsum, tid, &totCh_, &totKeep_);
+            totalCh = (int)totCh_;
+            newSize = totalCh + (int)totKeep_;
+            for (int k = tid; k < P; k += NT) {
+                const int i = (int)(sortKey[n2 - 1 - k] & 0xFFFF);
+                const int c = nch[i];
+                const int blockStart = totalCh - (int)s1[k] - c;
+                const int v = table ? (int)PA[i] : 0, p4 = (v & 0xFFF) * 4, dn = (v >> 12) + 1;
+                int fwd = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const u32 qn = qc[i * 4 + q];
+                    if (qn > 0) {
+                        const int pos = blockStart + (c - 1 - fwd);
+                        QNode nd; nd.r = qt_child_rect(A[i].r, q); nd.cnt = qn; nd.seq = (u32)(s_seqBase + (int)s1[k] + fwd);
+                        B[pos] = nd;
+                        if (table) { PB[pos] = (u16)((p4 + q) | (dn << 12)); if (qn > 1 && dn >= histD) s_deep = 1; }
+                        else childPos[i * 4 + q] = (u16)pos;
+                        ++fwd;
+                    }
+                }
+            }
+            for (int i = tid; i < size; i += NT)
+                if (!proc[i]) {
+                    const int pos = totalCh + (int)s2[i];
+                    B[pos] = A[i];
+                    if (table) PB[pos] = PA[i]; else newPos[i] = (u16)pos;
+                }
+        }
+        __syncthreads();
+        // (3) outside table mode: relabel the keypoints; the next iteration's histograms start from zero
+        if (!table) {
+            for (int i = tid; i < min(newSize, cap) * 4; i += NT) qc[i] = 0;
+            QT_FOR_KP({ kn[ki] = proc[nd] ? childPos[nd * 4 + qt_quadrant(A[nd].r, e & 0xFFF, (e >> 12) & 0xFFF)] : newPos[nd]; })
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const int nToExpand = s_cnt;
+            s_cnt = 0; s_ncand = 0;
+            s_seqBase += totalCh;
+            s_size = newSize;
+            if (newSize > cap) { atomicExch(err, 2); s_state = 2; }
+            else if (newSize >= N || newSize == size) s_state = 2;
+            else if (state == 0 && newSize + nToExpand * 3 > N) s_state = 1;
+        }
+        QNode* t_ = A; A = B; B = t_;
+        u16* tp_ = PA; PA = PB; PB = tp_;
+        __syncthreads();
+    }
+    // ---- one keypoint per node: first maximum of `response` in candidate order (ORBextractor.cc:1005-1030).  In table mode the
+    // candidates still carry their deepest path: the pass resolves it to the final node on the way
+    const int nsel = s_size;
+    u32* best = qc;
+    for (int i = tid; i < nsel; i += NT) best[i] = 0;
+    if (table) { QT_FILL_TD(min(nsel, cap)) }
+    __syncthreads();
+    if (table) { QT_FOR_KP({ atomicMax(&best[TD[nd]], ((e >> 24) << 24) | (0xFFFFFFu - (u32)ki)); }) }
+    else { QT_FOR_KP({ atomicMax(&best[nd], ((e >> 24) << 24) | (0xFFFFFFu - (u32)ki)); }) }
+    __syncthreads();
+    u32* so = selOut + (size_t)frame * g.totalSel + L.selBase;
+    for (int i = tid; i < nsel; i += NT) {
+        if (i < L.selCap) so[i] = de[0xFFFFFFu - (best[i] & 0xFFFFFFu)];
+        else atomicExch(err, 3);
+    }
+    if (tid == 0) selCnt[frame * g.nlevels + level] = (u32)min(nsel, L.selCap);
+#undef QT_FILL_TD
+#undef QT_QC4
 #undef QT_FOR_KP
 #undef QT_H
 }

@@ -206,6 +206,7 @@ struct Plan {                                              // geometry of one im
     int64_t algBytes = 0, fusedBytes = 0;
     size_t qtLds = 0, qt2Lds = 0;
     int qtFuseD = 3;
+    int qtHistD = 3;                                           // depth of k_quadtree2's deepest path histogram (>= qtFuseD)
     int maxIni = 1;                                            // most quadtree roots of any level
     int qt2Cap = 0, qt2Sort = 0;
     int maxCells = 0;
@@ -380,6 +381,13 @@ static inline int plan_quadtree_level(Planner& P, int l) {
     return 0;
 }
 
+// bytes of the quadrant histograms of depths fuseD + 1 .. D (u32, maxIni * 4^d entries at depth d)
+static inline size_t qt_hist_bytes(int maxIni, int fuseD, int D) {
+    size_t words = 0;
+    for (int d = fuseD + 1; d <= D; ++d) words += (size_t)maxIni << (2 * d);
+    return words * 4;
+}
+
 // the quadtree kernels' capacities, LDS sizes and fused depth, once every level is known
 static inline int plan_quadtree(Planner& P) {
     Plan& p = P.p;
@@ -410,6 +418,14 @@ static inline int plan_quadtree(Planner& P) {
         p.qt2Lds = (size_t)sc2 * 8 + (size_t)p.qt2Cap * (16 * 2 + 16 + 4 + 4 + 8 + 2 + 1 + 1) + (size_t)(p.maxCells + 1) * 4 + 64 +
                    (size_t)p.maxIni * (hw * 4 + tw * 2) + (size_t)p.qt2Cap * 4 + 8;
         if (p.qt2Lds > 160 * 1024 - 512) return P.fail(ORBX_E_UNSUPPORTED, "quadtree for %d features/level needs %zu B of LDS (> 160 KiB)", maxN, p.qt2Lds);
+        // depth of the deepest path histogram (table mode of k_quadtree2): the largest of fuseD .. fuseD + 2 that costs no LDS, so that
+        // as many workgroups stay resident per CU as before.  The levels beyond fuseD overlay childPos / newPos (10 B per node), the
+        // path table [maxIni * 4^D] of u16 overlays the sort keys, and a node's path | depth << 12 leaves the path 12 bits
+        p.qtHistD = p.qtFuseD;
+        for (int D = p.qtFuseD + 2; D > p.qtFuseD; --D) {
+            const size_t paths = (size_t)p.maxIni << (2 * D);
+            if (paths <= 4096 && qt_hist_bytes(p.maxIni, p.qtFuseD, D) <= (size_t)p.qt2Cap * 10 && paths * 2 <= (size_t)sc2 * 8) { p.qtHistD = D; break; }
+        }
     }
     if (p.qtLds > 160 * 1024 - 512) return P.fail(ORBX_E_UNSUPPORTED, "quadtree for %d features/level needs %zu B of LDS (> 160 KiB)", maxN, p.qtLds);
     return 0;
