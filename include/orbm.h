@@ -1085,6 +1085,97 @@ int orbm_keyframe_culling_batch_async(orbm_t*, int ncand, const int32_t* cand_ro
                                       const uint8_t* mp_valid, const int32_t* mp_nobs, const uint8_t* erased, int th_obs, float redundant_th,
                                       int32_t* n_mps, int32_t* n_redundant, uint8_t* cull, uint8_t* slot_state, int32_t* first_cull);
 
+/* ---- Covisibility votes and the local map: KeyFrame::UpdateConnections step 1 (KeyFrame.cc:474-512), the keyframeCounter of
+ * Tracking::UpdateLocalKeyFrames (Tracking.cc:3964-4013), Tracking::UpdateLocalPoints (Tracking.cc:3917-3948) and the gather of the
+ * query rows SearchLocalPoints reads, over the arrays the MapPoint refresh and KeyFrameCulling already keep resident.  Everything is
+ * integer: results are exact.
+ *
+ * orbm_covisibility_votes (host pointers, synchronous) / orbm_covisibility_votes_batch_async (device pointers, enqueue-only): one
+ * parameter list.
+ * Inputs.  counts_kf [nkf_rows] and the observation CSR obs_off [nmp + 1] / obs_row / obs_slot / obs_flags [nobs] follow the MapPoint
+ * refresh convention exactly: an entry is skipped when obs_row lies outside [0, nkf_rows) or obs_slot outside [0, min(counts_kf[row],
+ * cap)), a non-increasing obs_off pair, a pair that leaves [0, nobs] and a list of more than ORBM_MP_MAX_OBS entries are an empty list.
+ * The pool (nkf_rows, cap, counts_kf) is used only for the slot skip rule.  q_mp [nq][q_stride] = per query the MapPoint index of each
+ * slot, q_n [nq] its slot count: min(q_n, q_stride) slots are read, a negative count reads as 0, an index outside [0, nmp) means NULL.
+ * A query is a Frame's mvpMapPoints (UpdateLocalKeyFrames) or a KeyFrame's GetMapPointMatches() (UpdateConnections).  self_row [nq] =
+ * the query KeyFrame's own pool row, whose entries do not vote (mnId == mnId, KeyFrame.cc:503); -1, or a NULL array, means no self
+ * row, as for a Frame.  kf_skip [nkf_rows]: non-zero = entries of this row do not vote (the caller folds GetMap() != mpMap in here);
+ * NULL = none.  mp_valid [nmp] = !isBad(); NULL = all valid.  th is 15 for UpdateConnections and is used only for n_over.
+ * Entry flags.  Bit 0 of obs_flags = a right-camera entry.  Bit 1 = the KeyFrame isBad(): with skip_bad non-zero such an entry does
+ * not vote (UpdateConnections passes 1); UpdateLocalKeyFrames passes 0, the reference counts a bad KeyFrame and drops it afterwards
+ * (:4033).  Bit 2 is ignored here.
+ * Semantics.  Each slot of a query votes, in any order, through its MapPoint, which must be non-NULL and valid.  Every live,
+ * non-skipped entry of that MapPoint adds one vote to its row.  The reference's mObservations holds one entry per KeyFrame, so a right
+ * entry directly preceded in the list by a live, non-skipped left entry of the same row adds nothing: the KeyFrame voted at the left
+ * entry (the pair rule of KeyFrameCulling).  Any other arrangement votes per entry: this is defined here, not by the reference.  A
+ * MapPoint that sits in two slots of a query votes twice, as the reference's loop over slots does.
+ * Outputs.  votes [nq][nkf_rows] = the dense votes per query; n_voted [nq] = the number of rows with votes > 0; max_votes [nq] = the
+ * maximum vote; n_over [nq] = the number of voted rows with votes >= th; list_row / list_votes [nq][list_cap] = the rows with votes > 0 in
+ * ascending row order and their counts: the first min(n_voted, list_cap) entries are written and the rest of the row keeps the
+ * caller's bytes; list_cap may be 0 with both pointers NULL.  The reference's tie rules stay with the caller (facade/Covisibility.h):
+ * pKFmax is the first maximum in pointer order with strict >, sort(vPairs) runs on (weight, pointer) pairs; the library reports only
+ * counts.  Both forms return ORBM_OK.
+ * The device form uses no scratch: votes and the three count rows are zeroed by memsets inside the enqueued work, the votes are summed
+ * with integer atomics (per workgroup in LDS first), every output is recomputed per launch and nothing accumulates across graph
+ * replays; it is capturable (orbx_capture_begin) from the first call, and a replay follows rewritten q_mp, q_n, self_row and kf_skip
+ * rows.  Nothing reads out of bounds whatever the indices hold.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL required array (self_row, kf_skip and mp_valid may be NULL; list_row / list_votes only
+ * with list_cap 0); nq, q_stride, nkf_rows, cap or nmp < 1; nobs or list_cap < 0.  ORBM_E_CAPACITY: nq > ORBM_COVIS_MAX_QUERIES,
+ * q_stride > ORBM_COVIS_MAX_SLOTS, nkf_rows > ORBM_COVIS_MAX_ROWS, nmp > ORBM_MP_MAX_BATCH, nq * nkf_rows > ORBM_COVIS_MAX_VOTES,
+ * nkf_rows * cap > 2^31 - 1.  No CPU fallback: ORBM_E_HIP without a device.
+ *
+ * orbm_local_points (host pointers, synchronous) / orbm_local_points_batch_async (device pointers, enqueue-only): one parameter list.
+ * lkf_row [T][lkf_stride], n_lkf [T] = per frame the local KeyFrames' pool rows IN THE ORDER WALKED: the reference walks
+ * mvpLocalKeyFrames with a reverse iterator (:3921), so the caller lays the list out reversed.  min(n_lkf, lkf_stride) rows are read, a
+ * negative count reads as 0, a row outside [0, nkf_rows) contributes nothing.  kf_mp [nkf_rows][cap] is pool-wide: per pool slot the
+ * MapPoint index of GetMapPointMatches()[i]; an index outside [0, nmp) means NULL.  mp_valid as above.
+ * Semantics, for one frame.  Position (k, i) holds the MapPoint j = kf_mp[lkf_row[k]][i], for i < min(counts_kf[row], cap).  j is
+ * emitted at its FIRST position in (k, i) lexicographic order, provided it is valid: the mnTrackReferenceForFrame test of :3938-3944.
+ * A KeyFrame listed twice emits nothing the second time.
+ * Outputs.  local_mp [T][q_stride] = the emitted indices in position order, which is the order of mvpLocalMapPoints (M3's claim
+ * order); n_total [T] = how many MapPoints were emitted in all; nq [T] = min(n_total, q_stride).  Emissions beyond q_stride are
+ * dropped; slots at and beyond nq keep the caller's bytes.  local_mp and nq are inputs of orbm_gather_map_points_batch_async and
+ * orbm_is_in_frustum_batch_async.  Both forms return ORBM_OK.
+ * Scratch: the first positions [T][nmp] and the chunk counts are handle-owned, grown by an eager call; after one eager call the same
+ * or a smaller shape enqueues with no allocation and can be captured (orbx_capture_begin).  The first positions are reset by a memset
+ * inside the enqueued work.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL array (mp_valid may be NULL); T, lkf_stride, nkf_rows, cap, nmp or q_stride < 1.
+ * ORBM_E_CAPACITY: T > ORBM_LOCALPTS_MAX_FRAMES, lkf_stride > ORBM_LOCALPTS_MAX_KFS, cap > ORBM_LOCALPTS_MAX_CAP, lkf_stride * cap >
+ * 2^31 - 1, T * nmp > ORBM_COVIS_MAX_VOTES, nmp > ORBM_MP_MAX_BATCH.  ORBM_E_HIP without a device.
+ *
+ * orbm_gather_map_points_batch_async (device pointers, enqueue-only; there is no host form): for e < min(nq[f], q_stride) and j =
+ * local_mp[f][e] the MapPoint pool rows mp_pw [nmp][3], mp_normal [nmp][3], mp_min_dist, mp_max_dist [nmp], mp_desc [nmp][32] and
+ * mp_nobs [nmp] (int32, Observations()) are copied to pw, normal [T][q_stride][3], min_dist, max_dist [T][q_stride], qdesc
+ * [T][q_stride][32] and mp_obs [T][q_stride] (uint8, mp_nobs > 0): the rows orbm_is_in_frustum_batch_async and
+ * orbm_search_by_projection_points_batch_async read.  skip [T][q_stride] = mp_skip [T][nmp] at j, the caller's mnLastFrameSeen == mnId
+ * flags; with mp_skip NULL it is 0.  Every source / destination pair is optional: a NULL destination (or source) is not written.
+ * Entries at and beyond nq[f] keep the caller's bytes.  An index outside [0, nmp), possible only if the caller wrote local_mp itself,
+ * gets skip = 1 and nothing else.  Alignment: mp_desc and qdesc must be 16-byte aligned (descriptor rows move as two 128-bit words);
+ * every other array is aligned to its element.  No scratch; capturable from the first call.  ORBM_E_INVALID: local_mp or nq NULL; T,
+ * q_stride or nmp < 1; a misaligned descriptor array.  ORBM_E_CAPACITY: T > ORBM_LOCALPTS_MAX_FRAMES, nmp > ORBM_MP_MAX_BATCH. */
+enum { ORBM_COVIS_MAX_QUERIES = 65535, ORBM_COVIS_MAX_SLOTS = 65535, ORBM_COVIS_MAX_ROWS = 1 << 20, ORBM_COVIS_MAX_VOTES = 1 << 28 };
+enum { ORBM_LOCALPTS_MAX_FRAMES = 65535, ORBM_LOCALPTS_MAX_KFS = 65535, ORBM_LOCALPTS_MAX_CAP = 65535 };
+int orbm_covisibility_votes(orbm_t*, int nq, int q_stride, const int32_t* q_mp, const int32_t* q_n, const int32_t* self_row,
+                            int nkf_rows, int cap, const int32_t* counts_kf, const uint8_t* kf_skip, int skip_bad,
+                            int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                            const uint8_t* obs_flags, const uint8_t* mp_valid, int th, int list_cap,
+                            int32_t* votes, int32_t* n_voted, int32_t* max_votes, int32_t* n_over, int32_t* list_row, int32_t* list_votes);
+int orbm_covisibility_votes_batch_async(orbm_t*, int nq, int q_stride, const int32_t* q_mp, const int32_t* q_n, const int32_t* self_row,
+                                        int nkf_rows, int cap, const int32_t* counts_kf, const uint8_t* kf_skip, int skip_bad,
+                                        int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                        const uint8_t* obs_flags, const uint8_t* mp_valid, int th, int list_cap,
+                                        int32_t* votes, int32_t* n_voted, int32_t* max_votes, int32_t* n_over, int32_t* list_row, int32_t* list_votes);
+int orbm_local_points(orbm_t*, int T, int lkf_stride, const int32_t* lkf_row, const int32_t* n_lkf, int nkf_rows, int cap,
+                      const int32_t* counts_kf, const int32_t* kf_mp, int nmp, const uint8_t* mp_valid, int q_stride,
+                      int32_t* local_mp, int32_t* n_total, int32_t* nq);
+int orbm_local_points_batch_async(orbm_t*, int T, int lkf_stride, const int32_t* lkf_row, const int32_t* n_lkf, int nkf_rows, int cap,
+                                  const int32_t* counts_kf, const int32_t* kf_mp, int nmp, const uint8_t* mp_valid, int q_stride,
+                                  int32_t* local_mp, int32_t* n_total, int32_t* nq);
+int orbm_gather_map_points_batch_async(orbm_t*, int T, int q_stride, const int32_t* local_mp, const int32_t* nq, int nmp,
+                                       const float* mp_pw, const float* mp_normal, const float* mp_min_dist, const float* mp_max_dist,
+                                       const uint8_t* mp_desc, const int32_t* mp_nobs, const uint8_t* mp_skip,
+                                       float* pw, float* normal, float* min_dist, float* max_dist, uint8_t* qdesc, uint8_t* mp_obs, uint8_t* skip);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

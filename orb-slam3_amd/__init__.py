@@ -25,6 +25,8 @@ DEPTH_SELECT_MAX_CAP = 16384                         # include/orbm.h: ORBM_DEPT
 BOWVEC_MAX_CAP = 16384                               # include/orbm.h: ORBM_BOWVEC_MAX_CAP
 KFDB_MAX_ROWS, KFDB_MAX_QUERIES = 1 << 20, 65535     # include/orbm.h: ORBM_KFDB_MAX_ROWS, ORBM_KFDB_MAX_QUERIES
 KFCULL_MAX_CAND, KFCULL_MAX_CAP = 65535, 65535       # include/orbm.h: ORBM_KFCULL_MAX_CAND, ORBM_KFCULL_MAX_CAP
+COVIS_MAX_QUERIES, COVIS_MAX_SLOTS, COVIS_MAX_ROWS, COVIS_MAX_VOTES = 65535, 65535, 1 << 20, 1 << 28   # include/orbm.h: ORBM_COVIS_MAX_*
+LOCALPTS_MAX_FRAMES, LOCALPTS_MAX_KFS, LOCALPTS_MAX_CAP = 65535, 65535, 65535                          # include/orbm.h: ORBM_LOCALPTS_MAX_*
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -947,6 +949,19 @@ def _install_search():
                                      ci, ci, vp, vp, vp, vp,                       # nmp, nobs, obs_off, obs_row, obs_slot, obs_flags
                                      vp, vp, vp, ci, cf,                           # mp_valid, mp_nobs, erased, th_obs, redundant_th
                                      vp, vp, vp, vp, vp]                           # n_mps, n_redundant, cull, slot_state, first_cull
+    for name in ("orbm_covisibility_votes", "orbm_covisibility_votes_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, ci, vp, vp, vp,                       # nq, q_stride, q_mp, q_n, self_row
+                                     ci, ci, vp, vp, ci,                           # nkf_rows, cap, counts_kf, kf_skip, skip_bad
+                                     ci, ci, vp, vp, vp, vp, vp,                   # nmp, nobs, obs_off, obs_row, obs_slot, obs_flags, mp_valid
+                                     ci, ci,                                       # th, list_cap
+                                     vp, vp, vp, vp, vp, vp]                       # votes, n_voted, max_votes, n_over, list_row, list_votes
+    for name in ("orbm_local_points", "orbm_local_points_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, ci, vp, vp, ci, ci,                   # T, lkf_stride, lkf_row, n_lkf, nkf_rows, cap
+                                     vp, vp, ci, vp, ci,                           # counts_kf, kf_mp, nmp, mp_valid, q_stride
+                                     vp, vp, vp]                                   # local_mp, n_total, nq
+    L.orbm_gather_map_points_batch_async.argtypes = [vp, ci, ci, vp, vp, ci,       # T, q_stride, local_mp, nq, nmp
+                                                     vp, vp, vp, vp, vp, vp, vp,   # mp_pw, mp_normal, mp_min_dist, mp_max_dist, mp_desc, mp_nobs, mp_skip
+                                                     vp, vp, vp, vp, vp, vp, vp]   # pw, normal, min_dist, max_dist, qdesc, mp_obs, skip
     L.orbm_is_in_frustum_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp,                 # nframes, tcw, ow, nq, q_stride, skip
                                                  vp, vp, vp, vp, ci,                         # pw, normal, min_dist, max_dist, q_shared
                                                  vp, vp, cf, cf, cf, ci,                     # k, bounds (host), bf, cos limit, log scale factor, levels
@@ -1151,6 +1166,69 @@ def _install_search():
                                                              float(redundant_th), n_mps, n_redundant, cull, slot_state, first_cull),
                     "orbm_keyframe_culling_batch_async")
 
+    def covisibility_votes(self, q_mp, q_n, self_row, counts_kf, cap, kf_skip, skip_bad, obs_off, obs_row, obs_slot, obs_flags, mp_valid=None, th=15,
+                           list_cap=0, list_fill=-1):
+        """The covisibility vote of KeyFrame::UpdateConnections step 1 (KeyFrame.cc:474-512, skip_bad 1) or Tracking::UpdateLocalKeyFrames
+        (Tracking.cc:3964-4013, skip_bad 0) for the queries q_mp [nq][q_stride] -> dict of votes [nq][nkf_rows], n_voted, max_votes, n_over
+        [nq], list_row, list_votes [nq][list_cap] (None with list_cap 0; entries that are not written hold list_fill).  self_row, kf_skip
+        and mp_valid may be None (include/orbm.h: orbm_covisibility_votes)."""
+        qm = np.ascontiguousarray(q_mp, np.int32); nq, qs = qm.shape
+        qn = np.ascontiguousarray(q_n, np.int32); cnt = np.ascontiguousarray(counts_kf, np.int32); nrows = len(cnt)
+        sr = None if self_row is None else np.ascontiguousarray(self_row, np.int32)
+        ks = None if kf_skip is None else np.ascontiguousarray(kf_skip, np.uint8)
+        nmp = len(obs_off) - 1
+        off, row, slot, fl, v, nobs = _obs_arrays(obs_off, obs_row, obs_slot, obs_flags, mp_valid, nmp)
+        if len(qn) != nq or (sr is not None and len(sr) != nq) or (ks is not None and len(ks) != nrows):
+            raise OrbError("q_n and self_row hold one entry per query, kf_skip one per pool row")
+        out = {"votes": np.zeros((max(nq, 1), nrows), np.int32), "n_voted": np.zeros(max(nq, 1), np.int32), "max_votes": np.zeros(max(nq, 1), np.int32),
+               "n_over": np.zeros(max(nq, 1), np.int32)}
+        lr = np.full((max(nq, 1), list_cap), list_fill, np.int32) if list_cap > 0 else None
+        lv = np.full((max(nq, 1), list_cap), list_fill, np.int32) if list_cap > 0 else None
+        opt = lambda a: None if a is None else _p(a)
+        _chk(self.L.orbm_covisibility_votes(self.h, nq, qs, _p(qm), _p(qn), opt(sr), nrows, int(cap), _p(cnt), opt(ks), int(skip_bad), nmp, nobs, _p(off),
+                                            _p(row), _p(slot), _p(fl), opt(v), int(th), int(list_cap), _p(out["votes"]), _p(out["n_voted"]),
+                                            _p(out["max_votes"]), _p(out["n_over"]), opt(lr), opt(lv)), "orbm_covisibility_votes")
+        out = {key: a[:nq] for key, a in out.items()}
+        out.update(list_row=None if lr is None else lr[:nq], list_votes=None if lv is None else lv[:nq])
+        return out
+
+    def covisibility_votes_batch_async(self, nq, q_stride, q_mp, q_n, self_row, nkf_rows, cap, counts_kf, kf_skip, skip_bad, nmp, nobs, obs_off, obs_row,
+                                       obs_slot, obs_flags, mp_valid, th, list_cap, votes, n_voted, max_votes, n_over, list_row=None, list_votes=None):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_covisibility_votes_batch_async)."""
+        return _chk(self.L.orbm_covisibility_votes_batch_async(self.h, nq, q_stride, q_mp, q_n, self_row, nkf_rows, cap, counts_kf, kf_skip, int(skip_bad),
+                                                               nmp, nobs, obs_off, obs_row, obs_slot, obs_flags, mp_valid, int(th), int(list_cap), votes,
+                                                               n_voted, max_votes, n_over, list_row, list_votes),
+                    "orbm_covisibility_votes_batch_async")
+
+    def local_points(self, lkf_row, n_lkf, counts_kf, kf_mp, nmp, mp_valid=None, q_stride=None, fill=-1):
+        """Tracking::UpdateLocalPoints (Tracking.cc:3917-3948) for T frames: lkf_row [T][lkf_stride] = the local KeyFrames' pool rows in the
+        order walked, kf_mp [nkf_rows][cap] -> (local_mp [T][q_stride], n_total [T], nq [T]); slots at and beyond nq hold `fill`
+        (include/orbm.h: orbm_local_points)."""
+        lk = np.ascontiguousarray(lkf_row, np.int32); T, ls = lk.shape
+        nl = np.ascontiguousarray(n_lkf, np.int32); cnt = np.ascontiguousarray(counts_kf, np.int32)
+        km = np.ascontiguousarray(kf_mp, np.int32); nrows, cap = km.shape
+        v = None if mp_valid is None else np.ascontiguousarray(mp_valid, np.uint8)
+        if len(nl) != T or len(cnt) != nrows or (v is not None and len(v) != nmp):
+            raise OrbError("n_lkf holds one entry per frame, counts_kf one per pool row, mp_valid one per MapPoint")
+        qs = int(q_stride) if q_stride is not None else max(1, min(int(nmp), ls * cap))
+        out = np.full((max(T, 1), max(qs, 1)), fill, np.int32); nt = np.zeros(max(T, 1), np.int32); nq = np.zeros(max(T, 1), np.int32)
+        _chk(self.L.orbm_local_points(self.h, T, ls, _p(lk), _p(nl), nrows, cap, _p(cnt), _p(km), int(nmp), None if v is None else _p(v), qs, _p(out),
+                                      _p(nt), _p(nq)), "orbm_local_points")
+        return out[:T], nt[:T], nq[:T]
+
+    def local_points_batch_async(self, T, lkf_stride, lkf_row, n_lkf, nkf_rows, cap, counts_kf, kf_mp, nmp, mp_valid, q_stride, local_mp, n_total, nq):
+        """Device form, enqueue only: every array argument is a device pointer (include/orbm.h: orbm_local_points_batch_async)."""
+        return _chk(self.L.orbm_local_points_batch_async(self.h, T, lkf_stride, lkf_row, n_lkf, nkf_rows, cap, counts_kf, kf_mp, nmp, mp_valid, q_stride,
+                                                         local_mp, n_total, nq), "orbm_local_points_batch_async")
+
+    def gather_map_points_batch_async(self, T, q_stride, local_mp, nq, nmp, mp_pw=None, mp_normal=None, mp_min_dist=None, mp_max_dist=None, mp_desc=None,
+                                      mp_nobs=None, mp_skip=None, pw=None, normal=None, min_dist=None, max_dist=None, qdesc=None, mp_obs=None, skip=None):
+        """The query rows of SearchLocalPoints gathered from the MapPoint pool by local_mp, enqueue only: every array argument is a device
+        pointer, every source / destination pair optional (include/orbm.h: orbm_gather_map_points_batch_async)."""
+        return _chk(self.L.orbm_gather_map_points_batch_async(self.h, T, q_stride, local_mp, nq, nmp, mp_pw, mp_normal, mp_min_dist, mp_max_dist, mp_desc,
+                                                              mp_nobs, mp_skip, pw, normal, min_dist, max_dist, qdesc, mp_obs, skip),
+                    "orbm_gather_map_points_batch_async")
+
     def is_in_frustum_batch(self, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, q_shared, K, bounds, bf, viewing_cos_limit,
                             log_scale_factor, n_levels, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view=None):
         """Frame::isInFrustum for every frame of a batch in one launch, enqueue only: every array argument is a device pointer except K =
@@ -1167,6 +1245,11 @@ def _install_search():
     ORBmatcher.KfdbQueryBatchAsync = kfdb_query_batch_async
     ORBmatcher.KeyframeCulling = keyframe_culling
     ORBmatcher.KeyframeCullingBatchAsync = keyframe_culling_batch_async
+    ORBmatcher.CovisibilityVotes = covisibility_votes
+    ORBmatcher.CovisibilityVotesBatchAsync = covisibility_votes_batch_async
+    ORBmatcher.LocalPoints = local_points
+    ORBmatcher.LocalPointsBatchAsync = local_points_batch_async
+    ORBmatcher.GatherMapPointsBatchAsync = gather_map_points_batch_async
     ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
     ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
     ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
@@ -1259,6 +1342,8 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_update_normal_and_depth", "orbm_update_normal_and_depth_batch_async",
             "orbm_bow_vector_batch_async", "orbm_kfdb_query", "orbm_kfdb_query_batch_async",
             "orbm_keyframe_culling", "orbm_keyframe_culling_batch_async",
+            "orbm_covisibility_votes", "orbm_covisibility_votes_batch_async", "orbm_local_points", "orbm_local_points_batch_async",
+            "orbm_gather_map_points_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

@@ -3008,4 +3008,202 @@ int orbm_keyframe_culling(orbm_t* m, int ncand, const int32_t* cand_row, int nkf
     return n;
 }
 
+
+// ---- Covisibility votes, local map points and their gather: KeyFrame::UpdateConnections step 1, Tracking::UpdateLocalKeyFrames' vote,
+// Tracking::UpdateLocalPoints and the query rows of SearchLocalPoints, over the pool and the CSR of the MapPoint refresh ----
+static int covis_handle(const char* who, orbm_t* m) {
+    if (m) return ORBM_OK;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) { set_merr("%s: no HIP device: the MI355X matcher has no CPU fallback", who); return ORBM_E_HIP; }
+    set_merr("%s: the handle is NULL", who);
+    return ORBM_E_INVALID;
+}
+
+// the argument tests the host and the device form share; fills the observation block of the kernel
+static int covis_args(const char* who, orbm_t* m, int nq, int q_stride, const int32_t* q_mp, const int32_t* q_n, int nkf_rows, int cap,
+                      const int32_t* counts_kf, int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                      const uint8_t* obs_flags, const uint8_t* mp_valid, int list_cap, int32_t* votes, int32_t* n_voted, int32_t* max_votes,
+                      int32_t* n_over, int32_t* list_row, int32_t* list_votes, MpObs& O) {
+    if (const int rc = covis_handle(who, m)) return rc;
+    const struct { const void* p; const char* name; } req[] = {
+        {q_mp, "q_mp"}, {q_n, "q_n"}, {counts_kf, "counts_kf"}, {obs_off, "obs_off"}, {obs_row, "obs_row"}, {obs_slot, "obs_slot"},
+        {obs_flags, "obs_flags"}, {votes, "votes"}, {n_voted, "n_voted"}, {max_votes, "max_votes"}, {n_over, "n_over"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (nq < 1 || q_stride < 1) { set_merr("%s: nq %d and q_stride %d must be >= 1", who, nq, q_stride); return ORBM_E_INVALID; }
+    if (list_cap < 0 || (list_cap > 0 && (!list_row || !list_votes))) { set_merr("%s: list_cap %d needs list_row and list_votes", who, list_cap); return ORBM_E_INVALID; }
+    if (nmp < 1 || nkf_rows < 1 || cap < 1 || nobs < 0) { set_merr("%s: nmp, nkf_rows and cap must be >= 1 and nobs >= 0", who); return ORBM_E_INVALID; }
+    if (nq > ORBM_COVIS_MAX_QUERIES || q_stride > ORBM_COVIS_MAX_SLOTS) {
+        set_merr("%s: %d queries of %d slots (at most %d of %d)", who, nq, q_stride, (int)ORBM_COVIS_MAX_QUERIES, (int)ORBM_COVIS_MAX_SLOTS);
+        return ORBM_E_CAPACITY;
+    }
+    if (nkf_rows > ORBM_COVIS_MAX_ROWS) { set_merr("%s: %d pool rows (at most %d)", who, nkf_rows, (int)ORBM_COVIS_MAX_ROWS); return ORBM_E_CAPACITY; }
+    if ((long long)nq * nkf_rows > ORBM_COVIS_MAX_VOTES) { set_merr("%s: %d queries x %d rows of votes (at most 2^28)", who, nq, nkf_rows); return ORBM_E_CAPACITY; }
+    return mp_obs_args(who, nmp, nkf_rows, cap, nobs, obs_off, obs_row, obs_slot, obs_flags, mp_valid, O);
+}
+
+int orbm_covisibility_votes_batch_async(orbm_t* m, int nq, int q_stride, const int32_t* q_mp, const int32_t* q_n, const int32_t* self_row,
+                                        int nkf_rows, int cap, const int32_t* counts_kf, const uint8_t* kf_skip, int skip_bad,
+                                        int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                                        const uint8_t* obs_flags, const uint8_t* mp_valid, int th, int list_cap,
+                                        int32_t* votes, int32_t* n_voted, int32_t* max_votes, int32_t* n_over, int32_t* list_row, int32_t* list_votes) {
+    MpObs O;
+    const int rc = covis_args("CovisibilityVotes batch", m, nq, q_stride, q_mp, q_n, nkf_rows, cap, counts_kf, nmp, nobs, obs_off, obs_row, obs_slot,
+                              obs_flags, mp_valid, list_cap, votes, n_voted, max_votes, n_over, list_row, list_votes, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const CovisParams P{q_stride, skip_bad ? 1 : 0, q_mp, q_n, self_row, counts_kf, kf_skip};
+    // the vote rows start from zero inside the enqueued work: a replayed graph replays the memsets
+    MHIPCHK(hipMemsetAsync(votes, 0, sizeof(int32_t) * (size_t)nq * nkf_rows, m->stream));
+    MHIPCHK(hipMemsetAsync(n_voted, 0, sizeof(int32_t) * nq, m->stream));
+    MHIPCHK(hipMemsetAsync(max_votes, 0, sizeof(int32_t) * nq, m->stream));
+    MHIPCHK(hipMemsetAsync(n_over, 0, sizeof(int32_t) * nq, m->stream));
+    const dim3 grid((q_stride + COVIS_WG_SLOTS - 1) / COVIS_WG_SLOTS, nq);
+#ifdef ORBX_AB
+    if (ab_env("ORBM_COVIS_PLAIN"))                                         // A/B: one global atomicAdd per vote
+        hipLaunchKernelGGL(k_covis_votes<false>, grid, dim3(256), 0, m->stream, P, O, votes);
+    else
+#endif
+    hipLaunchKernelGGL(k_covis_votes<true>, grid, dim3(256), 0, m->stream, P, O, votes);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_covis_finish, dim3(nq), dim3(1024), 0, m->stream, nkf_rows, th, list_cap, votes, n_voted, max_votes, n_over, list_row, list_votes);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_covisibility_votes(orbm_t* m, int nq, int q_stride, const int32_t* q_mp, const int32_t* q_n, const int32_t* self_row,
+                            int nkf_rows, int cap, const int32_t* counts_kf, const uint8_t* kf_skip, int skip_bad,
+                            int nmp, int nobs, const int32_t* obs_off, const int32_t* obs_row, const int32_t* obs_slot,
+                            const uint8_t* obs_flags, const uint8_t* mp_valid, int th, int list_cap,
+                            int32_t* votes, int32_t* n_voted, int32_t* max_votes, int32_t* n_over, int32_t* list_row, int32_t* list_votes) {
+    MpObs O;
+    int rc = covis_args("CovisibilityVotes", m, nq, q_stride, q_mp, q_n, nkf_rows, cap, counts_kf, nmp, nobs, obs_off, obs_row, obs_slot, obs_flags,
+                        mp_valid, list_cap, votes, n_voted, max_votes, n_over, list_row, list_votes, O);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t ne = (size_t)std::max(nobs, 1), nv = (size_t)nq * nkf_rows, nl = (size_t)nq * list_cap;
+    DevBuf dqm, dqn, dself, dc, dks, doff, drow, dslot, dfl, dv, dcnt, dvotes, dlr, dlv;
+    arena_reset(m);
+    UP(dqm, q_mp, sizeof(int32_t) * (size_t)nq * q_stride); UP(dqn, q_n, sizeof(int32_t) * nq);
+    if (self_row) UP(dself, self_row, sizeof(int32_t) * nq);
+    UP(dc, counts_kf, sizeof(int32_t) * nkf_rows);
+    if (kf_skip) UP(dks, kf_skip, nkf_rows);
+    UP(doff, obs_off, sizeof(int32_t) * ((size_t)nmp + 1));
+    UP(drow, obs_row, sizeof(int32_t) * ne * (nobs > 0)); UP(dslot, obs_slot, sizeof(int32_t) * ne * (nobs > 0)); UP(dfl, obs_flags, ne * (nobs > 0));
+    if (mp_valid) UP(dv, mp_valid, nmp);
+    AL(dcnt, sizeof(int32_t) * 3 * (size_t)nq); AL(dvotes, sizeof(int32_t) * nv);
+    if (list_cap > 0) { AL(dlr, sizeof(int32_t) * nl); AL(dlv, sizeof(int32_t) * nl); }
+    ARENA_FLUSH(m);
+    int32_t* cnt = dcnt.as<int32_t>();
+    rc = orbm_covisibility_votes_batch_async(m, nq, q_stride, dqm.as<int32_t>(), dqn.as<int32_t>(), self_row ? dself.as<int32_t>() : nullptr, nkf_rows, cap,
+                                             dc.as<int32_t>(), kf_skip ? dks.as<uint8_t>() : nullptr, skip_bad, nmp, nobs, doff.as<int32_t>(),
+                                             drow.as<int32_t>(), dslot.as<int32_t>(), dfl.as<uint8_t>(), mp_valid ? dv.as<uint8_t>() : nullptr, th, list_cap,
+                                             dvotes.as<int32_t>(), cnt, cnt + nq, cnt + 2 * (size_t)nq, list_cap > 0 ? dlr.as<int32_t>() : nullptr,
+                                             list_cap > 0 ? dlv.as<int32_t>() : nullptr);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    const int32_t* hc = (const int32_t*)dcnt.host();
+    memcpy(n_voted, hc, sizeof(int32_t) * nq); memcpy(max_votes, hc + nq, sizeof(int32_t) * nq); memcpy(n_over, hc + 2 * (size_t)nq, sizeof(int32_t) * nq);
+    memcpy(votes, dvotes.host(), sizeof(int32_t) * nv);
+    for (int q = 0; q < nq && list_cap > 0; ++q) {                           // the rest of a list row keeps the caller's bytes
+        const size_t n = (size_t)std::min(n_voted[q], list_cap), o = (size_t)q * list_cap;
+        memcpy(list_row + o, (const int32_t*)dlr.host() + o, sizeof(int32_t) * n); memcpy(list_votes + o, (const int32_t*)dlv.host() + o, sizeof(int32_t) * n);
+    }
+    return ORBM_OK;
+}
+
+static int lp_args(const char* who, orbm_t* m, int T, int lkf_stride, const int32_t* lkf_row, const int32_t* n_lkf, int nkf_rows, int cap,
+                   const int32_t* counts_kf, const int32_t* kf_mp, int nmp, int q_stride, int32_t* local_mp, int32_t* n_total, int32_t* nq) {
+    if (const int rc = covis_handle(who, m)) return rc;
+    const struct { const void* p; const char* name; } req[] = {
+        {lkf_row, "lkf_row"}, {n_lkf, "n_lkf"}, {counts_kf, "counts_kf"}, {kf_mp, "kf_mp"}, {local_mp, "local_mp"}, {n_total, "n_total"}, {nq, "nq"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (T < 1 || lkf_stride < 1 || nkf_rows < 1 || cap < 1 || nmp < 1 || q_stride < 1) {
+        set_merr("%s: T, lkf_stride, nkf_rows, cap, nmp and q_stride must be >= 1", who);
+        return ORBM_E_INVALID;
+    }
+    if (T > ORBM_LOCALPTS_MAX_FRAMES || lkf_stride > ORBM_LOCALPTS_MAX_KFS || cap > ORBM_LOCALPTS_MAX_CAP) {
+        set_merr("%s: %d frames of %d KeyFrames of %d slots (at most %d, %d, %d)", who, T, lkf_stride, cap, (int)ORBM_LOCALPTS_MAX_FRAMES,
+                 (int)ORBM_LOCALPTS_MAX_KFS, (int)ORBM_LOCALPTS_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if ((long long)lkf_stride * cap > INT_MAX) { set_merr("%s: %d x %d positions (the key holds 2^31 - 1)", who, lkf_stride, cap); return ORBM_E_CAPACITY; }
+    if (nmp > ORBM_MP_MAX_BATCH) { set_merr("%s: %d MapPoints in one call (at most %d)", who, nmp, (int)ORBM_MP_MAX_BATCH); return ORBM_E_CAPACITY; }
+    if ((long long)T * nmp > ORBM_COVIS_MAX_VOTES) { set_merr("%s: %d frames x %d MapPoints of first positions (at most 2^28)", who, T, nmp); return ORBM_E_CAPACITY; }
+    return ORBM_OK;
+}
+
+int orbm_local_points_batch_async(orbm_t* m, int T, int lkf_stride, const int32_t* lkf_row, const int32_t* n_lkf, int nkf_rows, int cap,
+                                  const int32_t* counts_kf, const int32_t* kf_mp, int nmp, const uint8_t* mp_valid, int q_stride,
+                                  int32_t* local_mp, int32_t* n_total, int32_t* nq) {
+    const int rc = lp_args("LocalPoints batch", m, T, lkf_stride, lkf_row, n_lkf, nkf_rows, cap, counts_kf, kf_mp, nmp, q_stride, local_mp, n_total, nq);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const unsigned npos = (unsigned)lkf_stride * (unsigned)cap;
+    const int nchunks = (int)((npos + LP_CHUNK - 1) / LP_CHUNK);
+    const size_t bFirst = (sizeof(unsigned) * (size_t)T * nmp + 255) & ~(size_t)255, bCnt = sizeof(int) * (size_t)T * nchunks;
+    uint8_t* scr = batch_scratch(m, bFirst + bCnt);
+    if (!scr) { set_merr("LocalPoints scratch of %zu B unavailable (inside a capture, run the call once eagerly first)", bFirst + bCnt); return ORBM_E_HIP; }
+    unsigned* first_pos = (unsigned*)scr;
+    int* chunk = (int*)(scr + bFirst);
+    const LpParams P{lkf_stride, nkf_rows, cap, nmp, nchunks, lkf_row, n_lkf, counts_kf, kf_mp, mp_valid};
+    MHIPCHK(hipMemsetAsync(first_pos, 0xFF, sizeof(unsigned) * (size_t)T * nmp, m->stream));
+    hipLaunchKernelGGL(k_lp_mark, dim3((npos + 255) / 256, T), dim3(256), 0, m->stream, P, npos, first_pos);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_lp_count, dim3(nchunks, T), dim3(256), 0, m->stream, P, npos, first_pos, chunk);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_lp_scan, dim3(T), dim3(1024), 0, m->stream, nchunks, q_stride, chunk, n_total, nq);
+    MHIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_lp_write, dim3(nchunks, T), dim3(256), 0, m->stream, P, npos, first_pos, chunk, q_stride, local_mp);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_local_points(orbm_t* m, int T, int lkf_stride, const int32_t* lkf_row, const int32_t* n_lkf, int nkf_rows, int cap,
+                      const int32_t* counts_kf, const int32_t* kf_mp, int nmp, const uint8_t* mp_valid, int q_stride,
+                      int32_t* local_mp, int32_t* n_total, int32_t* nq) {
+    int rc = lp_args("LocalPoints", m, T, lkf_stride, lkf_row, n_lkf, nkf_rows, cap, counts_kf, kf_mp, nmp, q_stride, local_mp, n_total, nq);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    DevBuf dl, dn, dc, dkm, dv, dcnt, dout;
+    arena_reset(m);
+    UP(dl, lkf_row, sizeof(int32_t) * (size_t)T * lkf_stride); UP(dn, n_lkf, sizeof(int32_t) * T); UP(dc, counts_kf, sizeof(int32_t) * nkf_rows);
+    UP(dkm, kf_mp, sizeof(int32_t) * (size_t)nkf_rows * cap);
+    if (mp_valid) UP(dv, mp_valid, nmp);
+    AL(dcnt, sizeof(int32_t) * 2 * (size_t)T); AL(dout, sizeof(int32_t) * (size_t)T * q_stride);
+    ARENA_FLUSH(m);
+    int32_t* cnt = dcnt.as<int32_t>();
+    rc = orbm_local_points_batch_async(m, T, lkf_stride, dl.as<int32_t>(), dn.as<int32_t>(), nkf_rows, cap, dc.as<int32_t>(), dkm.as<int32_t>(), nmp,
+                                       mp_valid ? dv.as<uint8_t>() : nullptr, q_stride, dout.as<int32_t>(), cnt, cnt + T);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    const int32_t* hc = (const int32_t*)dcnt.host();
+    memcpy(n_total, hc, sizeof(int32_t) * T); memcpy(nq, hc + T, sizeof(int32_t) * T);
+    for (int f = 0; f < T; ++f)                                              // slots at and beyond nq keep the caller's bytes
+        memcpy(local_mp + (size_t)f * q_stride, (const int32_t*)dout.host() + (size_t)f * q_stride, sizeof(int32_t) * (size_t)std::max(nq[f], 0));
+    return ORBM_OK;
+}
+
+int orbm_gather_map_points_batch_async(orbm_t* m, int T, int q_stride, const int32_t* local_mp, const int32_t* nq, int nmp,
+                                       const float* mp_pw, const float* mp_normal, const float* mp_min_dist, const float* mp_max_dist,
+                                       const uint8_t* mp_desc, const int32_t* mp_nobs, const uint8_t* mp_skip,
+                                       float* pw, float* normal, float* min_dist, float* max_dist, uint8_t* qdesc, uint8_t* mp_obs, uint8_t* skip) {
+    const char* who = "GatherMapPoints batch";
+    if (const int rc = covis_handle(who, m)) return rc;
+    if (!local_mp || !nq) { set_merr("%s: local_mp or nq is NULL", who); return ORBM_E_INVALID; }
+    if (T < 1 || q_stride < 1 || nmp < 1) { set_merr("%s: T, q_stride and nmp must be >= 1", who); return ORBM_E_INVALID; }
+    if (T > ORBM_LOCALPTS_MAX_FRAMES) { set_merr("%s: %d frames in one call (at most %d)", who, T, (int)ORBM_LOCALPTS_MAX_FRAMES); return ORBM_E_CAPACITY; }
+    if (nmp > ORBM_MP_MAX_BATCH) { set_merr("%s: %d MapPoints (at most %d)", who, nmp, (int)ORBM_MP_MAX_BATCH); return ORBM_E_CAPACITY; }
+    if ((((uintptr_t)mp_desc) | ((uintptr_t)qdesc)) & 15) { set_merr("%s: mp_desc and qdesc must be 16-byte aligned", who); return ORBM_E_INVALID; }
+    MHIPCHK(hipSetDevice(m->device));
+    const GatherMpParams P{q_stride, nmp, local_mp, nq, mp_pw, mp_normal, mp_min_dist, mp_max_dist, mp_desc, mp_nobs, mp_skip,
+                           pw, normal, min_dist, max_dist, qdesc, mp_obs, skip};
+    hipLaunchKernelGGL(k_gather_map_points, dim3((q_stride + 255) / 256, T), dim3(256), 0, m->stream, P);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
 }  // extern "C"

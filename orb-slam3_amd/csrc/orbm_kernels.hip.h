@@ -4941,4 +4941,269 @@ __global__ __launch_bounds__(1024) void k_kfcull_finish(int ncand, const int* __
     if (threadIdx.x == 0 && first_cull) *first_cull = sFirst == INT_MAX ? -1 : sFirst;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Covisibility votes: KeyFrame::UpdateConnections step 1 (KeyFrame.cc:474-512) and Tracking::UpdateLocalKeyFrames' keyframeCounter
+// (Tracking.cc:3964-4013): every MapPoint of a query votes for the KeyFrames that observe it, over the observation CSR of the MapPoint
+// refresh (MpObs, mp_obs_range, mp_obs_slot: the same skip rules).
+// k_covis_votes, grid = (ceil(q_stride / COVIS_WG_SLOTS), nq), 256 threads:
+//   Work split.  k_kfcull's (see its header comment): a group of 16 lanes per (query, slot), 16 entries of the MapPoint's list a round,
+//   a list of more than 64 entries taken afterwards by the whole wave, 64 a round.  A workgroup takes COVIS_WG_SLOTS = 64 slots in four
+//   passes of 16, so that its LDS table sees a few hundred votes.
+//   Pairs.  A right entry (bit 0) directly preceded by a live, non-skipped left entry of the same row adds nothing: the KeyFrame voted
+//   at the left entry (mObservations holds one entry per KeyFrame).  No state crosses a round: the right entry re-reads its predecessor.
+//   Counts.  The votes of a query pile onto a few tens of rows.  LDS = true: a direct-mapped table of COVIS_TBL (row tag, count)
+//   pairs takes them; the tag is claimed by an LDS compare-and-swap, a vote whose entry holds another row goes straight to a global
+//   atomicAdd, and at the end of the workgroup every occupied entry is flushed with one global atomicAdd.  LDS = false (A/B build only):
+//   one global atomicAdd per vote.  Integer atomics into a row that a memset in the same stream has zeroed: exact, the same on every
+//   replay.
+// k_covis_finish, one workgroup per query behind it: n_voted, max_votes, n_over and the rows with votes > 0 in ascending row order, by a
+// workgroup prefix scan over the dense row in chunks of 1024, with plain stores.
+// Nothing reads out of bounds whatever q_mp, self_row and the CSR hold.
+// ------------------------------------------------------------------------------------------------
+#define COVIS_WG_SLOTS 64
+#define COVIS_TBL 256
+struct CovisParams {
+    int q_stride, skip_bad;
+    const int* q_mp; const int* q_n; const int* self_row; const int* counts_kf; const uint8_t* kf_skip;
+};
+
+// the row entry a of the CSR votes for, or -1: skipped, the query's own row, a kf_skip row, a bad KeyFrame under skip_bad
+__device__ __forceinline__ int covis_live(const CovisParams& P, const MpObs& O, int self, int a) {
+    if (mp_obs_slot(O, P.counts_kf, a) < 0) return -1;
+    const int row = O.row[a];
+    if (row == self) return -1;                                             // mnId == mnId (KeyFrame.cc:503)
+    if (P.kf_skip && P.kf_skip[row]) return -1;
+    if (P.skip_bad && (O.flags[a] & 2)) return -1;
+    return row;
+}
+__device__ __forceinline__ int covis_entry(const CovisParams& P, const MpObs& O, int self, int a, bool first) {
+    const int row = covis_live(P, O, self, a);
+    if (row < 0) return -1;
+    if ((O.flags[a] & 1) && !first && O.row[a - 1] == row && !(O.flags[a - 1] & 1) && covis_live(P, O, self, a - 1) == row) return -1;   // voted at the left entry
+    return row;
+}
+
+template <bool LDS>
+__device__ __forceinline__ void covis_vote(int row, int* __restrict__ vq, int* sTag, int* sCnt) {
+    if (row < 0) return;
+    if (LDS) {
+        const int h = row & (COVIS_TBL - 1);
+        const int was = atomicCAS(&sTag[h], -1, row);
+        if (was == -1 || was == row) { atomicAdd(&sCnt[h], 1); return; }
+    }
+    atomicAdd(&vq[row], 1);
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_covis_votes(CovisParams P, MpObs O, int* __restrict__ votes) {
+    __shared__ int sTag[COVIS_TBL], sCnt[COVIS_TBL];
+    const int q = blockIdx.y, lane = threadIdx.x & 63, l = lane & 15;
+    if (LDS) {
+        for (int t = threadIdx.x; t < COVIS_TBL; t += 256) { sTag[t] = -1; sCnt[t] = 0; }
+        __syncthreads();
+    }
+    const int n = min(max(P.q_n[q], 0), P.q_stride);
+    const int self = P.self_row ? P.self_row[q] : -1;
+    int* vq = votes + (size_t)q * O.nkf_rows;
+    for (int pass = 0; pass < COVIS_WG_SLOTS / 16; ++pass) {
+        const int i = blockIdx.x * COVIS_WG_SLOTS + pass * 16 + (threadIdx.x >> 4);   // the group's slot
+        int o0 = 0, E = 0;
+        if (i < n) {
+            const int j = P.q_mp[(size_t)q * P.q_stride + i];
+            if ((unsigned)j < (unsigned)O.nmp) E = mp_obs_range(O, j, o0);  // an invalid MapPoint has an empty list
+        }
+        // lists of at most 64 entries: the group's 16 lanes, 16 entries a round
+        const int Es = E <= 64 ? E : 0;
+        for (int e = l; e < Es; e += 16) covis_vote<LDS>(covis_entry(P, O, self, o0 + e, e == 0), vq, sTag, sCnt);
+        // longer lists: the whole wave, 64 entries a round, one list after the other
+        for (u64 m = __ballot(E > 64 && l == 0); m; m &= m - 1) {
+            const int src = __ffsll((long long)m) - 1;                       // the first lane of the list's group
+            const int o0w = __shfl(o0, src), Ew = __shfl(E, src);
+            for (int e = lane; e < Ew; e += 64) covis_vote<LDS>(covis_entry(P, O, self, o0w + e, e == 0), vq, sTag, sCnt);
+        }
+    }
+    if (LDS) {
+        __syncthreads();
+        for (int t = threadIdx.x; t < COVIS_TBL; t += 256)
+            if (sCnt[t] > 0) atomicAdd(&vq[sTag[t]], sCnt[t]);
+    }
+}
+
+// exclusive position of this thread's flag among the workgroup's 1024 threads, and the workgroup's total; sWave holds 16 ints
+__device__ __forceinline__ int wg_scan_flag(bool flag, int* sWave, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const u64 b = __ballot(flag);
+    __syncthreads();                                                        // the previous round's readers are done
+    if (lane == 0) sWave[w] = __popcll(b);
+    __syncthreads();
+    int before = 0; total = 0;
+    for (int k = 0; k < nw; ++k) { const int c = sWave[k]; if (k < w) before += c; total += c; }
+    return before + __popcll(b & ((1ull << lane) - 1));
+}
+
+__global__ __launch_bounds__(1024) void k_covis_finish(int nkf_rows, int th, int list_cap, const int* __restrict__ votes, int* __restrict__ n_voted,
+                                                       int* __restrict__ max_votes, int* __restrict__ n_over, int* __restrict__ list_row,
+                                                       int* __restrict__ list_votes) {
+    __shared__ int sWave[16], sMax, sOver;
+    const int q = blockIdx.x;
+    const int* vq = votes + (size_t)q * nkf_rows;
+    if (threadIdx.x == 0) { sMax = 0; sOver = 0; }
+    int base = 0, mx = 0, over = 0;
+    for (int r0 = 0; r0 < nkf_rows; r0 += 1024) {
+        const int r = r0 + threadIdx.x;
+        const int v = r < nkf_rows ? vq[r] : 0;
+        int total;
+        const int pos = base + wg_scan_flag(v > 0, sWave, total);
+        if (v > 0) {
+            mx = max(mx, v); over += v >= th ? 1 : 0;
+            if (pos < list_cap) { list_row[(size_t)q * list_cap + pos] = r; list_votes[(size_t)q * list_cap + pos] = v; }
+        }
+        base += total;
+    }
+    __syncthreads();
+    if (mx > 0) atomicMax(&sMax, mx);
+    if (over) atomicAdd(&sOver, over);
+    __syncthreads();
+    if (threadIdx.x == 0) { n_voted[q] = base; max_votes[q] = sMax; n_over[q] = sOver; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Local map points: Tracking::UpdateLocalPoints (Tracking.cc:3917-3948).  Position (k, i) of a frame holds MapPoint j =
+// kf_mp[lkf_row[k]][i]; j is emitted at its FIRST position in (k, i) order (the mnTrackReferenceForFrame test of :3938-3944), and the
+// emitted indices stand in position order.  The 32-bit key of a position is k * cap + i; a chunk is LP_CHUNK consecutive keys.
+//   k_lp_mark   thread per position: atomicMin of the key into first_pos [T][nmp], which a memset in the same stream set to 0xFF.
+//   k_lp_count  workgroup per (chunk, frame), four consecutive keys per thread: the number of positions whose key equals first_pos[j].
+//   k_lp_scan   workgroup per frame: the chunk counts become exclusive offsets in place, 1024 a round; n_total and nq.
+//   k_lp_write  workgroup per (chunk, frame): the chunk's own scan again, then local_mp with plain stores; emissions at and beyond
+//               q_stride are dropped.
+// No thread walks more than four positions or 1 / 1024 of the chunk counts.  Nothing reads out of bounds whatever lkf_row and kf_mp hold.
+// ------------------------------------------------------------------------------------------------
+#define LP_CHUNK 1024
+struct LpParams {
+    int lkf_stride, nkf_rows, cap, nmp, nchunks;
+    const int* lkf_row; const int* n_lkf; const int* counts_kf; const int* kf_mp; const uint8_t* mp_valid;
+};
+// the MapPoint at position `key` of frame f, or -1
+__device__ __forceinline__ int lp_at(const LpParams& P, int f, unsigned key) {
+    const unsigned k = key / (unsigned)P.cap, i = key - k * (unsigned)P.cap;
+    if ((int)k >= min(max(P.n_lkf[f], 0), P.lkf_stride)) return -1;
+    const int row = P.lkf_row[(size_t)f * P.lkf_stride + k];
+    if ((unsigned)row >= (unsigned)P.nkf_rows) return -1;
+    if ((int)i >= min(P.counts_kf[row], P.cap)) return -1;
+    const int j = P.kf_mp[(size_t)row * P.cap + i];
+    if ((unsigned)j >= (unsigned)P.nmp) return -1;
+    if (P.mp_valid && !P.mp_valid[j]) return -1;
+    return j;
+}
+
+__global__ __launch_bounds__(256) void k_lp_mark(LpParams P, unsigned npos, unsigned* __restrict__ first_pos) {
+    const int f = blockIdx.y;
+    const unsigned key = blockIdx.x * 256u + threadIdx.x;
+    if (key >= npos) return;
+    const int j = lp_at(P, f, key);
+    if (j >= 0) atomicMin(&first_pos[(size_t)f * P.nmp + j], key);
+}
+
+// the flags of the thread's four keys (bit b = key0 + b is a first position)
+__device__ __forceinline__ unsigned lp_flags(const LpParams& P, int f, unsigned npos, const unsigned* __restrict__ first_pos, int* js) {
+    const unsigned key0 = blockIdx.x * (unsigned)LP_CHUNK + threadIdx.x * 4u;
+    unsigned fl = 0;
+    for (int b = 0; b < 4; ++b) {
+        js[b] = -1;
+        if (key0 + b >= npos || key0 + b < key0) continue;
+        const int j = lp_at(P, f, key0 + b);
+        if (j >= 0 && first_pos[(size_t)f * P.nmp + j] == key0 + b) { fl |= 1u << b; js[b] = j; }
+    }
+    return fl;
+}
+
+__global__ __launch_bounds__(256) void k_lp_count(LpParams P, unsigned npos, const unsigned* __restrict__ first_pos, int* __restrict__ chunk_cnt) {
+    __shared__ int sSum;
+    const int f = blockIdx.y;
+    if (threadIdx.x == 0) sSum = 0;
+    __syncthreads();
+    int js[4];
+    int c = __popc(lp_flags(P, f, npos, first_pos, js));
+    for (int o = 32; o; o >>= 1) c += __shfl_down(c, o);
+    if ((threadIdx.x & 63) == 0 && c) atomicAdd(&sSum, c);
+    __syncthreads();
+    if (threadIdx.x == 0) chunk_cnt[(size_t)f * P.nchunks + blockIdx.x] = sSum;
+}
+
+// inclusive scan of v over the workgroup; sWave holds blockDim.x / 64 ints; total = the workgroup's sum
+__device__ __forceinline__ int wg_scan_incl(int v, int* sWave, int& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    int s = v;
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(s, o); if (lane >= o) s += t; }
+    __syncthreads();
+    if (lane == 63) sWave[w] = s;
+    __syncthreads();
+    int before = 0; total = 0;
+    for (int k = 0; k < nw; ++k) { const int c = sWave[k]; if (k < w) before += c; total += c; }
+    return before + s;
+}
+
+__global__ __launch_bounds__(1024) void k_lp_scan(int nchunks, int q_stride, int* __restrict__ chunk_cnt, int* __restrict__ n_total, int* __restrict__ nq) {
+    __shared__ int sWave[16];
+    const int f = blockIdx.x;
+    int* c = chunk_cnt + (size_t)f * nchunks;
+    int base = 0;
+    for (int c0 = 0; c0 < nchunks; c0 += 1024) {
+        const int at = c0 + threadIdx.x;
+        const int v = at < nchunks ? c[at] : 0;
+        int total;
+        const int incl = wg_scan_incl(v, sWave, total);
+        if (at < nchunks) c[at] = base + incl - v;
+        base += total;
+    }
+    if (threadIdx.x == 0) { n_total[f] = base; nq[f] = min(base, q_stride); }
+}
+
+__global__ __launch_bounds__(256) void k_lp_write(LpParams P, unsigned npos, const unsigned* __restrict__ first_pos, const int* __restrict__ chunk_off,
+                                                  int q_stride, int* __restrict__ local_mp) {
+    __shared__ int sWave[4];
+    const int f = blockIdx.y;
+    int js[4];
+    const unsigned fl = lp_flags(P, f, npos, first_pos, js);
+    const int c = __popc(fl);
+    int total;
+    int pos = chunk_off[(size_t)f * P.nchunks + blockIdx.x] + wg_scan_incl(c, sWave, total) - c;
+    for (int b = 0; b < 4; ++b)
+        if (fl & (1u << b)) { if (pos < q_stride) local_mp[(size_t)f * q_stride + pos] = js[b]; ++pos; }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_gather_map_points: the rows SearchLocalPoints reads, gathered from the MapPoint pool by local_mp.  Thread per (frame, entry); a
+// descriptor moves as two 128-bit words.  Entries at and beyond nq[f] are not touched; an index outside [0, nmp) gets skip = 1 only.
+// ------------------------------------------------------------------------------------------------
+struct GatherMpParams {
+    int q_stride, nmp;
+    const int* local_mp; const int* nq;
+    const float* mp_pw; const float* mp_normal; const float* mp_min_dist; const float* mp_max_dist; const uint8_t* mp_desc; const int* mp_nobs;
+    const uint8_t* mp_skip;
+    float* pw; float* normal; float* min_dist; float* max_dist; uint8_t* qdesc; uint8_t* mp_obs; uint8_t* skip;
+};
+__global__ __launch_bounds__(256) void k_gather_map_points(GatherMpParams P) {
+    const int f = blockIdx.y;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= min(max(P.nq[f], 0), P.q_stride)) return;
+    const size_t o = (size_t)f * P.q_stride + e;
+    const int j = P.local_mp[o];
+    if ((unsigned)j >= (unsigned)P.nmp) { if (P.skip) P.skip[o] = 1; return; }
+    if (P.pw && P.mp_pw) { P.pw[o * 3] = P.mp_pw[(size_t)j * 3]; P.pw[o * 3 + 1] = P.mp_pw[(size_t)j * 3 + 1]; P.pw[o * 3 + 2] = P.mp_pw[(size_t)j * 3 + 2]; }
+    if (P.normal && P.mp_normal) {
+        P.normal[o * 3] = P.mp_normal[(size_t)j * 3]; P.normal[o * 3 + 1] = P.mp_normal[(size_t)j * 3 + 1]; P.normal[o * 3 + 2] = P.mp_normal[(size_t)j * 3 + 2];
+    }
+    if (P.min_dist && P.mp_min_dist) P.min_dist[o] = P.mp_min_dist[j];
+    if (P.max_dist && P.mp_max_dist) P.max_dist[o] = P.mp_max_dist[j];
+    if (P.qdesc && P.mp_desc) {
+        const uint4* s = (const uint4*)(P.mp_desc + (size_t)j * 32);
+        uint4* d = (uint4*)(P.qdesc + o * 32);
+        const uint4 a = s[0], b = s[1];
+        d[0] = a; d[1] = b;
+    }
+    if (P.mp_obs && P.mp_nobs) P.mp_obs[o] = P.mp_nobs[j] > 0 ? 1 : 0;
+    if (P.skip) P.skip[o] = P.mp_skip ? (P.mp_skip[(size_t)f * P.nmp + j] ? 1 : 0) : 0;
+}
+
 }  // namespace orbmk
