@@ -1176,6 +1176,78 @@ int orbm_gather_map_points_batch_async(orbm_t*, int T, int q_stride, const int32
                                        const uint8_t* mp_desc, const int32_t* mp_nobs, const uint8_t* mp_skip,
                                        float* pw, float* normal, float* min_dist, float* max_dist, uint8_t* qdesc, uint8_t* mp_obs, uint8_t* skip);
 
+/* ---- Pose optimisation on the device: Optimizer::PoseOptimization(Frame*) (Optimizer.cc:943-1286) for !pFrame->mpCamera2 -- pinhole,
+ * Nleft == -1, monocular (mvuRight < 0) and stereo edges in one frame -- and the bookkeeping Tracking wraps around it: the outlier discard
+ * loops (Tracking.cc:3029-3059, :3239-3266), mnMatchesInliers (:3388-3410) and step 1 of SearchLocalPoints (:3812-3832).  Nothing else
+ * of Optimizer.cc is here; the mpCamera2 branch (:1085-1152), other camera models and the inertial optimisations stay with the caller.
+ * This is the one entry point whose result is held to a TOLERANCE against the reference and not to bits: g2o sums in Eigen's order
+ * on the host's FMA unit and holds the rotation as a quaternion.  Against this library's own arithmetic (csrc/orbm_poseopt.h, which
+ * the host tests compile) the device result is bit-identical, pose included.
+ *
+ * orbm_pose_optimization (host pointers, synchronous) / orbm_pose_optimization_batch_async (device pointers except k_host and
+ * inv_level_sigma2_host, enqueue-only): one parameter list, one kernel.
+ * Rows.  Frame f of the call is block frame first + f of kps_un (mvKeysUn) and counts, rows of cap slots, as
+ * orbm_unproject_stereo_batch_async takes them; min(max(counts, 0), cap) slots are read.  uright [nframes][cap] = mvuRight, or NULL: every
+ * edge is mono.  q_mp [nframes][cap] = the frame's mvpMapPoints as indices into the MapPoint pool, an index outside [0, nmp) is NULL (the
+ * convention of orbm_covisibility_votes_batch_async); mp_pw [nmp][3] = the pool's world positions (orbm_gather_map_points_batch_async).
+ * tcw_in / tcw_out [nframes][12] = the row-major 3x4 [Rcw | tcw] of orbm_is_in_frustum_batch_async, DEVICE rows in the async form, so a
+ * replayed graph follows new poses and new match rows; tcw_out == tcw_in is allowed (SetPose).  k_host = (fx, fy, cx, cy), bf = mbf,
+ * inv_level_sigma2_host [nlevels] = mvInvLevelSigma2 hold for every frame of the call.  A slot whose octave is outside [0, nlevels) is
+ * treated as NULL (the reference would read past mvInvLevelSigma2).
+ * The rules, each restated in csrc/orbm_poseopt.h with its citation:
+ *  - edges: one per slot with a MapPoint, in slot order; information = inv_level_sigma2[octave] * I; Huber delta (float)sqrt(5.991) for a
+ *    mono and (float)sqrt(7.815) for a stereo edge, widened to double; no isBad() test.
+ *  - the < 3 rule: with fewer than 3 edges nothing is optimised: n_good = 0, the flags of the slots that hold a MapPoint are cleared and
+ *    tcw_out[f] = tcw_in[f], bit for bit.
+ *  - the float invz: the stereo error uses cam_project's `const float invz = 1.0f / z` (the double quotient rounded to float), the
+ *    stereo Jacobian the double invz, as types_six_dof_expmap.cpp:339-404 writes them; the mono error is obs - (fx * x / z + cx, ...).
+ *  - Levenberg-Marquardt as optimization_algorithm_levenberg.cpp:61-194 with the dense LDLT and SE3Quat::exp, both theta branches; at
+ *    most 10 iterations of at most 10 trials per round.
+ *  - the round-restart rule: four rounds, and EVERY round starts from the input pose (Optimizer.cc:1176 reads mTcw, which is written
+ *    after the last round only); the rounds differ in their active set and, in the last, in having no robust kernel.
+ *  - classification after each round: (float)chi2 > 5.991f / 7.815f, strictly; an edge flagged as an outlier is recomputed at the round's
+ *    final pose.  The stale-error rule: an inlier edge is read as the last computeActiveErrors left it, which after a rejected last
+ *    trial is the error at the REJECTED pose (pop() restores the estimate, not the errors).
+ *  - the < 10 rule: with fewer than 10 edges in all (active or not) only the first round runs.  A round with an empty active set
+ *    leaves the estimate at the input pose and classifies there.
+ *  - the reduction order: slot s belongs to thread s % 256 and a thread adds its slots in ascending order; the 64 lanes of a wave
+ *    combine by an xor butterfly (masks 32 ... 1), the four wave sums are added in wave order.  It is part of the contract: it fixes
+ *    the bits, and csrc/orbm_poseopt.h replays it on the host.
+ * Outputs.  outlier [nframes][cap] = mvbOutlier, written ONLY for slots that hold a MapPoint (the others keep the caller's bytes); n_corr
+ * [nframes] = nInitialCorrespondences; n_good [nframes] = the return value, nInitialCorrespondences - nBad of the last round run; tcw_out
+ * = the estimate rounded to float (Converter::toCvMat).  Both forms return ORBM_OK.
+ * The device form is ONE launch of one workgroup per frame: all four rounds, their iterations and trials run inside it with data-dependent
+ * loops; no host decision, no scratch, no atomics, nothing accumulates across replays: capturable (orbx_capture_begin) from the first call.
+ * With cap <= 1536 the frame's edges are staged in LDS once; a larger cap gathers them from the rows in every pass (same bits, slower).
+ * ORBM_E_INVALID, with nothing enqueued: a NULL array other than uright; nframes, cap, nmp or nlevels < 1; first < 0; a k_host entry or bf
+ * that is not finite.  ORBM_E_CAPACITY: nframes > ORBM_POSEOPT_MAX_FRAMES, cap > ORBM_POSEOPT_MAX_CAP, nlevels > ORBM_POSEOPT_MAX_LEVELS, nmp >
+ * ORBM_MP_MAX_BATCH, (first + nframes) * cap > 2^31 - 1.  No CPU fallback: ORBM_E_HIP without a device.
+ *
+ * orbm_discard_outliers_batch_async (device pointers, enqueue-only; there is no host form): counts [nframes], q_mp and outlier
+ * [nframes][cap] are the rows above (counts already offset by first), both IN/OUT; mp_nobs [nmp] = Observations(), mp_valid [nmp] = !isBad()
+ * (NULL = all valid).  For slot i < min(max(counts[f], 0), cap) with a MapPoint j = q_mp[f][i] inside [0, nmp):
+ *  - with discard != 0 and outlier[f][i] set (Tracking.cc:3038-3054): q_mp = -1, outlier = 0, mp_seen[f][j] = 1 (mnLastFrameSeen), and the
+ *    slot is counted in n_discarded[f];
+ *  - otherwise n_matches_map[f] counts the slot if it is not an outlier and mp_nobs[j] > 0 (:3055-3057; mnMatchesInliers of :3388-3410 with
+ *    discard == 0); then, with clear_bad != 0 and mp_valid[j] == 0, the slot becomes -1 (:3817-3819), else mp_seen[f][j] = 1 (:3826).
+ * mp_seen [nframes][nmp] is the mp_skip row of orbm_gather_map_points_batch_async; it is zeroed inside the enqueued work and takes plain
+ * byte stores of the value 1 (several slots may hit one MapPoint).  The two count rows are zeroed there too and summed by ballot popcount
+ * and one integer atomic per wave: exact, and the same on every replay.  mp_seen, n_matches_map and n_discarded may each be NULL (not
+ * wanted).  No scratch; capturable from the first call.  ORBM_E_INVALID: counts, q_mp, outlier or mp_nobs NULL; nframes, cap or nmp < 1.
+ * ORBM_E_CAPACITY: nframes > ORBM_POSEOPT_MAX_FRAMES, cap > ORBM_POSEOPT_MAX_CAP, nmp > ORBM_MP_MAX_BATCH, nframes * nmp > 2^28. */
+enum { ORBM_POSEOPT_MAX_FRAMES = 65535, ORBM_POSEOPT_MAX_CAP = 65535, ORBM_POSEOPT_MAX_LEVELS = 32 };
+int orbm_pose_optimization(orbm_t*, int nframes, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                           const float* uright, const int32_t* q_mp, int nmp, const float* mp_pw, const float* tcw_in,
+                           const float* k_host, float bf, const float* inv_level_sigma2_host, int nlevels,
+                           float* tcw_out, uint8_t* outlier, int32_t* n_corr, int32_t* n_good);
+int orbm_pose_optimization_batch_async(orbm_t*, int nframes, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                                       const float* uright, const int32_t* q_mp, int nmp, const float* mp_pw, const float* tcw_in,
+                                       const float* k_host, float bf, const float* inv_level_sigma2_host, int nlevels,
+                                       float* tcw_out, uint8_t* outlier, int32_t* n_corr, int32_t* n_good);
+int orbm_discard_outliers_batch_async(orbm_t*, int nframes, int cap, const int32_t* counts, int32_t* q_mp, uint8_t* outlier,
+                                      int nmp, const int32_t* mp_nobs, const uint8_t* mp_valid, int discard, int clear_bad,
+                                      uint8_t* mp_seen, int32_t* n_matches_map, int32_t* n_discarded);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

@@ -27,6 +27,7 @@ KFDB_MAX_ROWS, KFDB_MAX_QUERIES = 1 << 20, 65535     # include/orbm.h: ORBM_KFDB
 KFCULL_MAX_CAND, KFCULL_MAX_CAP = 65535, 65535       # include/orbm.h: ORBM_KFCULL_MAX_CAND, ORBM_KFCULL_MAX_CAP
 COVIS_MAX_QUERIES, COVIS_MAX_SLOTS, COVIS_MAX_ROWS, COVIS_MAX_VOTES = 65535, 65535, 1 << 20, 1 << 28   # include/orbm.h: ORBM_COVIS_MAX_*
 LOCALPTS_MAX_FRAMES, LOCALPTS_MAX_KFS, LOCALPTS_MAX_CAP = 65535, 65535, 65535                          # include/orbm.h: ORBM_LOCALPTS_MAX_*
+POSEOPT_MAX_FRAMES, POSEOPT_MAX_CAP, POSEOPT_MAX_LEVELS = 65535, 65535, 32                              # include/orbm.h: ORBM_POSEOPT_MAX_*
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -962,6 +963,14 @@ def _install_search():
     L.orbm_gather_map_points_batch_async.argtypes = [vp, ci, ci, vp, vp, ci,       # T, q_stride, local_mp, nq, nmp
                                                      vp, vp, vp, vp, vp, vp, vp,   # mp_pw, mp_normal, mp_min_dist, mp_max_dist, mp_desc, mp_nobs, mp_skip
                                                      vp, vp, vp, vp, vp, vp, vp]   # pw, normal, min_dist, max_dist, qdesc, mp_obs, skip
+    for name in ("orbm_pose_optimization", "orbm_pose_optimization_batch_async"):
+        getattr(L, name).argtypes = [vp, ci, ci, ci, vp, vp,                       # nframes, first, cap, kps_un, counts
+                                     vp, vp, ci, vp, vp,                           # uright, q_mp, nmp, mp_pw, tcw_in
+                                     vp, cf, vp, ci,                               # k (host), bf, inv_level_sigma2 (host), nlevels
+                                     vp, vp, vp, vp]                               # tcw_out, outlier, n_corr, n_good
+    L.orbm_discard_outliers_batch_async.argtypes = [vp, ci, ci, vp, vp, vp,        # nframes, cap, counts, q_mp, outlier
+                                                    ci, vp, vp, ci, ci,            # nmp, mp_nobs, mp_valid, discard, clear_bad
+                                                    vp, vp, vp]                    # mp_seen, n_matches_map, n_discarded
     L.orbm_is_in_frustum_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp,                 # nframes, tcw, ow, nq, q_stride, skip
                                                  vp, vp, vp, vp, ci,                         # pw, normal, min_dist, max_dist, q_shared
                                                  vp, vp, cf, cf, cf, ci,                     # k, bounds (host), bf, cos limit, log scale factor, levels
@@ -1229,6 +1238,46 @@ def _install_search():
                                                               mp_nobs, mp_skip, pw, normal, min_dist, max_dist, qdesc, mp_obs, skip),
                     "orbm_gather_map_points_batch_async")
 
+    def pose_optimization(self, kps_un, counts, uright, q_mp, mp_pw, tcw_in, K, bf, inv_level_sigma2, first=0, outlier_fill=255):
+        """Optimizer::PoseOptimization(Frame*) (Optimizer.cc:943-1286, !mpCamera2) for the frames first .. first + nframes - 1 of the block
+        kps_un [rows][cap] (KP_DTYPE) / counts [rows]: uright [nframes][cap] or None (every edge mono), q_mp [nframes][cap] = mvpMapPoints as
+        indices into mp_pw [nmp][3] (outside [0, nmp) = NULL), tcw_in [nframes][3][4] -> dict of tcw [nframes][3][4] float32, outlier
+        [nframes][cap] uint8 (slots without a MapPoint hold outlier_fill), n_corr, n_good [nframes] (include/orbm.h:
+        orbm_pose_optimization)."""
+        kp = np.ascontiguousarray(kps_un, KP_DTYPE); cnt = np.ascontiguousarray(counts, np.int32)
+        qm = np.ascontiguousarray(q_mp, np.int32); nf, cap = qm.shape
+        ur = None if uright is None else np.ascontiguousarray(uright, np.float32)
+        pw = np.ascontiguousarray(mp_pw, np.float32).reshape(-1, 3); nmp = len(pw)
+        tin = np.ascontiguousarray(tcw_in, np.float32).reshape(-1, 12)
+        k = np.ascontiguousarray(K, np.float32); ils = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        if kp.shape != (len(cnt), cap) or len(cnt) < first + nf or len(tin) != nf or (ur is not None and ur.shape != qm.shape) or len(k) != 4:
+            raise OrbError("kps_un is [rows][cap] with rows >= first + nframes; uright, q_mp are [nframes][cap]; tcw_in holds one row per frame")
+        out = {"tcw": np.zeros((max(nf, 1), 12), np.float32), "outlier": np.full((max(nf, 1), cap), outlier_fill, np.uint8),
+               "n_corr": np.zeros(max(nf, 1), np.int32), "n_good": np.zeros(max(nf, 1), np.int32)}
+        _chk(self.L.orbm_pose_optimization(self.h, nf, int(first), cap, _p(kp), _p(cnt), None if ur is None else _p(ur), _p(qm), nmp, _p(pw), _p(tin),
+                                           _p(k), float(bf), _p(ils), len(ils), _p(out["tcw"]), _p(out["outlier"]), _p(out["n_corr"]),
+                                           _p(out["n_good"])), "orbm_pose_optimization")
+        out = {key: a[:nf] for key, a in out.items()}
+        out["tcw"] = out["tcw"].reshape(-1, 3, 4)
+        return out
+
+    def pose_optimization_batch_async(self, nframes, first, cap, kps_un, counts, uright, q_mp, nmp, mp_pw, tcw_in, K, bf, inv_level_sigma2,
+                                      tcw_out, outlier, n_corr, n_good):
+        """Device form, enqueue only: every array argument is a device pointer except K = (fx, fy, cx, cy) and inv_level_sigma2, which are
+        host arrays (include/orbm.h: orbm_pose_optimization_batch_async)."""
+        k = np.ascontiguousarray(K, np.float32); ils = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        return _chk(self.L.orbm_pose_optimization_batch_async(self.h, nframes, first, cap, kps_un, counts, uright, q_mp, nmp, mp_pw, tcw_in, _p(k),
+                                                              float(bf), _p(ils), len(ils), tcw_out, outlier, n_corr, n_good),
+                    "orbm_pose_optimization_batch_async")
+
+    def discard_outliers_batch_async(self, nframes, cap, counts, q_mp, outlier, nmp, mp_nobs, mp_valid=None, discard=1, clear_bad=0, mp_seen=None,
+                                     n_matches_map=None, n_discarded=None):
+        """The outlier discard loops around PoseOptimization and step 1 of SearchLocalPoints, enqueue only: every array argument is a device
+        pointer (include/orbm.h: orbm_discard_outliers_batch_async)."""
+        return _chk(self.L.orbm_discard_outliers_batch_async(self.h, nframes, cap, counts, q_mp, outlier, nmp, mp_nobs, mp_valid, int(discard),
+                                                             int(clear_bad), mp_seen, n_matches_map, n_discarded),
+                    "orbm_discard_outliers_batch_async")
+
     def is_in_frustum_batch(self, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, q_shared, K, bounds, bf, viewing_cos_limit,
                             log_scale_factor, n_levels, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view=None):
         """Frame::isInFrustum for every frame of a batch in one launch, enqueue only: every array argument is a device pointer except K =
@@ -1250,6 +1299,9 @@ def _install_search():
     ORBmatcher.LocalPoints = local_points
     ORBmatcher.LocalPointsBatchAsync = local_points_batch_async
     ORBmatcher.GatherMapPointsBatchAsync = gather_map_points_batch_async
+    ORBmatcher.PoseOptimization = pose_optimization
+    ORBmatcher.PoseOptimizationBatchAsync = pose_optimization_batch_async
+    ORBmatcher.DiscardOutliersBatchAsync = discard_outliers_batch_async
     ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
     ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
     ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
@@ -1344,6 +1396,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_keyframe_culling", "orbm_keyframe_culling_batch_async",
             "orbm_covisibility_votes", "orbm_covisibility_votes_batch_async", "orbm_local_points", "orbm_local_points_batch_async",
             "orbm_gather_map_points_batch_async",
+            "orbm_pose_optimization", "orbm_pose_optimization_batch_async", "orbm_discard_outliers_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

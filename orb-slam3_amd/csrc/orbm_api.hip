@@ -3206,4 +3206,116 @@ int orbm_gather_map_points_batch_async(orbm_t* m, int T, int q_stride, const int
     return ORBM_OK;
 }
 
+// ---- Pose optimisation and the bookkeeping around it: Optimizer::PoseOptimization(Frame*) and the discard loops of Tracking ----
+// the argument tests the host and the device form share; fills the kernel's parameter block (rows still unset)
+static int poseopt_args(const char* who, orbm_t* m, int nframes, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                        const int32_t* q_mp, int nmp, const float* mp_pw, const float* tcw_in, const float* k_host, float bf,
+                        const float* ils2_host, int nlevels, float* tcw_out, uint8_t* outlier, int32_t* n_corr, int32_t* n_good, PoseOptParams& P) {
+    if (const int rc = covis_handle(who, m)) return rc;
+    const struct { const void* p; const char* name; } req[] = {
+        {kps_un, "kps_un"}, {counts, "counts"}, {q_mp, "q_mp"}, {mp_pw, "mp_pw"}, {tcw_in, "tcw_in"}, {k_host, "k_host"},
+        {ils2_host, "inv_level_sigma2_host"}, {tcw_out, "tcw_out"}, {outlier, "outlier"}, {n_corr, "n_corr"}, {n_good, "n_good"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (nframes < 1 || cap < 1 || nmp < 1 || nlevels < 1 || first < 0) {
+        set_merr("%s: nframes, cap, nmp and nlevels must be >= 1 and first >= 0", who);
+        return ORBM_E_INVALID;
+    }
+    if (!std::isfinite(bf) || !std::isfinite(k_host[0]) || !std::isfinite(k_host[1]) || !std::isfinite(k_host[2]) || !std::isfinite(k_host[3])) {
+        set_merr("%s: k_host or bf is not finite", who);
+        return ORBM_E_INVALID;
+    }
+    if (nframes > ORBM_POSEOPT_MAX_FRAMES || cap > ORBM_POSEOPT_MAX_CAP) {
+        set_merr("%s: %d frames of %d slots (at most %d of %d)", who, nframes, cap, (int)ORBM_POSEOPT_MAX_FRAMES, (int)ORBM_POSEOPT_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (nlevels > ORBM_POSEOPT_MAX_LEVELS) { set_merr("%s: %d pyramid levels (at most %d)", who, nlevels, (int)ORBM_POSEOPT_MAX_LEVELS); return ORBM_E_CAPACITY; }
+    if (nmp > ORBM_MP_MAX_BATCH) { set_merr("%s: %d MapPoints (at most %d)", who, nmp, (int)ORBM_MP_MAX_BATCH); return ORBM_E_CAPACITY; }
+    if ((long long)(first + (long long)nframes) * cap > INT_MAX) { set_merr("%s: (first + nframes) * cap exceeds 2^31 - 1", who); return ORBM_E_CAPACITY; }
+    static_assert(ORBM_POSEOPT_MAX_LEVELS == PO_MAX_LEVELS, "the kernel's level table");
+    P = PoseOptParams{};
+    P.first = first; P.cap = cap; P.nmp = nmp; P.nlevels = nlevels; P.bf = bf;
+    for (int i = 0; i < 4; ++i) P.k[i] = k_host[i];
+    for (int i = 0; i < PO_MAX_LEVELS; ++i) P.ils2[i] = i < nlevels ? ils2_host[i] : 0.0f;
+    return ORBM_OK;
+}
+
+static int poseopt_launch(orbm_t* m, int nframes, PoseOptParams& P, const orbm_kp_t* kps_un, const int32_t* counts, const float* uright,
+                          const int32_t* q_mp, const float* mp_pw, const float* tcw_in, float* tcw_out, uint8_t* outlier, int32_t* n_corr,
+                          int32_t* n_good) {
+    P.kps_un = (const KpIn*)kps_un; P.counts = counts; P.uright = uright; P.q_mp = q_mp; P.mp_pw = mp_pw; P.tcw_in = tcw_in;
+    P.tcw_out = tcw_out; P.outlier = outlier; P.n_corr = n_corr; P.n_good = n_good;
+    if (P.cap <= PO_LDS_CAP) hipLaunchKernelGGL(k_pose_opt<true>, dim3(nframes), dim3(PO_THREADS), 0, m->stream, P);
+    else hipLaunchKernelGGL(k_pose_opt<false>, dim3(nframes), dim3(PO_THREADS), 0, m->stream, P);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_pose_optimization_batch_async(orbm_t* m, int nframes, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                                       const float* uright, const int32_t* q_mp, int nmp, const float* mp_pw, const float* tcw_in,
+                                       const float* k_host, float bf, const float* inv_level_sigma2_host, int nlevels,
+                                       float* tcw_out, uint8_t* outlier, int32_t* n_corr, int32_t* n_good) {
+    PoseOptParams P;
+    const int rc = poseopt_args("PoseOptimization batch", m, nframes, first, cap, kps_un, counts, q_mp, nmp, mp_pw, tcw_in, k_host, bf,
+                                inv_level_sigma2_host, nlevels, tcw_out, outlier, n_corr, n_good, P);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    return poseopt_launch(m, nframes, P, kps_un, counts, uright, q_mp, mp_pw, tcw_in, tcw_out, outlier, n_corr, n_good);
+}
+
+int orbm_pose_optimization(orbm_t* m, int nframes, int first, int cap, const orbm_kp_t* kps_un, const int32_t* counts,
+                           const float* uright, const int32_t* q_mp, int nmp, const float* mp_pw, const float* tcw_in,
+                           const float* k_host, float bf, const float* inv_level_sigma2_host, int nlevels,
+                           float* tcw_out, uint8_t* outlier, int32_t* n_corr, int32_t* n_good) {
+    PoseOptParams P;
+    int rc = poseopt_args("PoseOptimization", m, nframes, first, cap, kps_un, counts, q_mp, nmp, mp_pw, tcw_in, k_host, bf, inv_level_sigma2_host,
+                          nlevels, tcw_out, outlier, n_corr, n_good, P);
+    if (rc) return rc;
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t rows = (size_t)nframes * cap;
+    DevBuf dk, dc, du, dq, dp, dt, dout, dcnt, dto;
+    arena_reset(m);
+    UP(dk, kps_un + (size_t)first * cap, sizeof(KpIn) * rows); UP(dc, counts + first, sizeof(int32_t) * nframes);   // the block's rows first .. first + nframes - 1
+    if (uright) UP(du, uright, sizeof(float) * rows);
+    UP(dq, q_mp, sizeof(int32_t) * rows); UP(dp, mp_pw, sizeof(float) * 3 * (size_t)nmp); UP(dt, tcw_in, sizeof(float) * 12 * nframes);
+    UPIO(dout, outlier, rows);                                              // slots without a MapPoint keep the caller's bytes
+    AL(dcnt, sizeof(int32_t) * 2 * (size_t)nframes); AL(dto, sizeof(float) * 12 * nframes);
+    ARENA_FLUSH(m);
+    P.first = 0;
+    int32_t* cnt = dcnt.as<int32_t>();
+    rc = poseopt_launch(m, nframes, P, (const orbm_kp_t*)dk.ptr(), dc.as<int32_t>(), uright ? du.as<float>() : nullptr, dq.as<int32_t>(), dp.as<float>(),
+                        dt.as<float>(), dto.as<float>(), dout.as<uint8_t>(), cnt, cnt + nframes);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    const int32_t* hc = (const int32_t*)dcnt.host();
+    memcpy(n_corr, hc, sizeof(int32_t) * nframes); memcpy(n_good, hc + nframes, sizeof(int32_t) * nframes);
+    memcpy(tcw_out, dto.host(), sizeof(float) * 12 * nframes); memcpy(outlier, dout.host(), rows);
+    return ORBM_OK;
+}
+
+int orbm_discard_outliers_batch_async(orbm_t* m, int nframes, int cap, const int32_t* counts, int32_t* q_mp, uint8_t* outlier,
+                                      int nmp, const int32_t* mp_nobs, const uint8_t* mp_valid, int discard, int clear_bad,
+                                      uint8_t* mp_seen, int32_t* n_matches_map, int32_t* n_discarded) {
+    const char* who = "DiscardOutliers batch";
+    if (const int rc = covis_handle(who, m)) return rc;
+    if (!counts || !q_mp || !outlier || !mp_nobs) { set_merr("%s: counts, q_mp, outlier or mp_nobs is NULL", who); return ORBM_E_INVALID; }
+    if (nframes < 1 || cap < 1 || nmp < 1) { set_merr("%s: nframes, cap and nmp must be >= 1", who); return ORBM_E_INVALID; }
+    if (nframes > ORBM_POSEOPT_MAX_FRAMES || cap > ORBM_POSEOPT_MAX_CAP) {
+        set_merr("%s: %d frames of %d slots (at most %d of %d)", who, nframes, cap, (int)ORBM_POSEOPT_MAX_FRAMES, (int)ORBM_POSEOPT_MAX_CAP);
+        return ORBM_E_CAPACITY;
+    }
+    if (nmp > ORBM_MP_MAX_BATCH) { set_merr("%s: %d MapPoints (at most %d)", who, nmp, (int)ORBM_MP_MAX_BATCH); return ORBM_E_CAPACITY; }
+    if ((long long)nframes * nmp > ORBM_COVIS_MAX_VOTES) { set_merr("%s: %d frames x %d MapPoints of seen flags (at most 2^28)", who, nframes, nmp); return ORBM_E_CAPACITY; }
+    MHIPCHK(hipSetDevice(m->device));
+    // the rows start from zero inside the enqueued work: a replayed graph replays the memsets
+    if (mp_seen) MHIPCHK(hipMemsetAsync(mp_seen, 0, (size_t)nframes * nmp, m->stream));
+    if (n_matches_map) MHIPCHK(hipMemsetAsync(n_matches_map, 0, sizeof(int32_t) * nframes, m->stream));
+    if (n_discarded) MHIPCHK(hipMemsetAsync(n_discarded, 0, sizeof(int32_t) * nframes, m->stream));
+    const DiscardParams P{cap, nmp, discard ? 1 : 0, clear_bad ? 1 : 0, counts, q_mp, outlier, mp_nobs, mp_valid, mp_seen, n_matches_map, n_discarded};
+    hipLaunchKernelGGL(k_discard_outliers, dim3((cap + 255) / 256, nframes), dim3(256), 0, m->stream, P);
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
 }  // extern "C"

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#define PO_FN __host__ __device__ static inline
+#include "orbm_poseopt.h"          // the arithmetic of k_pose_opt, shared with the host tests
 
 namespace orbmk {
 
@@ -5204,6 +5206,215 @@ __global__ __launch_bounds__(256) void k_gather_map_points(GatherMpParams P) {
     }
     if (P.mp_obs && P.mp_nobs) P.mp_obs[o] = P.mp_nobs[j] > 0 ? 1 : 0;
     if (P.skip) P.skip[o] = P.mp_skip ? (P.mp_skip[(size_t)f * P.nmp + j] ? 1 : 0) : 0;
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_pose_opt: Optimizer::PoseOptimization(Frame*) (Optimizer.cc:943-1286, !mpCamera2) for one frame per workgroup of 256 threads.  The
+// arithmetic, the LM state machine, the four rounds and the REDUCTION ORDER are those of orbm_poseopt.h, which the host tests compile
+// too; this file only supplies the context: where a thread's edges live and how 256 partial sums become one.
+//   edges    slot s belongs to thread s % 256.  With cap <= PO_LDS_CAP (LDS = true) a slot's observation, point, weight, kind and state
+//            are gathered once through q_mp into LDS (seven float planes and two byte planes, lane-consecutive: no bank conflicts) and
+//            every later pass reads them there.  Past PO_LDS_CAP (LDS = false) every pass gathers the slot again from the global rows
+//            (L2 hits after the first pass) and the state lives in the `outlier` row itself, which only the owning thread touches.
+//            Registers were not used for the edges: the solve path already holds the 28 partial sums, three poses, H, b and x as doubles.
+//   sums     po_dev_reduce: xor butterfly over the wave by __shfl_xor (a double moves as two 32-bit halves), lane 0 of each wave stores
+//            to LDS, every thread adds the four wave sums in wave order.  Every thread therefore holds the same bits, the 6x6 solve and
+//            every LM decision are computed redundantly by all 256 threads, and each data-dependent loop is uniform over the
+//            workgroup: no broadcast, no divergence, and the barriers inside the loops are reached by everyone.
+//   results  plain vector stores by the owning thread (flags) and by thread 0 (pose, counts).  One launch, no scratch, no atomics.
+// A slot holds an edge when i < min(counts, cap), q_mp is inside [0, nmp) and the octave inside [0, nlevels).
+// ------------------------------------------------------------------------------------------------
+#define PO_LDS_CAP 1536
+#define PO_MAX_LEVELS 32
+struct PoseOptParams {
+    int first, cap, nmp, nlevels;
+    float k[4], bf, ils2[PO_MAX_LEVELS];
+    const KpIn* kps_un; const int* counts; const float* uright; const int* q_mp; const float* mp_pw; const float* tcw_in;
+    float* tcw_out; uint8_t* outlier; int* n_corr; int* n_good;
+};
+
+template <int NACC>
+__device__ __forceinline__ void po_dev_reduce(double* v, double* sRed) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) {
+        double x = v[a];
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) x = x + __shfl_xor(x, m, 64);
+        v[a] = x;
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int a = 0; a < NACC; ++a) sRed[wv * PO_NACC + a] = v[a];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int a = 0; a < NACC; ++a) v[a] = ((sRed[a] + sRed[PO_NACC + a]) + sRed[2 * PO_NACC + a]) + sRed[3 * PO_NACC + a];
+    __syncthreads();
+}
+
+__device__ __forceinline__ int po_dev_count(int c, int* sCnt) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m, 64);
+    if ((threadIdx.x & 63) == 0) sCnt[threadIdx.x >> 6] = c;
+    __syncthreads();
+    const int t = sCnt[0] + sCnt[1] + sCnt[2] + sCnt[3];
+    __syncthreads();
+    return t;
+}
+
+template <bool LDS>
+struct PoDevCtx {
+    PoCam C;
+    int n, nmp, nlevels;
+    float* sE; uint8_t* sState; uint8_t* sStereo; const float* sIls2; double* sRed; int* sCnt;    // LDS
+    const KpIn* kp; const float* ur; const int* qmp; const float* pw; uint8_t* gState;           // the frame's global rows
+
+    // the slot's edge from the global rows; false = no edge
+    __device__ __forceinline__ bool gather(int s, PoEdge& e) const {
+        const int j = qmp[s];
+        if ((unsigned)j >= (unsigned)nmp) return false;
+        const KpIn& k = kp[s];
+        return po_make_edge(k.x, k.y, k.octave, ur ? ur + s : nullptr, pw + 3 * (size_t)j, sIls2, nlevels, e);
+    }
+    // the slot's edge and state for a pass; PO_NONE = no edge
+    __device__ __forceinline__ int fetch(int s, PoEdge& e) const {
+        if (LDS) {
+            const int st = sState[s];
+            if (st == PO_NONE) return st;
+            e.u = (double)sE[s]; e.v = (double)sE[PO_LDS_CAP + s]; e.ur = (double)sE[2 * PO_LDS_CAP + s];
+            e.X = (double)sE[3 * PO_LDS_CAP + s]; e.Y = (double)sE[4 * PO_LDS_CAP + s]; e.Z = (double)sE[5 * PO_LDS_CAP + s];
+            e.w = (double)sE[6 * PO_LDS_CAP + s]; e.stereo = sStereo[s] != 0;
+            return st;
+        }
+        if (!gather(s, e)) return PO_NONE;
+        return gState[s] ? PO_OUTLIER : PO_INLIER;
+    }
+    __device__ __forceinline__ void system(const double T[12], bool kernel, double acc[PO_NACC]) const {
+#pragma unroll
+        for (int a = 0; a < PO_NACC; ++a) acc[a] = 0.0;
+        for (int s = threadIdx.x; s < n; s += PO_THREADS) {
+            PoEdge e;
+            if (fetch(s, e) == PO_INLIER) po_edge_system(C, T, e, kernel, acc);
+        }
+        po_dev_reduce<PO_NACC>(acc, sRed);
+    }
+    __device__ __forceinline__ double chi(const double T[12], bool kernel) const {
+        double c = 0.0;
+        for (int s = threadIdx.x; s < n; s += PO_THREADS) {
+            PoEdge e;
+            if (fetch(s, e) == PO_INLIER) c = c + po_edge_chi(C, T, e, kernel);
+        }
+        po_dev_reduce<1>(&c, sRed);
+        return c;
+    }
+    __device__ __forceinline__ int classify(const double Terr[12], const double T[12]) const {
+        int nBad = 0;
+        for (int s = threadIdx.x; s < n; s += PO_THREADS) {
+            PoEdge e;
+            const int st = fetch(s, e);
+            if (st == PO_NONE) continue;
+            const int ns = po_edge_classify(C, Terr, T, e, st);
+            if (LDS) sState[s] = (uint8_t)ns; else gState[s] = (uint8_t)ns;
+            nBad += ns == PO_OUTLIER;
+        }
+        return po_dev_count(nBad, sCnt);
+    }
+};
+
+template <bool LDS>
+__global__ __launch_bounds__(256) void k_pose_opt(PoseOptParams P) {
+    __shared__ float sE[LDS ? 7 * PO_LDS_CAP : 1];
+    __shared__ uint8_t sState[LDS ? PO_LDS_CAP : 1], sStereo[LDS ? PO_LDS_CAP : 1];
+    __shared__ float sIls2[PO_MAX_LEVELS];
+    __shared__ double sRed[4 * PO_NACC];
+    __shared__ int sCnt[4];
+    const int f = blockIdx.x, tid = threadIdx.x;
+    const size_t in0 = (size_t)(P.first + f) * P.cap, out0 = (size_t)f * P.cap;
+    int n = min(max(P.counts[P.first + f], 0), P.cap);
+    if (LDS) n = min(n, PO_LDS_CAP);                                       // the host picks LDS = true only for cap <= PO_LDS_CAP
+    float tin[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) tin[i] = P.tcw_in[12 * (size_t)f + i];
+#pragma unroll
+    for (int i = 0; i < PO_MAX_LEVELS; ++i) if (tid == i) sIls2[i] = P.ils2[i];
+    __syncthreads();
+    PoDevCtx<LDS> ctx;
+    ctx.C = PoCam{(double)P.k[0], (double)P.k[1], (double)P.k[2], (double)P.k[3], (double)P.bf};
+    ctx.n = n; ctx.nmp = P.nmp; ctx.nlevels = min(P.nlevels, PO_MAX_LEVELS);
+    ctx.sE = sE; ctx.sState = sState; ctx.sStereo = sStereo; ctx.sIls2 = sIls2; ctx.sRed = sRed; ctx.sCnt = sCnt;
+    ctx.kp = P.kps_un + in0; ctx.ur = P.uright ? P.uright + out0 : nullptr; ctx.qmp = P.q_mp + out0; ctx.pw = P.mp_pw; ctx.gState = P.outlier + out0;
+    // the edges: every slot with a MapPoint starts as an inlier, mvbOutlier[i] = false (Optimizer.cc:1011, :1046)
+    int cnt = 0;
+    for (int s = tid; s < n; s += PO_THREADS) {
+        PoEdge e;
+        const bool has = ctx.gather(s, e);
+        if (LDS) {
+            sState[s] = has ? PO_INLIER : PO_NONE;
+            if (has) {
+                sE[s] = (float)e.u; sE[PO_LDS_CAP + s] = (float)e.v; sE[2 * PO_LDS_CAP + s] = (float)e.ur;
+                sE[3 * PO_LDS_CAP + s] = (float)e.X; sE[4 * PO_LDS_CAP + s] = (float)e.Y; sE[5 * PO_LDS_CAP + s] = (float)e.Z;
+                sE[6 * PO_LDS_CAP + s] = (float)e.w; sStereo[s] = e.stereo ? 1 : 0;
+            }
+        } else if (has) {
+            ctx.gState[s] = 0;
+        }
+        cnt += has ? 1 : 0;
+    }
+    const int nCorr = po_dev_count(cnt, sCnt);                             // its barriers also publish the LDS planes (each slot stays with one thread anyway)
+    double T[12];
+    int nGood = 0;
+    if (nCorr >= 3) {
+        double T0[12];
+        po_pose_from_float(tin, T0);
+        nGood = po_four_rounds(ctx, nCorr, T0, T);
+    }
+    if (LDS)
+        for (int s = tid; s < n; s += PO_THREADS)
+            if (sState[s] != PO_NONE) P.outlier[out0 + s] = sState[s] == PO_OUTLIER ? 1 : 0;
+    if (tid == 0) {
+#pragma unroll
+        for (int i = 0; i < 12; ++i) P.tcw_out[12 * (size_t)f + i] = nCorr >= 3 ? (float)T[i] : tin[i];
+        P.n_corr[f] = nCorr; P.n_good[f] = nGood;
+    }
+}
+
+// k_discard_outliers: the loops around PoseOptimization for one (frame, slot) per thread.  With discard and the slot's outlier flag
+// set (Tracking.cc:3038-3054, :3246-3262): q_mp = -1, outlier = 0, mp_seen = 1, counted in n_discarded.  Otherwise the slot counts in
+// n_matches_map when it is no outlier and mp_nobs > 0 (:3055-3057; mnMatchesInliers of :3388-3410 with discard == 0), and step 1 of
+// SearchLocalPoints (:3812-3832) follows: a bad MapPoint leaves the slot when clear_bad is set, any other is marked seen.  mp_seen takes
+// plain byte stores of 1 (several slots may hit one MapPoint); the counts go by ballot popcount and one integer atomic per wave into
+// rows a memset in the same stream zeroed, as k_frustum_batch.
+struct DiscardParams {
+    int cap, nmp, discard, clear_bad;
+    const int* counts; int* q_mp; uint8_t* outlier; const int* mp_nobs; const uint8_t* mp_valid;
+    uint8_t* mp_seen; int* n_matches_map; int* n_discarded;
+};
+__global__ __launch_bounds__(256) void k_discard_outliers(DiscardParams P) {
+    const int f = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int n = min(max(P.counts[f], 0), P.cap);
+    bool match = false, gone = false;
+    if (i < n) {
+        const size_t o = (size_t)f * P.cap + i;
+        const int j = P.q_mp[o];
+        if ((unsigned)j < (unsigned)P.nmp) {
+            const bool out = P.outlier[o] != 0;
+            if (P.discard && out) {
+                P.q_mp[o] = -1; P.outlier[o] = 0;
+                if (P.mp_seen) P.mp_seen[(size_t)f * P.nmp + j] = 1;
+                gone = true;
+            } else {
+                match = !out && P.mp_nobs[j] > 0;
+                if (P.clear_bad && P.mp_valid && !P.mp_valid[j]) P.q_mp[o] = -1;
+                else if (P.mp_seen) P.mp_seen[(size_t)f * P.nmp + j] = 1;
+            }
+        }
+    }
+    const u64 bm = __ballot(match), bg = __ballot(gone);
+    if ((threadIdx.x & 63) == 0) {
+        if (P.n_matches_map && bm) atomicAdd(&P.n_matches_map[f], __popcll(bm));
+        if (P.n_discarded && bg) atomicAdd(&P.n_discarded[f], __popcll(bg));
+    }
 }
 
 }  // namespace orbmk
