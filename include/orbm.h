@@ -1248,6 +1248,83 @@ int orbm_discard_outliers_batch_async(orbm_t*, int nframes, int cap, const int32
                                       int nmp, const int32_t* mp_nobs, const uint8_t* mp_valid, int discard, int clear_bad,
                                       uint8_t* mp_seen, int32_t* n_matches_map, int32_t* n_discarded);
 
+/* ---- CreateNewMapPoints behind M10: step 6 of LocalMapping::CreateNewMapPoints (LocalMapping.cc:609-892) for every match M10 left in
+ * matches12 -- the parallax tests, the linear triangulation or UnprojectStereo_, the two reprojection tests, the scale-consistency test, the
+ * cross-pair rule and the order in which the reference creates its MapPoints.  Pinhole cameras, NLeft == -1, !mpCamera2; the
+ * baseline / median-depth tests (:552-578) stay with the caller: a pair that fails them is simply not passed.  new MapPoint, AddObservation and
+ * AddMapPoint stay with the caller too, who walks `order`.
+ * x3d is held to a TOLERANCE against the reference and is NOT bit-identical to cv::SVD: the null vector of the 4x4 (:768) comes from a
+ * one-sided Jacobi in float32 (csrc/orbm_triangulate.h), whose sign-aligned unit vector lies within C * eps32 * sigma1 / (sigma3 - sigma4) of
+ * the float64 one (C and its measurement: tests/triangulate_results.py, profiles/NOTES.md).  On the UnprojectStereo_ branches there is no SVD
+ * and x3d is the reference's float expression.  Against this library's own arithmetic (the header, which the host tests compile) the device
+ * result is bit-identical, x3d included.
+ *
+ * orbm_triangulate_new_points_batch_async (device pointers except group_start_host and the *_host tables, enqueue-only) /
+ * orbm_triangulate_new_points (the same list behind `space`: ORBM_HOST = every array is a host array, ORBM_DEVICE = device arrays as in the
+ * async form; synchronous in both): one parameter list, the same two kernels.
+ * Groups.  Group g is ONE current KeyFrame: its pairs are [group_start_host[g], group_start_host[g + 1]), they share one row1 and are walked
+ * in the order given (the order of vpNeighKFs).  group_start_host [ngroups + 1] is a HOST array in both forms, runs from 0 to npairs and is
+ * copied into the launch (a captured graph keeps it).  A group whose pairs do not share one row1 is refused: ORBM_E_INVALID where row1 is
+ * readable (ORBM_HOST); in the device forms such a group creates nothing and its reason rows read 15.
+ * Pools as in orbm_search_for_triangulation_batch_async: pool 1 has nrows1 rows of cap1 slots -- kps_un1 (mvKeysUn), kps1 (mvKeys, read only
+ * by UnprojectStereo_; NULL = kps_un1), counts1 [nrows1], uright1 (mvuRight; NULL = no stereo feature), depth1 (mvDepth; NULL = -1), tcw1
+ * [nrows1][12] = the row-major 3x4 [Rcw | tcw], ow1 [nrows1][3] = GetCameraCenter --, pool 2 the same with nrows2 / cap2; one pool may be
+ * passed twice.  row1 / row2 [npairs] and matches12 [npairs][cap1] are M10's arrays as they are.  k1_host / k2_host = (fx, fy, cx, cy,
+ * invfx, invfy) of the current KeyFrames / the neighbours, mb1 / mbf1 = the current KeyFrame's mb / mbf, mb2 = the neighbours' mb;
+ * scale_factors*_host = mvScaleFactors, level_sigma2_*_host = mvLevelSigma2 [nlevels]; ratio_factor = 1.5f * mfScaleFactor; th_far =
+ * mThFarPoints, <= 0: mbFarPoints is off.
+ * The rules, each restated in csrc/orbm_triangulate.h with its citation:
+ *  - a match is idx2 = matches12[p][idx1] with idx1 < the row-1 count and 0 <= idx2 < the row-2 count; anything else in the entry (-1,
+ *    garbage below -1 or past the count) and a row1 / row2 outside its pool read as "no match" and are never dereferenced.
+ *  - bStereo = uright >= 0; `if (bStereo1) ... else if (bStereo2)` as written: cosParallaxStereo2 is computed only when KeyFrame 1's feature
+ *    is not stereo; cos(2 * atan2(mb / 2, depth)) in double, stored to float.
+ *  - triangulate when cosParallaxRays < cosParallaxStereo, > 0 and (either feature stereo or < 0.9998); else UnprojectStereo_ of KeyFrame 1,
+ *    else of KeyFrame 2 (mvKeys; zeros for depth <= 0), else reject.  x3D_h(3) == 0 rejects.
+ *  - z1 <= 0, z2 <= 0 reject; invz = 1.0 / z stored to float; mono error through project() (fx * x / z + cx), stereo error fx * x * invz + cx.
+ *    The mbf1 rule: u2_r of the SECOND KeyFrame subtracts mbf1 * invz2 -- KeyFrame 1's mbf, as :861 reads mpCurrentKeyFrame->mbf.
+ *    chi2 > 5.991 * sigma2 (mono) / > 7.8 * sigma2 (stereo) against the double product.
+ *  - dist == 0 rejects; with th_far > 0, dist >= th_far rejects; ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave *
+ *    ratio_factor rejects.  An octave outside [0, nlevels) rejects and indexes no table.
+ *  - the cross-pair rule: per idx1 the pairs of the group are tried in order and the FIRST pair whose match passes every gate wins; a later
+ *    pair's match for that idx1 is dropped (reason 4), as the reference's search of a later neighbour skips a feature that already holds a
+ *    MapPoint.  A pair whose match fails leaves idx1 free for the next pair.
+ * Outputs.  won_pair [ngroups][cap1] = the winning pair's index in [0, npairs) or -1, won_idx2 = its idx2 or -1, x3d [ngroups][cap1][3] =
+ * the new point (zeros where won_pair is -1); reason [npairs][cap1] (optional, NULL = not wanted) = the exit of every (pair, idx1), the
+ * values of enum TriReason in csrc/orbm_triangulate.h (0..2 success by branch, 3 no match, 4 taken by an earlier pair, 5..14 the gates);
+ * ncreated [npairs] = the MapPoints pair p creates; order [ngroups][cap1] = the group's winning idx1 in the reference's creation order (pair
+ * by pair, ascending idx1 inside a pair), -1 past ntotal [ngroups].  Every slot of every output row is written by every call; counts start
+ * from zero inside the enqueued work, nothing is atomic, a replayed graph repeats its result.  No scratch, no allocation: capturable
+ * (orbx_capture_begin) from the first call.  Both forms return ORBM_OK.
+ * ORBM_E_INVALID, with nothing enqueued: a NULL array other than kps1 / kps2, uright*, depth* and reason; ngroups, npairs, nrows*, cap* or
+ * nlevels < 1; group_start_host not starting at 0, not ending at npairs or not monotone; a ratio_factor that is not finite; a `space` that is
+ * neither.  ORBM_E_CAPACITY: cap1 or cap2 > ORBM_TRI_MAX_CAP, npairs > ORBM_TRI_MAX_PAIRS, a group of more than ORBM_TRI_MAX_GROUP_PAIRS pairs,
+ * nlevels > ORBM_TRI_MAX_LEVELS.  No CPU fallback: ORBM_E_HIP without a device. */
+enum { ORBM_TRI_MAX_CAP = 65535, ORBM_TRI_MAX_PAIRS = 65535, ORBM_TRI_MAX_GROUP_PAIRS = 64, ORBM_TRI_MAX_LEVELS = 32 };
+int orbm_triangulate_new_points_batch_async(orbm_t*, int ngroups, const int32_t* group_start_host, int npairs,
+                                            int nrows1, int cap1, const orbm_kp_t* kps_un1, const orbm_kp_t* kps1, const int32_t* counts1,
+                                            const float* uright1, const float* depth1, const float* tcw1, const float* ow1,
+                                            int nrows2, int cap2, const orbm_kp_t* kps_un2, const orbm_kp_t* kps2, const int32_t* counts2,
+                                            const float* uright2, const float* depth2, const float* tcw2, const float* ow2,
+                                            const int32_t* row1, const int32_t* row2, const int32_t* matches12,
+                                            const float* k1_host, const float* k2_host, float mb1, float mbf1, float mb2,
+                                            const float* scale_factors1_host, const float* level_sigma2_1_host,
+                                            const float* scale_factors2_host, const float* level_sigma2_2_host,
+                                            int nlevels, float ratio_factor, float th_far,
+                                            int32_t* won_pair, int32_t* won_idx2, float* x3d, uint8_t* reason, int32_t* ncreated,
+                                            int32_t* order, int32_t* ntotal);
+int orbm_triangulate_new_points(orbm_t*, int space, int ngroups, const int32_t* group_start_host, int npairs,
+                                int nrows1, int cap1, const orbm_kp_t* kps_un1, const orbm_kp_t* kps1, const int32_t* counts1,
+                                const float* uright1, const float* depth1, const float* tcw1, const float* ow1,
+                                int nrows2, int cap2, const orbm_kp_t* kps_un2, const orbm_kp_t* kps2, const int32_t* counts2,
+                                const float* uright2, const float* depth2, const float* tcw2, const float* ow2,
+                                const int32_t* row1, const int32_t* row2, const int32_t* matches12,
+                                const float* k1_host, const float* k2_host, float mb1, float mbf1, float mb2,
+                                const float* scale_factors1_host, const float* level_sigma2_1_host,
+                                const float* scale_factors2_host, const float* level_sigma2_2_host,
+                                int nlevels, float ratio_factor, float th_far,
+                                int32_t* won_pair, int32_t* won_idx2, float* x3d, uint8_t* reason, int32_t* ncreated,
+                                int32_t* order, int32_t* ntotal);
+
 /* M15 Frame::ComputeStereoMatches (Frame.cc:1027-1276).  left/right are orbx_t* extractor handles (include/orbx.h)
  * on the same device whose LAST call produced the two keypoint sets: their device-resident pyramids supply the
  * 11x11 SAD windows (mvImagePyramid, include/ORBextractor.h:83).  frame_l/frame_r select the batch slot.

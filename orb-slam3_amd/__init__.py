@@ -28,6 +28,7 @@ KFCULL_MAX_CAND, KFCULL_MAX_CAP = 65535, 65535       # include/orbm.h: ORBM_KFCU
 COVIS_MAX_QUERIES, COVIS_MAX_SLOTS, COVIS_MAX_ROWS, COVIS_MAX_VOTES = 65535, 65535, 1 << 20, 1 << 28   # include/orbm.h: ORBM_COVIS_MAX_*
 LOCALPTS_MAX_FRAMES, LOCALPTS_MAX_KFS, LOCALPTS_MAX_CAP = 65535, 65535, 65535                          # include/orbm.h: ORBM_LOCALPTS_MAX_*
 POSEOPT_MAX_FRAMES, POSEOPT_MAX_CAP, POSEOPT_MAX_LEVELS = 65535, 65535, 32                              # include/orbm.h: ORBM_POSEOPT_MAX_*
+TRI_MAX_CAP, TRI_MAX_PAIRS, TRI_MAX_GROUP_PAIRS, TRI_MAX_LEVELS = 65535, 65535, 64, 32                  # include/orbm.h: ORBM_TRI_MAX_*
 TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30          # ORBmatcher.cc:36-38
 
 EXPORTS = [
@@ -971,6 +972,14 @@ def _install_search():
     L.orbm_discard_outliers_batch_async.argtypes = [vp, ci, ci, vp, vp, vp,        # nframes, cap, counts, q_mp, outlier
                                                     ci, vp, vp, ci, ci,            # nmp, mp_nobs, mp_valid, discard, clear_bad
                                                     vp, vp, vp]                    # mp_seen, n_matches_map, n_discarded
+    _tri = [ci, vp, ci,                                                            # ngroups, group_start (host), npairs
+            ci, ci, vp, vp, vp, vp, vp, vp, vp,                                    # nrows1, cap1, kps_un1, kps1, counts1, uright1, depth1, tcw1, ow1
+            ci, ci, vp, vp, vp, vp, vp, vp, vp,                                    # pool 2
+            vp, vp, vp, vp, vp, cf, cf, cf,                                        # row1, row2, matches12, k1, k2 (host), mb1, mbf1, mb2
+            vp, vp, vp, vp, ci, cf, cf,                                            # scale factors / level sigma2 of both sides (host), nlevels, ratio_factor, th_far
+            vp, vp, vp, vp, vp, vp, vp]                                            # won_pair, won_idx2, x3d, reason, ncreated, order, ntotal
+    L.orbm_triangulate_new_points_batch_async.argtypes = [vp] + _tri
+    L.orbm_triangulate_new_points.argtypes = [vp, ci] + _tri                       # handle, space
     L.orbm_is_in_frustum_batch_async.argtypes = [vp, ci, vp, vp, vp, ci, vp,                 # nframes, tcw, ow, nq, q_stride, skip
                                                  vp, vp, vp, vp, ci,                         # pw, normal, min_dist, max_dist, q_shared
                                                  vp, vp, cf, cf, cf, ci,                     # k, bounds (host), bf, cos limit, log scale factor, levels
@@ -1278,6 +1287,61 @@ def _install_search():
                                                              int(clear_bad), mp_seen, n_matches_map, n_discarded),
                     "orbm_discard_outliers_batch_async")
 
+    def _tri_tables(k1, k2, sf1, ls1, sf2, ls2):
+        t = [np.ascontiguousarray(a, np.float32) for a in (k1, k2, sf1, ls1, sf2, ls2)]
+        if len(t[0]) != 6 or len(t[1]) != 6 or not (len(t[2]) == len(t[3]) == len(t[4]) == len(t[5])):
+            raise OrbError("k1, k2 are (fx, fy, cx, cy, invfx, invfy); the four level tables hold nlevels entries each")
+        return t
+
+    def triangulate_new_points(self, group_start, pool1, pool2, row1, row2, matches12, k1, k2, mb1, mbf1, mb2, sf1, ls1, sf2, ls2, ratio_factor,
+                               th_far=0.0, want_reason=True):
+        """Step 6 of LocalMapping::CreateNewMapPoints (LocalMapping.cc:609-892) for M10's matches12 [npairs][cap1], host arrays in and out.
+        pool = dict(kps_un [rows][cap] KP_DTYPE, counts [rows], tcw [rows][12], ow [rows][3], and optionally kps (mvKeys), uright, depth);
+        pool2 may be pool1.  -> dict of won_pair, won_idx2 [ngroups][cap1], x3d [ngroups][cap1][3], reason [npairs][cap1] (or None), ncreated
+        [npairs], order [ngroups][cap1], ntotal [ngroups] (include/orbm.h: orbm_triangulate_new_points)."""
+        gs = np.ascontiguousarray(group_start, np.int32); ng = len(gs) - 1
+        m12 = np.ascontiguousarray(matches12, np.int32); npairs, cap1 = m12.shape
+        r1 = np.ascontiguousarray(row1, np.int32); r2 = np.ascontiguousarray(row2, np.int32)
+        def flat(pool):
+            kp = np.ascontiguousarray(pool["kps_un"], KP_DTYPE); rows, cap = kp.shape
+            d = {"rows": rows, "cap": cap, "kps_un": kp, "counts": np.ascontiguousarray(pool["counts"], np.int32),
+                 "tcw": np.ascontiguousarray(pool["tcw"], np.float32).reshape(rows, 12), "ow": np.ascontiguousarray(pool["ow"], np.float32).reshape(rows, 3)}
+            d["kps"] = None if pool.get("kps") is None else np.ascontiguousarray(pool["kps"], KP_DTYPE)
+            for key in ("uright", "depth"):
+                d[key] = None if pool.get(key) is None else np.ascontiguousarray(pool[key], np.float32)
+                if d[key] is not None and d[key].shape != kp.shape: raise OrbError("%s is [rows][cap]" % key)
+            if d["kps"] is not None and d["kps"].shape != kp.shape: raise OrbError("kps is [rows][cap]")
+            return d
+        a = flat(pool1); b = a if pool2 is pool1 else flat(pool2)
+        if a["cap"] != cap1 or len(r1) != npairs or len(r2) != npairs or ng < 0:
+            raise OrbError("matches12 is [npairs][cap1]; row1, row2 hold one entry per pair; group_start holds ngroups + 1")
+        t = _tri_tables(k1, k2, sf1, ls1, sf2, ls2)
+        ngo = max(ng, 1)
+        out = {"won_pair": np.full((ngo, cap1), -2, np.int32), "won_idx2": np.full((ngo, cap1), -2, np.int32), "x3d": np.zeros((ngo, cap1, 3), np.float32),
+               "reason": np.full((npairs, cap1), 255, np.uint8) if want_reason else None, "ncreated": np.full(max(npairs, 1), -2, np.int32),
+               "order": np.full((ngo, cap1), -2, np.int32), "ntotal": np.full(ngo, -2, np.int32)}
+        q = lambda x: None if x is None else _p(x)
+        pa = lambda d: (d["rows"], d["cap"], _p(d["kps_un"]), q(d["kps"]), _p(d["counts"]), q(d["uright"]), q(d["depth"]), _p(d["tcw"]), _p(d["ow"]))
+        _chk(self.L.orbm_triangulate_new_points(self.h, HOST, ng, _p(gs), npairs, *pa(a), *pa(b), _p(r1), _p(r2), _p(m12), _p(t[0]), _p(t[1]),
+                                                float(mb1), float(mbf1), float(mb2), _p(t[2]), _p(t[3]), _p(t[4]), _p(t[5]), len(t[2]),
+                                                float(ratio_factor), float(th_far), _p(out["won_pair"]), _p(out["won_idx2"]), _p(out["x3d"]),
+                                                q(out["reason"]), _p(out["ncreated"]), _p(out["order"]), _p(out["ntotal"])),
+             "orbm_triangulate_new_points")
+        return out
+
+    def triangulate_new_points_batch_async(self, group_start, npairs, pool1, pool2, row1, row2, matches12, k1, k2, mb1, mbf1, mb2, sf1, ls1, sf2, ls2,
+                                           ratio_factor, th_far, won_pair, won_idx2, x3d, reason, ncreated, order, ntotal):
+        """Device form, enqueue only: pool = (nrows, cap, kps_un, kps, counts, uright, depth, tcw, ow) of device pointers, every other array
+        argument is a device pointer except group_start, k1, k2 and the four level tables, which are host arrays (include/orbm.h:
+        orbm_triangulate_new_points_batch_async)."""
+        gs = np.ascontiguousarray(group_start, np.int32)
+        t = _tri_tables(k1, k2, sf1, ls1, sf2, ls2)
+        return _chk(self.L.orbm_triangulate_new_points_batch_async(self.h, len(gs) - 1, _p(gs), npairs, *pool1, *pool2, row1, row2, matches12,
+                                                                   _p(t[0]), _p(t[1]), float(mb1), float(mbf1), float(mb2), _p(t[2]), _p(t[3]),
+                                                                   _p(t[4]), _p(t[5]), len(t[2]), float(ratio_factor), float(th_far), won_pair,
+                                                                   won_idx2, x3d, reason, ncreated, order, ntotal),
+                    "orbm_triangulate_new_points_batch_async")
+
     def is_in_frustum_batch(self, nframes, tcw, ow, nq, q_stride, skip, pw, normal, min_dist, max_dist, q_shared, K, bounds, bf, viewing_cos_limit,
                             log_scale_factor, n_levels, in_view, proj_x, proj_y, proj_xr, depth, level, view_cos, n_in_view=None):
         """Frame::isInFrustum for every frame of a batch in one launch, enqueue only: every array argument is a device pointer except K =
@@ -1302,6 +1366,8 @@ def _install_search():
     ORBmatcher.PoseOptimization = pose_optimization
     ORBmatcher.PoseOptimizationBatchAsync = pose_optimization_batch_async
     ORBmatcher.DiscardOutliersBatchAsync = discard_outliers_batch_async
+    ORBmatcher.TriangulateNewPoints = triangulate_new_points
+    ORBmatcher.TriangulateNewPointsBatchAsync = triangulate_new_points_batch_async
     ORBmatcher.ComputeDistinctiveDescriptors = distinctive_descriptors
     ORBmatcher.ComputeDistinctiveDescriptorsBatchAsync = distinctive_descriptors_batch_async
     ORBmatcher.UpdateNormalAndDepth = update_normal_and_depth
@@ -1397,6 +1463,7 @@ EXPORTS += ["orbm_grid_build", "orbm_window_candidates", "orbm_search_by_project
             "orbm_covisibility_votes", "orbm_covisibility_votes_batch_async", "orbm_local_points", "orbm_local_points_batch_async",
             "orbm_gather_map_points_batch_async",
             "orbm_pose_optimization", "orbm_pose_optimization_batch_async", "orbm_discard_outliers_batch_async",
+            "orbm_triangulate_new_points", "orbm_triangulate_new_points_batch_async",
             "orbm_vocab_load_text", "orbm_vocab_create", "orbm_vocab_destroy", "orbm_vocab_info", "orbm_bow_transform", "orbm_bow_vectors"]
 _orig_lib = lib
 _search_ready = False

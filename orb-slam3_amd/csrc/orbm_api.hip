@@ -3318,4 +3318,173 @@ int orbm_discard_outliers_batch_async(orbm_t* m, int nframes, int cap, const int
     return ORBM_OK;
 }
 
+// ---- CreateNewMapPoints behind M10: the parallax tests, the triangulation, the gates and the creation order (LocalMapping.cc:609-892) ----
+struct TriPoolArgs {
+    int nrows, cap; const orbm_kp_t* kps_un; const orbm_kp_t* kps; const int32_t* counts; const float* uright; const float* depth;
+    const float* tcw; const float* ow;
+};
+struct TriOutArgs { int32_t* won_pair; int32_t* won_idx2; float* x3d; uint8_t* reason; int32_t* ncreated; int32_t* order; int32_t* ntotal; };
+
+// the argument tests both forms share; fills the kernels' parameter block (pointers and group_start still unset)
+static int tri_args(const char* who, orbm_t* m, int ngroups, const int32_t* group_start, int npairs, const TriPoolArgs& a, const TriPoolArgs& b,
+                    const int32_t* row1, const int32_t* row2, const int32_t* matches12, const float* k1, const float* k2,
+                    const float* sf1, const float* ls1, const float* sf2, const float* ls2, int nlevels, float ratio_factor, const TriOutArgs& o,
+                    TriNewParams& P) {
+    if (const int rc = covis_handle(who, m)) return rc;
+    const struct { const void* p; const char* name; } req[] = {
+        {group_start, "group_start"}, {a.kps_un, "kps_un1"}, {a.counts, "counts1"}, {a.tcw, "tcw1"}, {a.ow, "ow1"},
+        {b.kps_un, "kps_un2"}, {b.counts, "counts2"}, {b.tcw, "tcw2"}, {b.ow, "ow2"}, {row1, "row1"}, {row2, "row2"}, {matches12, "matches12"},
+        {k1, "k1_host"}, {k2, "k2_host"}, {sf1, "scale_factors1_host"}, {ls1, "level_sigma2_1_host"}, {sf2, "scale_factors2_host"},
+        {ls2, "level_sigma2_2_host"}, {o.won_pair, "won_pair"}, {o.won_idx2, "won_idx2"}, {o.x3d, "x3d"}, {o.ncreated, "ncreated"},
+        {o.order, "order"}, {o.ntotal, "ntotal"}};
+    for (const auto& r : req)
+        if (!r.p) { set_merr("%s: %s is NULL", who, r.name); return ORBM_E_INVALID; }
+    if (ngroups < 1 || npairs < 1 || a.nrows < 1 || a.cap < 1 || b.nrows < 1 || b.cap < 1 || nlevels < 1) {
+        set_merr("%s: ngroups, npairs, nrows1, cap1, nrows2, cap2 and nlevels must be >= 1", who);
+        return ORBM_E_INVALID;
+    }
+    if (!std::isfinite(ratio_factor)) { set_merr("%s: ratio_factor is not finite", who); return ORBM_E_INVALID; }
+    if (a.cap > ORBM_TRI_MAX_CAP || b.cap > ORBM_TRI_MAX_CAP || npairs > ORBM_TRI_MAX_PAIRS) {
+        set_merr("%s: cap1 %d, cap2 %d, npairs %d (at most %d, %d, %d)", who, a.cap, b.cap, npairs, (int)ORBM_TRI_MAX_CAP, (int)ORBM_TRI_MAX_CAP,
+                 (int)ORBM_TRI_MAX_PAIRS);
+        return ORBM_E_CAPACITY;
+    }
+    if (nlevels > ORBM_TRI_MAX_LEVELS) { set_merr("%s: %d pyramid levels (at most %d)", who, nlevels, (int)ORBM_TRI_MAX_LEVELS); return ORBM_E_CAPACITY; }
+    if (ngroups > npairs || group_start[0] != 0 || group_start[ngroups] != npairs) {
+        set_merr("%s: group_start must run from 0 to npairs over at most npairs groups", who);
+        return ORBM_E_INVALID;
+    }
+    for (int g = 0; g < ngroups; ++g) {
+        const long long n = (long long)group_start[g + 1] - group_start[g];
+        if (n < 0 || group_start[g + 1] > npairs) { set_merr("%s: group_start is not monotone at group %d", who, g); return ORBM_E_INVALID; }
+        if (n > ORBM_TRI_MAX_GROUP_PAIRS) { set_merr("%s: group %d holds %lld pairs (at most %d)", who, g, n, (int)ORBM_TRI_MAX_GROUP_PAIRS); return ORBM_E_CAPACITY; }
+    }
+    static_assert(ORBM_TRI_MAX_LEVELS == TRI_MAX_LEVELS && ORBM_TRI_MAX_GROUP_PAIRS == TRI_MAX_GROUP_PAIRS, "the kernels' tables");
+    P = TriNewParams{};
+    P.npairs = npairs; P.nlevels = nlevels; P.ratio_factor = ratio_factor;
+    P.k1 = TriCam{k1[0], k1[1], k1[2], k1[3], k1[4], k1[5]}; P.k2 = TriCam{k2[0], k2[1], k2[2], k2[3], k2[4], k2[5]};
+    for (int i = 0; i < TRI_MAX_LEVELS; ++i) {
+        P.sf1[i] = i < nlevels ? sf1[i] : 1.0f; P.ls1[i] = i < nlevels ? ls1[i] : 1.0f;
+        P.sf2[i] = i < nlevels ? sf2[i] : 1.0f; P.ls2[i] = i < nlevels ? ls2[i] : 1.0f;
+    }
+    return ORBM_OK;
+}
+
+static TriPool tri_pool(const TriPoolArgs& a) {
+    const KpIn* un = (const KpIn*)a.kps_un;
+    return TriPool{a.nrows, a.cap, un, a.kps ? (const KpIn*)a.kps : un, a.counts, a.uright, a.depth, a.tcw, a.ow};
+}
+
+// TRI_GROUPS_PER_LAUNCH groups per launch pair: group_start rides in the kernel arguments, so nothing is staged or allocated
+static int tri_launch(orbm_t* m, int ngroups, const int32_t* group_start, TriNewParams& P, const TriPoolArgs& a, const TriPoolArgs& b,
+                      const int32_t* row1, const int32_t* row2, const int32_t* matches12, const TriOutArgs& o) {
+    P.p1 = tri_pool(a); P.p2 = tri_pool(b); P.row1 = row1; P.row2 = row2; P.matches12 = matches12;
+    P.won_pair = o.won_pair; P.won_idx2 = o.won_idx2; P.x3d = o.x3d; P.reason = o.reason; P.ncreated = o.ncreated; P.order = o.order; P.ntotal = o.ntotal;
+    for (int g0 = 0; g0 < ngroups; g0 += TRI_GROUPS_PER_LAUNCH) {
+        const int ng = std::min(ngroups - g0, (int)TRI_GROUPS_PER_LAUNCH);
+        P.g0 = g0;
+        for (int i = 0; i <= TRI_GROUPS_PER_LAUNCH; ++i) P.gstart[i] = group_start[g0 + std::min(i, ng)];
+        hipLaunchKernelGGL(k_triangulate_new, dim3((a.cap + 255) / 256, ng), dim3(256), 0, m->stream, P);
+        hipLaunchKernelGGL(k_triangulate_order, dim3(ng), dim3(64), 0, m->stream, P);
+    }
+    MHIPCHK(hipGetLastError());
+    return ORBM_OK;
+}
+
+int orbm_triangulate_new_points_batch_async(orbm_t* m, int ngroups, const int32_t* group_start_host, int npairs,
+                                            int nrows1, int cap1, const orbm_kp_t* kps_un1, const orbm_kp_t* kps1, const int32_t* counts1,
+                                            const float* uright1, const float* depth1, const float* tcw1, const float* ow1,
+                                            int nrows2, int cap2, const orbm_kp_t* kps_un2, const orbm_kp_t* kps2, const int32_t* counts2,
+                                            const float* uright2, const float* depth2, const float* tcw2, const float* ow2,
+                                            const int32_t* row1, const int32_t* row2, const int32_t* matches12,
+                                            const float* k1_host, const float* k2_host, float mb1, float mbf1, float mb2,
+                                            const float* scale_factors1_host, const float* level_sigma2_1_host,
+                                            const float* scale_factors2_host, const float* level_sigma2_2_host,
+                                            int nlevels, float ratio_factor, float th_far,
+                                            int32_t* won_pair, int32_t* won_idx2, float* x3d, uint8_t* reason, int32_t* ncreated,
+                                            int32_t* order, int32_t* ntotal) {
+    const TriPoolArgs a{nrows1, cap1, kps_un1, kps1, counts1, uright1, depth1, tcw1, ow1}, b{nrows2, cap2, kps_un2, kps2, counts2, uright2, depth2, tcw2, ow2};
+    const TriOutArgs o{won_pair, won_idx2, x3d, reason, ncreated, order, ntotal};
+    TriNewParams P;
+    const int rc = tri_args("TriangulateNewPoints batch", m, ngroups, group_start_host, npairs, a, b, row1, row2, matches12, k1_host, k2_host,
+                            scale_factors1_host, level_sigma2_1_host, scale_factors2_host, level_sigma2_2_host, nlevels, ratio_factor, o, P);
+    if (rc) return rc;
+    P.mb1 = mb1; P.mbf1 = mbf1; P.mb2 = mb2; P.th_far = th_far;
+    MHIPCHK(hipSetDevice(m->device));
+    return tri_launch(m, ngroups, group_start_host, P, a, b, row1, row2, matches12, o);
+}
+
+int orbm_triangulate_new_points(orbm_t* m, int space, int ngroups, const int32_t* group_start_host, int npairs,
+                                int nrows1, int cap1, const orbm_kp_t* kps_un1, const orbm_kp_t* kps1, const int32_t* counts1,
+                                const float* uright1, const float* depth1, const float* tcw1, const float* ow1,
+                                int nrows2, int cap2, const orbm_kp_t* kps_un2, const orbm_kp_t* kps2, const int32_t* counts2,
+                                const float* uright2, const float* depth2, const float* tcw2, const float* ow2,
+                                const int32_t* row1, const int32_t* row2, const int32_t* matches12,
+                                const float* k1_host, const float* k2_host, float mb1, float mbf1, float mb2,
+                                const float* scale_factors1_host, const float* level_sigma2_1_host,
+                                const float* scale_factors2_host, const float* level_sigma2_2_host,
+                                int nlevels, float ratio_factor, float th_far,
+                                int32_t* won_pair, int32_t* won_idx2, float* x3d, uint8_t* reason, int32_t* ncreated,
+                                int32_t* order, int32_t* ntotal) {
+    const char* who = "TriangulateNewPoints";
+    if (space != ORBM_HOST && space != ORBM_DEVICE) {
+        if (const int rc = covis_handle(who, m)) return rc;
+        set_merr("%s: space must be ORBM_HOST or ORBM_DEVICE", who);
+        return ORBM_E_INVALID;
+    }
+    TriPoolArgs a{nrows1, cap1, kps_un1, kps1, counts1, uright1, depth1, tcw1, ow1}, b{nrows2, cap2, kps_un2, kps2, counts2, uright2, depth2, tcw2, ow2};
+    TriOutArgs o{won_pair, won_idx2, x3d, reason, ncreated, order, ntotal};
+    TriNewParams P;
+    int rc = tri_args(who, m, ngroups, group_start_host, npairs, a, b, row1, row2, matches12, k1_host, k2_host, scale_factors1_host,
+                      level_sigma2_1_host, scale_factors2_host, level_sigma2_2_host, nlevels, ratio_factor, o, P);
+    if (rc) return rc;
+    P.mb1 = mb1; P.mbf1 = mbf1; P.mb2 = mb2; P.th_far = th_far;
+    MHIPCHK(hipSetDevice(m->device));
+    if (space == ORBM_DEVICE) {
+        rc = tri_launch(m, ngroups, group_start_host, P, a, b, row1, row2, matches12, o);
+        if (rc) return rc;
+        MHIPCHK(hipStreamSynchronize(m->stream));
+        return ORBM_OK;
+    }
+    for (int g = 0; g < ngroups; ++g)                          // readable here: a group is the pairs of ONE current KeyFrame
+        for (int p = group_start_host[g] + 1; p < group_start_host[g + 1]; ++p)
+            if (row1[p] != row1[group_start_host[g]]) { set_merr("%s: the pairs of group %d do not share one row1", who, g); return ORBM_E_INVALID; }
+    const size_t s1 = (size_t)nrows1 * cap1, s2 = (size_t)nrows2 * cap2, so = (size_t)ngroups * cap1, sp = (size_t)npairs * cap1;
+    // pool 2 may be pool 1 (one pool passed twice): each distinct host array goes up once
+    const bool samePool = nrows1 == nrows2 && cap1 == cap2 && kps_un1 == kps_un2 && kps1 == kps2 && counts1 == counts2 && uright1 == uright2 &&
+                          depth1 == depth2 && tcw1 == tcw2 && ow1 == ow2;
+    DevBuf du1, dk1, dc1, dr1, dd1, dt1, do1, du2, dk2, dc2, dr2, dd2, dt2, do2, drow1, drow2, dm, dwp, dwi, dx, dre, dnc, dord, dnt;
+    arena_reset(m);
+    UP(du1, kps_un1, sizeof(KpIn) * s1); UP(dc1, counts1, sizeof(int32_t) * nrows1); UP(dt1, tcw1, sizeof(float) * 12 * nrows1); UP(do1, ow1, sizeof(float) * 3 * nrows1);
+    if (kps1 && kps1 != kps_un1) UP(dk1, kps1, sizeof(KpIn) * s1);
+    if (uright1) UP(dr1, uright1, sizeof(float) * s1);
+    if (depth1) UP(dd1, depth1, sizeof(float) * s1);
+    if (!samePool) {
+        UP(du2, kps_un2, sizeof(KpIn) * s2); UP(dc2, counts2, sizeof(int32_t) * nrows2); UP(dt2, tcw2, sizeof(float) * 12 * nrows2); UP(do2, ow2, sizeof(float) * 3 * nrows2);
+        if (kps2 && kps2 != kps_un2) UP(dk2, kps2, sizeof(KpIn) * s2);
+        if (uright2) UP(dr2, uright2, sizeof(float) * s2);
+        if (depth2) UP(dd2, depth2, sizeof(float) * s2);
+    }
+    UP(drow1, row1, sizeof(int32_t) * npairs); UP(drow2, row2, sizeof(int32_t) * npairs); UP(dm, matches12, sizeof(int32_t) * sp);
+    AL(dwp, sizeof(int32_t) * so); AL(dwi, sizeof(int32_t) * so); AL(dx, sizeof(float) * 3 * so); AL(dnc, sizeof(int32_t) * npairs);
+    AL(dord, sizeof(int32_t) * so); AL(dnt, sizeof(int32_t) * ngroups);
+    if (reason) AL(dre, sp);
+    ARENA_FLUSH(m);
+    a = TriPoolArgs{nrows1, cap1, (const orbm_kp_t*)du1.ptr(), kps1 && kps1 != kps_un1 ? (const orbm_kp_t*)dk1.ptr() : nullptr, dc1.as<int32_t>(),
+                    uright1 ? dr1.as<float>() : nullptr, depth1 ? dd1.as<float>() : nullptr, dt1.as<float>(), do1.as<float>()};
+    if (samePool) b = a;
+    else b = TriPoolArgs{nrows2, cap2, (const orbm_kp_t*)du2.ptr(), kps2 && kps2 != kps_un2 ? (const orbm_kp_t*)dk2.ptr() : nullptr, dc2.as<int32_t>(),
+                         uright2 ? dr2.as<float>() : nullptr, depth2 ? dd2.as<float>() : nullptr, dt2.as<float>(), do2.as<float>()};
+    o = TriOutArgs{dwp.as<int32_t>(), dwi.as<int32_t>(), dx.as<float>(), reason ? dre.as<uint8_t>() : nullptr, dnc.as<int32_t>(), dord.as<int32_t>(),
+                   dnt.as<int32_t>()};
+    rc = tri_launch(m, ngroups, group_start_host, P, a, b, drow1.as<int32_t>(), drow2.as<int32_t>(), dm.as<int32_t>(), o);
+    if (rc) return rc;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    ARENA_FETCH(m);
+    memcpy(won_pair, dwp.host(), sizeof(int32_t) * so); memcpy(won_idx2, dwi.host(), sizeof(int32_t) * so); memcpy(x3d, dx.host(), sizeof(float) * 3 * so);
+    memcpy(ncreated, dnc.host(), sizeof(int32_t) * npairs); memcpy(order, dord.host(), sizeof(int32_t) * so); memcpy(ntotal, dnt.host(), sizeof(int32_t) * ngroups);
+    if (reason) memcpy(reason, dre.host(), sp);
+    return ORBM_OK;
+}
+
 }  // extern "C"

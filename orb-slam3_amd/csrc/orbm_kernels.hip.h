@@ -5,6 +5,8 @@
 #include <stdint.h>
 #define PO_FN __host__ __device__ static inline
 #include "orbm_poseopt.h"          // the arithmetic of k_pose_opt, shared with the host tests
+#define TRI_FN __host__ __device__ static inline
+#include "orbm_triangulate.h"      // the arithmetic of k_triangulate_new, shared with the host tests
 
 namespace orbmk {
 
@@ -5415,6 +5417,149 @@ __global__ __launch_bounds__(256) void k_discard_outliers(DiscardParams P) {
         if (P.n_matches_map && bm) atomicAdd(&P.n_matches_map[f], __popcll(bm));
         if (P.n_discarded && bg) atomicAdd(&P.n_discarded[f], __popcll(bg));
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// k_triangulate_new / k_triangulate_order: step 6 of LocalMapping::CreateNewMapPoints (LocalMapping.cc:609-892) behind M10's matches12.
+// The per-match arithmetic is tri_one_match of orbm_triangulate.h, which the host tests compile too; this file supplies the walk.
+//   k_triangulate_new    one lane per idx1 of the group's current KeyFrame (row1 of its pairs), 256 lanes per workgroup, grid.y = group.
+//            The lane walks the group's pairs IN ORDER, reads matches12[p][idx1] (lane-consecutive) and stops trying at the first pair
+//            whose match passes every gate: that loop IS the cross-pair rule -- a later pair's match for this idx1 is
+//            dropped (TRI_TAKEN) exactly where the reference's search would have skipped a feature that holds a MapPoint.  No flag array,
+//            no atomics.  The pair's pose, row and count are the same for every lane (uniform addresses); the level tables are copied to
+//            LDS once because the octave indexes them per lane.  The 4x4, its V and the rotations live in registers (four named columns
+//            each, constant indices after inlining).
+//   k_triangulate_order  ONE wave per group.  The reference creates MapPoints pair by pair and inside a pair in ascending idx1
+//            (ORBmatcher.cc, end of SearchForTriangulation_).  Lane L keeps the count of the group's pair L in a register (at most 64
+//            pairs per group); the wave walks won_pair in chunks of 64 idx1, and per distinct pair of the chunk a ballot gives the count
+//            and the rank of each lane among the lanes of the same pair.  Pass 1 counts, a wave scan over the lanes gives each pair's base,
+//            pass 2 stores idx1 at base + running count + rank.  Every count starts from zero in the kernel, nothing is atomic: a replay
+//            repeats its result.  The tail of `order` past ntotal is filled with -1.
+// group_start travels in the kernel arguments (TRI_GROUPS_PER_LAUNCH groups per launch): the host checked it, the kernels trust it.
+// ------------------------------------------------------------------------------------------------
+#define TRI_GROUPS_PER_LAUNCH 128
+#define TRI_MAX_GROUP_PAIRS 64
+struct TriPool {
+    int nrows, cap;
+    const KpIn* kps_un; const KpIn* kps; const int* counts; const float* uright; const float* depth; const float* tcw; const float* ow;
+};
+struct TriNewParams {
+    int g0, npairs, nlevels;                                  // first group of this launch
+    float mb1, mbf1, mb2, ratio_factor, th_far;
+    TriCam k1, k2;
+    float sf1[TRI_MAX_LEVELS], ls1[TRI_MAX_LEVELS], sf2[TRI_MAX_LEVELS], ls2[TRI_MAX_LEVELS];
+    int gstart[TRI_GROUPS_PER_LAUNCH + 1];
+    TriPool p1, p2;
+    const int* row1; const int* row2; const int* matches12;
+    int* won_pair; int* won_idx2; float* x3d; uint8_t* reason; int* ncreated; int* order; int* ntotal;
+};
+
+__device__ __forceinline__ void tri_load_pose(const TriPool& pool, int row, TriPose& P) {
+#pragma unroll
+    for (int i = 0; i < 12; ++i) P.T[i] = pool.tcw[12 * (size_t)row + i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) P.ow[i] = pool.ow[3 * (size_t)row + i];
+}
+__device__ __forceinline__ void tri_load_obs(const TriPool& pool, int row, int i, TriObs& o) {
+    const size_t s = (size_t)row * pool.cap + i;
+    const KpIn& ku = pool.kps_un[s];
+    o.ux = ku.x; o.uy = ku.y; o.octave = ku.octave;
+    if (pool.kps != pool.kps_un) { const KpIn& k = pool.kps[s]; o.kx = k.x; o.ky = k.y; } else { o.kx = o.ux; o.ky = o.uy; }
+    o.uright = pool.uright ? pool.uright[s] : -1.f;
+    o.depth = pool.depth ? pool.depth[s] : -1.f;
+}
+
+__global__ __launch_bounds__(256) void k_triangulate_new(TriNewParams P) {
+    __shared__ float sTab[4 * TRI_MAX_LEVELS];
+    const int tid = threadIdx.x, g = blockIdx.y;
+    if (tid < TRI_MAX_LEVELS) {
+        sTab[tid] = P.sf1[tid]; sTab[TRI_MAX_LEVELS + tid] = P.ls1[tid];
+        sTab[2 * TRI_MAX_LEVELS + tid] = P.sf2[tid]; sTab[3 * TRI_MAX_LEVELS + tid] = P.ls2[tid];
+    }
+    __syncthreads();
+    const int pBeg = P.gstart[g], pEnd = P.gstart[g + 1];
+    const int cap1 = P.p1.cap, idx1 = blockIdx.x * 256 + tid;
+    if (idx1 >= cap1) return;                                 // no barrier below
+    const size_t gout = (size_t)(P.g0 + g) * cap1 + idx1;
+    int won = -1, wonIdx2 = -1;
+    float wx = 0.f, wy = 0.f, wz = 0.f;
+    if (pBeg < pEnd) {
+        const int r1 = P.row1[pBeg];
+        bool mixed = false;
+        for (int p = pBeg + 1; p < pEnd; ++p) mixed = mixed || P.row1[p] != r1;
+        const bool ok1 = (unsigned)r1 < (unsigned)P.p1.nrows && !mixed;
+        const int n1 = ok1 ? min(max(P.p1.counts[r1], 0), cap1) : 0;
+        TriPose pose1; TriObs o1;
+        if (ok1) tri_load_pose(P.p1, r1, pose1);
+        const bool live = idx1 < n1;
+        if (live) tri_load_obs(P.p1, r1, idx1, o1);
+        for (int p = pBeg; p < pEnd; ++p) {
+            const int r2 = P.row2[p];
+            const bool ok2 = (unsigned)r2 < (unsigned)P.p2.nrows;
+            const int n2 = ok2 ? min(max(P.p2.counts[r2], 0), P.p2.cap) : 0;
+            const int m = live ? P.matches12[(size_t)p * cap1 + idx1] : -1;
+            int r = mixed ? TRI_MIXED_ROW1 : TRI_NO_MATCH;
+            if ((unsigned)m < (unsigned)n2) {                 // garbage (< -1, >= the row's count) reads as no match and is never dereferenced
+                if (won >= 0) r = TRI_TAKEN;
+                else {
+                    TriPose pose2; TriObs o2;
+                    tri_load_pose(P.p2, r2, pose2);
+                    tri_load_obs(P.p2, r2, m, o2);
+                    float x[3];
+                    r = tri_one_match(P.k1, P.k2, P.mb1, P.mbf1, P.mb2, pose1, pose2, o1, o2, sTab, sTab + TRI_MAX_LEVELS, sTab + 2 * TRI_MAX_LEVELS,
+                                      sTab + 3 * TRI_MAX_LEVELS, P.nlevels, P.ratio_factor, P.th_far, x);
+                    if (tri_ok(r)) { won = p; wonIdx2 = m; wx = x[0]; wy = x[1]; wz = x[2]; }
+                }
+            }
+            if (P.reason) P.reason[(size_t)p * cap1 + idx1] = (uint8_t)r;
+        }
+    }
+    P.won_pair[gout] = won; P.won_idx2[gout] = wonIdx2;
+    P.x3d[3 * gout] = wx; P.x3d[3 * gout + 1] = wy; P.x3d[3 * gout + 2] = wz;
+}
+
+__global__ __launch_bounds__(64) void k_triangulate_order(TriNewParams P) {
+    const int lane = threadIdx.x, g = blockIdx.x;
+    const int pBeg = P.gstart[g], np = min(P.gstart[g + 1] - pBeg, TRI_MAX_GROUP_PAIRS);
+    const int cap1 = P.p1.cap;
+    const size_t gout = (size_t)(P.g0 + g) * cap1;
+    const u64 below = lane ? (~0ull >> (64 - lane)) : 0ull;
+    int cnt = 0;
+    for (int c0 = 0; c0 < cap1; c0 += 64) {
+        const int idx = c0 + lane;
+        const int lp = (idx < cap1 ? P.won_pair[gout + idx] : -1) - pBeg;
+        const bool has = (unsigned)lp < (unsigned)np;
+        u64 rem = __ballot(has);
+        while (rem) {
+            const int pl = __shfl(lp, __ffsll(rem) - 1, 64);
+            const u64 mask = __ballot(has && lp == pl);
+            if (lane == pl) cnt += __popcll(mask);
+            rem &= ~mask;
+        }
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+    const int total = __shfl(incl, 63, 64);
+    if (lane < np) P.ncreated[pBeg + lane] = cnt;
+    if (lane == 0) P.ntotal[P.g0 + g] = total;
+    int run = incl - cnt;                                     // the pair's first position in `order`
+    for (int c0 = 0; c0 < cap1; c0 += 64) {
+        const int idx = c0 + lane;
+        const int lp = (idx < cap1 ? P.won_pair[gout + idx] : -1) - pBeg;
+        const bool has = (unsigned)lp < (unsigned)np;
+        u64 rem = __ballot(has);
+        while (rem) {
+            const int pl = __shfl(lp, __ffsll(rem) - 1, 64);
+            const bool mine = has && lp == pl;
+            const u64 mask = __ballot(mine);
+            const int at = __shfl(run, pl, 64) + __popcll(mask & below);
+            if (mine && at < cap1) P.order[gout + at] = idx;
+            if (lane == pl) run += __popcll(mask);
+            rem &= ~mask;
+        }
+    }
+    for (int i = total + lane; i < cap1; i += 64) P.order[gout + i] = -1;
 }
 
 }  // namespace orbmk
